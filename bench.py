@@ -28,6 +28,14 @@ GPU is touched; RCCL only with --dist-backend nccl).  A rank that fails
 leaves its error in the process group's store, and rank 0 prints one JSON
 line naming every failed rank.
 
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) sets up, warms up,
+times the N steps and prints the line.  --full adds everything beside the
+headline figure: the verification of the decoded data, a second pass of the
+steps under per-kernel HIP events (kernels, roofline, launch cost), the HBM
+streaming probe and the CPU baselines.  --dump-outputs DIR writes what the
+last timed step computed (dump_outputs below) for an output-for-output
+comparison of two builds.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -73,6 +81,15 @@ def parse(argv=None):
     p.add_argument("--symbol-size", type=int, default=None, help="override the config's symbol_size (L)")
     p.add_argument("--loss-rate", type=float, default=None, help="override the config's loss_rate")
     p.add_argument("--seed", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline figure: verification of the decoded data, the "
+                        "per-kernel pass and roofline figures, the launch cost, the HBM streaming "
+                        "probe and the CPU baselines (a plain run only sets up, warms up, times "
+                        "the steps and prints the line)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last step computed (parity and "
+                        "recovered symbols, a fixed seeded sample of at most 2^21 bytes each, and "
+                        "the per-block decode status) as DIR/<name>.npy in float32")
     p.add_argument("--decode-kernel", default="auto",
                    choices=["auto", "generated", "one_matrix", "general"])
     p.add_argument("--encode-kernel", default="auto",
@@ -685,6 +702,40 @@ def alg_bytes(k, e, L):
             "k_decode_prepare": 0.0, "k_decode_prepare_syn": 0.0}
 
 
+def verifying(args) -> bool:
+    """The decoded data is compared with the originals only under --full."""
+    return args.full and not args.no_verify
+
+
+DUMP_SAMPLE = 1 << 21  # bytes of each output array that --dump-outputs keeps
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(path, rank, world, enc, dec, blocks):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step -- the parity rows (encode_all) and the recovered rows (decode_all)
+    of the first `blocks` blocks, without the pitch padding, and the
+    per-block decode status -- as float32 .npy files (one set per rank).
+    An array of more than DUMP_SAMPLE bytes is sampled at DUMP_SAMPLE
+    positions drawn from a fixed seed: the same positions in every run of
+    the same geometry, so two builds compare output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    n = blocks * enc.e * enc.L
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+    else:
+        idx = np.arange(n, dtype=np.int64)
+    # position in the [blocks][e][L] array -> offset in the pitched rows
+    off = torch.from_numpy(idx // enc.L * enc.pitch + idx % enc.L).to(enc.par.device)
+    for name, buf in (("parity", enc.par), ("recovered", dec.out)):
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), buf[off].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, f"decode_status{sfx}.npy"),
+            dec.status[:blocks].cpu().numpy().astype(np.float32))
+
+
 def run_streamed(args, rsgpu, ctx, dev, rank, world, k, e, L, total_blocks):
     """C4: this rank's share of `total_blocks` blocks streamed through two
     resident batches.  Per batch: sources generated on the device and the
@@ -768,7 +819,7 @@ def run_streamed(args, rsgpu, ctx, dev, rank, world, k, e, L, total_blocks):
         ctx.decode_blocks(k, e, L, enc.pitch, nb, enc.src, enc.par, dec.err, dec.out, dec.ws,
                           dec.status)
         ev_t[i][1].record(s_cmp)
-        if not args.no_verify:
+        if verifying(args):
             ctx.verify_blocks(k, e, L, enc.pitch, nb, enc.src, dec.out, dec.err, dec.mism)
             # fold this batch's mismatches (and failed blocks) into its slot
             with torch.cuda.stream(s_cmp):
@@ -780,6 +831,9 @@ def run_streamed(args, rsgpu, ctx, dev, rank, world, k, e, L, total_blocks):
             generate(i + 1)
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
+    if args.dump_outputs:  # the last batch's parity and recovered rows
+        last = nb_total - 1
+        dump_outputs(args.dump_outputs, rank, world, *sets[last & 1], min(batch, share - last * batch))
     per_batch = [a.elapsed_time(b) for a, b in ev_t]
     timed = sum(per_batch) * 1e-3
     recs = ctx.timing_read()
@@ -975,7 +1029,7 @@ def run_rank(args, rank, world, device_index, red_dev):
         bad_t = torch.tensor([float(bad)], dtype=torch.float64, device=red_dev)
         if world > 1:
             dist.all_reduce(bad_t)
-        ok = args.no_verify or bad_t.item() == 0
+        ok = not verifying(args) or bad_t.item() == 0
         steps = 1
         # every rank's share counts (shares differ by at most one block)
         out_bytes_step = 2.0 * e * L * B / world
@@ -1012,7 +1066,7 @@ def run_rank(args, rank, world, device_index, red_dev):
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
-        if not args.no_verify and args.warmup > 0:
+        if verifying(args) and args.warmup > 0:
             assert dec.is_complete(), "decode matrix singular"
             assert dec.verify_data(enc), "recovered symbols differ from the originals"
         torch.cuda.synchronize()
@@ -1025,21 +1079,25 @@ def run_rank(args, rank, world, device_index, red_dev):
             step()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, rank, world, enc, dec, B)
         if world > 1:
             dist.barrier()
-        # per-kernel HIP events in a second pass of the same steps: the two
-        # event records per launch cost host time that a short step (C2,
-        # ~60 us) would otherwise count
-        ctx.timing_read()  # drop anything recorded so far
-        ctx.timing_enable(True)
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        recs = ctx.timing_read()
-        ctx.timing_enable(False)
+        recs = []
+        if args.full:
+            # per-kernel HIP events in a second pass of the same steps: the two
+            # event records per launch cost host time that a short step (C2,
+            # ~60 us) would otherwise count
+            ctx.timing_read()  # drop anything recorded so far
+            ctx.timing_enable(True)
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            recs = ctx.timing_read()
+            ctx.timing_enable(False)
         elapsed = reduce_max_time(elapsed, world, red_dev)
         ok = True
-        if not args.no_verify:
+        if verifying(args):
             ok = dec.is_complete() and dec.verify_data(enc)
         if world > 1:  # the line rank 0 prints speaks for every rank's shard
             ok_t = torch.tensor([1.0 if ok else 0.0], dtype=torch.float64, device=red_dev)
@@ -1051,34 +1109,54 @@ def run_rank(args, rank, world, device_index, red_dev):
         ms_step = elapsed / steps * 1e3
         workload = (f"isa_throughput {args.config}{' (custom geometry)' if custom else ''}: symbols={k} symbol_size={L} loss_rate={loss} "
                     f"erased={e} blocks_per_gpu={B}")
-        # launches per step and what one launch costs on this stream (short
-        # steps: C2's two launches)
-        extra = {"launch": dict(launch_cost(torch), launches_per_step=round(len(recs) / steps, 2),
-                                step_us=round(ms_step * 1e3, 2))}
+        extra = {}
+        if args.full:
+            # launches per step and what one launch costs on this stream (short
+            # steps: C2's two launches)
+            extra = {"launch": dict(launch_cost(torch), launches_per_step=round(len(recs) / steps, 2),
+                                    step_us=round(ms_step * 1e3, 2))}
 
-    # this rank's blocks per step (C4: its share of the stream)
-    per, kernels = kernel_stats(recs, steps, alg, out_bytes_step / (2.0 * e * L) if args.config != "c4" else share)
-    # dominant kernel = the most device time per step
-    dom = max(per, key=lambda n: per[n][0])
-    tot, n, nb, passes = per[dom]
-    dom_ms = tot / n
-    dom_bytes = alg.get(dom, 0.0) * nb / n / passes  # algorithmic bytes per launch
-    achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
-    read_bytes = float(k * L) * nb / n / passes if alg.get(dom, 0.0) else 0.0
-    # PMC bytes per launch come from a separate rocprofv3 --pmc pass of the
-    # same command (counters cannot be read inside this timed run); only
-    # valid for the C3 workload they were measured on
-    traffic, traffic_src = None, None
-    if (args.traffic and os.path.exists(args.traffic) and args.config == "c3" and not args.blocks
-            and not custom):
-        traffic = json.load(open(args.traffic)).get(dom)
-        traffic_src = os.path.relpath(args.traffic, ROOT) if traffic is not None else None
-    valu = None
-    if (args.sq_counters and os.path.exists(args.sq_counters) and args.config == "c3"
-            and not args.blocks and not custom):
-        sq = sq_counters(args.sq_counters)
-        ceil = valu_ceiling(args.valu_ceiling)
-        valu = {kn: r for kn in per if (r := valu_roofline(sq, kn, ceil))}
+    # per-kernel and roofline figures, from the kernel records (a plain
+    # C2 / C3 / C5 run takes none: they come from --full's second pass)
+    kernels, roofline, achieved = {}, None, None
+    if recs:
+        # this rank's blocks per step (C4: its share of the stream)
+        per, kernels = kernel_stats(recs, steps, alg, out_bytes_step / (2.0 * e * L) if args.config != "c4" else share)
+        # dominant kernel = the most device time per step
+        dom = max(per, key=lambda n: per[n][0])
+        tot, n, nb, passes = per[dom]
+        dom_ms = tot / n
+        dom_bytes = alg.get(dom, 0.0) * nb / n / passes  # algorithmic bytes per launch
+        achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
+        read_bytes = float(k * L) * nb / n / passes if alg.get(dom, 0.0) else 0.0
+        # PMC bytes per launch come from a separate rocprofv3 --pmc pass of the
+        # same command (counters cannot be read inside this timed run); only
+        # valid for the C3 workload they were measured on
+        traffic, traffic_src = None, None
+        if (args.traffic and os.path.exists(args.traffic) and args.config == "c3" and not args.blocks
+                and not custom):
+            traffic = json.load(open(args.traffic)).get(dom)
+            traffic_src = os.path.relpath(args.traffic, ROOT) if traffic is not None else None
+        valu = None
+        if (args.sq_counters and os.path.exists(args.sq_counters) and args.config == "c3"
+                and not args.blocks and not custom):
+            sq = sq_counters(args.sq_counters)
+            ceil = valu_ceiling(args.valu_ceiling)
+            valu = {kn: r for kn in per if (r := valu_roofline(sq, kn, ceil))}
+        roofline = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1),
+                    "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
+                    "traffic_source": traffic_src,
+                    "alg_bytes_per_launch": dom_bytes, "avg_ms": round(dom_ms, 3),
+                    # north_star's HBM-read variant: only the k source rows read
+                    # per block count
+                    "frac_read": round(read_bytes / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
+                    # how close each kernel's VALU stream runs to issue
+                    # (SQ counters of the same workload, one pass)
+                    "valu": valu,
+                    "valu_source": (os.path.relpath(args.sq_counters, ROOT) if valu else None),
+                    "valu_ceiling_source": (os.path.relpath(args.valu_ceiling, ROOT)
+                                            if valu and valu_ceiling(args.valu_ceiling) else None)}
     op_bytes = float((k + e) * L) * (out_bytes_step / (2.0 * e * L))
     step_frac = (2 * op_bytes) / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBPS
 
@@ -1093,25 +1171,12 @@ def run_rank(args, rank, world, device_index, red_dev):
                    "decode_kernel": args.decode_kernel, "encode_kernel": args.encode_kernel},
         "hbm_roofline_frac_step": round(step_frac, 4),
         "kernels": kernels,
-        "verified": ok,
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 1),
-                     "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                     "traffic_source": traffic_src,
-                     "alg_bytes_per_launch": dom_bytes, "avg_ms": round(dom_ms, 3),
-                     # north_star's HBM-read variant: only the k source rows read
-                     # per block count
-                     "frac_read": round(read_bytes / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4),
-                     # how close each kernel's VALU stream runs to issue
-                     # (SQ counters of the same workload, one pass)
-                     "valu": valu,
-                     "valu_source": (os.path.relpath(args.sq_counters, ROOT) if valu else None),
-                     "valu_ceiling_source": (os.path.relpath(args.valu_ceiling, ROOT)
-                                             if valu and valu_ceiling(args.valu_ceiling) else None)},
+        "verified": ok if args.full else None,  # a plain run does not compare the data
+        "roofline": roofline,
         "cpu_baseline": None,
     }
     line.update(extra)
-    if rank == 0:  # after the timed region: what streaming reaches on this GPU
+    if args.full and rank == 0:  # after the timed region: what streaming reaches on this GPU
         probe = hbm_probe(dev)
         probe["frac_of_read2_write1"] = round(achieved / probe["read2_write1_GBps"], 4)
         line["roofline"]["measured_peak"] = probe
@@ -1122,7 +1187,7 @@ def run_rank(args, rank, world, device_index, red_dev):
         line["host_io"]["pipelined"] = host_io_pipelined(rsgpu, ctx, k, e, L, args.host_io,
                                                          args.seed)
         line["host_io"]["session"] = host_io_session(rsgpu, ctx, k, e, L, args.host_io, args.seed)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpus = host_cpus()
         threads = args.cpu_threads or cpus["usable"]
         host = {"cpu_model": cpu_model(), **cpus,

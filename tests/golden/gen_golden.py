@@ -1,4 +1,5 @@
-"""Generate tests/golden/golden.json from the REFERENCE's own ISA-L 2.13 base C.
+"""Generate tests/golden/golden.json and reference_random.json from the
+REFERENCE's own ISA-L 2.13 base C.
 
 Run in the container where /root/reference exists (oracle/Makefile compiles the
 reference sources into oracle/_ref/libisal_ref.so):
@@ -21,6 +22,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 
+import random_cases as rc_  # noqa: E402
 from oracle_lib import Reference  # noqa: E402
 from synth import erasure_pattern, synth_block  # noqa: E402
 
@@ -140,6 +142,22 @@ def main() -> None:
     path = os.path.join(HERE, "golden.json")
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+    # the reference's results on the seeded random cross-check inputs
+    # (random_cases.py), as digests; the encode matrix of a general case is
+    # the reference's own
+    rnd = {"generator": out["generator"], "reference": out["reference"],
+           "encode": [rc_.encode_result(ref, c) for c in rc_.encode_cases()],
+           "invert": [rc_.invert_result(ref, m) for m in rc_.invert_cases()],
+           "matrices": [rc_.matrices_result(ref, m, k) for m, k in rc_.MATRIX_SHAPES],
+           "general_decode_matrix": [
+               rc_.general_result(ref, ref.gen_rs_matrix(m, k) if kind == "rs"
+                                  else ref.gen_cauchy1_matrix(m, k), err)
+               for kind, k, m, err in rc_.general_cases()]}
+    path = os.path.join(HERE, "reference_random.json")
+    with open(path, "w") as f:
+        json.dump(rnd, f, indent=1)
     print("wrote", path, os.path.getsize(path), "bytes")
 
 

@@ -379,7 +379,7 @@ def test_bench_spawns_its_own_ranks():
     disjoint contiguous shards, erasure lists drawn from the global block
     index, n_gpus 2, verified."""
     line = run_bench(["--gpus", "2", "--same-device", "--config", "c3",
-                      "--blocks", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+                      "--blocks", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"])
     assert line["n_gpus"] == 2 and line["verified"]
     assert line["config"]["dist_backend"] == "gloo"
     ranks = sorted(line["ranks"], key=lambda r: r["rank"])
@@ -401,7 +401,7 @@ def test_bench_under_torch_distributed_run():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--same-device",
-           "--config", "c3", "--blocks", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--config", "c3", "--blocks", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -458,7 +458,7 @@ def test_bench_c4_streams_ragged_batches():
     """The streamed C4 path: 3 batches with a ragged tail (2500 blocks in
     batches of 1024), every batch verified on the device."""
     line = run_bench(["--config", "c4", "--blocks", "2500", "--batch", "1024", "--warmup", "1",
-                      "--no-cpu-baseline"])
+                      "--no-cpu-baseline", "--full"])
     assert line["verified"]
     st = line["streamed"]
     assert st["batches"] == 3 and st["blocks_total"] == 2500 and st["mismatch_bytes"] == 0
@@ -469,7 +469,7 @@ def test_bench_c2_line_prices_its_kernels():
     """The C2 line (one block: split encode + one-launch decode): verified,
     its roofline kernel the one-launch decode, every timed kernel priced
     (a kernel missing from bench.alg_bytes used to report 0 GB/s)."""
-    line = run_bench(["--config", "c2", "--steps", "20", "--warmup", "2", "--no-cpu-baseline"])
+    line = run_bench(["--config", "c2", "--steps", "20", "--warmup", "2", "--no-cpu-baseline", "--full"])
     assert line["verified"]
     assert set(line["kernels"]) == {"k_rs_bs_split(encode)", "k_rs_syn_split(decode)"}
     assert all(v["alg_GBps"] > 0 for v in line["kernels"].values())
@@ -477,6 +477,52 @@ def test_bench_c2_line_prices_its_kernels():
     assert rf["kernel"] in line["kernels"] and rf["achieved"] > 0 and 0 < rf["frac"] < 1
     la = line["launch"]  # one launch per op, and what a launch costs on the stream
     assert la["launches_per_step"] == 2 and la["empty_kernel_us_device"] > 0 and la["step_us"] > 0
+
+
+@pytest.mark.parametrize("blocks", [3, 5])
+def test_bench_plain_run_dumps_its_outputs(ctx, orc, tmp_path, blocks):
+    """A plain run (no --full) times exactly --steps steps and prints the
+    headline keys with no per-kernel pass, no verification and no baseline;
+    --dump-outputs writes float32 arrays that hold the last step's parity,
+    recovered rows and status: whole at 3 blocks (3 * 8 * 64000 bytes per
+    array), at the fixed seeded sample positions at 5 blocks (more than
+    bench.DUMP_SAMPLE bytes).  The parity is compared with the CPU oracle,
+    the recovered rows with the erased originals."""
+    import bench
+    k, e, L = 16, 8, 64000
+    out = tmp_path / "dump"
+    line = run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--symbols", str(k),
+                      "--symbol-size", str(L), "--loss-rate", "0.5", "--blocks", str(blocks),
+                      "--dump-outputs", str(out)])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+    assert line["unit"] == "GiB/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert line["metric"] == bench.METRIC
+    # value and ms_per_step describe the same timed steps (the line rounds
+    # ms_per_step to 1e-3 and value to 1e-2)
+    rel = 0.0005 / line["ms_per_step"] + 0.005 / line["value"] + 1e-6
+    assert line["value"] == pytest.approx(2.0 * e * L * blocks / (line["ms_per_step"] * 1e-3) / 2 ** 30,
+                                          rel=1.05 * rel)
+    assert line["kernels"] == {} and line["roofline"] is None and line["cpu_baseline"] is None
+    assert line["verified"] is None and "launch" not in line
+    assert sorted(os.listdir(out)) == ["decode_status.npy", "parity.npy", "recovered.npy"]
+    got = {n: np.load(out / f"{n}.npy") for n in ("parity", "recovered", "decode_status")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    n = blocks * e * L
+    if n > bench.DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, n, size=bench.DUMP_SAMPLE,
+                                                                     dtype=np.int64))
+    else:
+        idx = np.arange(n)
+    enc = rsgpu.GpuEncoder(k, L, e, blocks=blocks, seed=1, ctx=ctx)
+    err = rsgpu.erasure_patterns(1, 0, blocks, k, e)
+    want_par, want_rec = [], []
+    for b in range(blocks):
+        data = enc.source_rows(b)
+        want_par.append(np.stack(orc.encode_block(list(data), e)))
+        want_rec.append(data[err[b].astype(np.int64)])
+    assert np.array_equal(got["parity"], np.stack(want_par).reshape(-1)[idx].astype(np.float32))
+    assert np.array_equal(got["recovered"], np.stack(want_rec).reshape(-1)[idx].astype(np.float32))
+    assert got["decode_status"].shape == (blocks,) and not got["decode_status"].any()
 
 
 @pytest.mark.parametrize("kernel", ["auto", "generated", "one_matrix"])
@@ -613,7 +659,7 @@ def test_bench_c4_two_ranks_ragged():
     both in ragged batches, every batch verified; the shares are contiguous
     and cover every block once."""
     line = run_bench(["--gpus", "2", "--same-device", "--dist-backend", "gloo", "--config", "c4",
-                      "--blocks", "2501", "--batch", "512", "--warmup", "1", "--no-cpu-baseline"])
+                      "--blocks", "2501", "--batch", "512", "--warmup", "1", "--no-cpu-baseline", "--full"])
     assert line["n_gpus"] == 2 and line["verified"]
     assert line["streamed"]["mismatch_bytes"] == 0 and line["streamed"]["blocks_total"] == 2501
     ranks = sorted(line["ranks"], key=lambda r: r["rank"])
@@ -625,7 +671,7 @@ def test_bench_c5_two_ranks():
     two ranks on device 0 with 3 blocks each): disjoint shards, erasure lists
     by global block index, verified."""
     line = run_bench(["--gpus", "2", "--same-device", "--dist-backend", "gloo", "--config", "c5",
-                      "--blocks", "3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"])
+                      "--blocks", "3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"])
     assert line["n_gpus"] == 2 and line["verified"]
     assert line["config"]["symbols"] == 100 and line["config"]["erased"] == 20
     ranks = sorted(line["ranks"], key=lambda r: r["rank"])

@@ -127,6 +127,18 @@ def test_bench_c1_cpu_line():
     assert "rsgpu" not in r.stderr
 
 
+def test_bench_is_plain_by_default():
+    """--full and --dump-outputs are off by default, and the data is compared
+    with the originals only under --full (without --no-verify)."""
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    assert not bench.verifying(a)
+    assert bench.verifying(bench.parse(["--full"]))
+    assert not bench.verifying(bench.parse(["--full", "--no-verify"]))
+    assert bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
 def test_bench_c1_rejects_geometry_and_gpus():
     """--config c1 is the reference's fixed CPU case: custom geometry and
     --gpus > 1 (N ranks timing the CPU on shared cores) are refused."""

@@ -4,8 +4,9 @@
    (erasure_code/gf_inverse_test.c:124-179, gf_vect_mul_test.c:53-80) and the
    committed golden vectors generated from the reference's ISA-L base C
    (tests/golden/golden.json, gen_golden.py).
-2. When oracle/_ref/libisal_ref.so is present (built from /root/reference in
-   the build container), random cross-checks oracle vs reference.
+2. Random cross-checks oracle vs reference: against the reference's recorded
+   results (tests/golden/reference_random.json), and against the library
+   itself where oracle/_ref/libisal_ref.so is built.
 """
 import hashlib
 import json
@@ -15,10 +16,13 @@ import numpy as np
 import pytest
 
 from oracle_lib import Oracle, Reference, have_reference
+from golden import random_cases as rc_
 from golden.synth import erasure_pattern, synth_block, synth_row
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = json.load(open(os.path.join(HERE, "golden", "golden.json")))
+# the reference's results on golden/random_cases.py (gen_golden.py)
+REF_RANDOM = json.load(open(os.path.join(HERE, "golden", "reference_random.json")))
 
 
 def sha(b):
@@ -97,54 +101,39 @@ def test_synth_matches_oracle(orc):
 needs_ref = pytest.mark.skipif(not have_reference(), reason="oracle/_ref not built")
 
 
-@needs_ref
 def test_oracle_vs_reference_random():
-    orc, ref = Oracle(), Reference()
-    rng = np.random.default_rng(11)  # TEST_SEED of erasure_code_base_test.c:62
-    for _ in range(30):
-        k = int(rng.integers(1, 40))
-        rows = int(rng.integers(1, 20))
-        L = int(rng.integers(1, 700))
-        coef = rng.integers(0, 256, (rows, k), dtype=np.uint8)
-        g1, g2 = orc.init_tables(k, rows, coef), ref.init_tables(k, rows, coef)
-        assert (g1 == g2).all()
-        data = [rng.integers(0, 256, L, dtype=np.uint8) for _ in range(k)]
-        o1 = [np.zeros(L, np.uint8) for _ in range(rows)]
-        o2 = [np.zeros(L, np.uint8) for _ in range(rows)]
-        orc.encode_data(L, k, rows, g1, data, o1)
-        ref.encode_data(L, k, rows, g2, data, o2)
-        assert all((x == y).all() for x, y in zip(o1, o2))
-        # update path (ec_encode_data_update_base)
-        vec_i = int(rng.integers(0, k))
-        u1 = [x.copy() for x in o1]
-        u2 = [x.copy() for x in o2]
-        orc.encode_data_update(L, k, rows, vec_i, g1, data[vec_i], u1)
-        ref.encode_data_update(L, k, rows, vec_i, g2, data[vec_i], u2)
-        assert all((x == y).all() for x, y in zip(u1, u2))
+    """Tables, encode and the update path (ec_encode_data_update_base) on
+    random coefficients and data: the oracle's bytes are the reference's
+    (its recorded digests; the library itself too where it is built)."""
+    orc = Oracle()
+    ref = Reference() if have_reference() else None
+    cases = list(rc_.encode_cases())
+    assert len(cases) == len(REF_RANDOM["encode"]) == 30
+    for case, want in zip(cases, REF_RANDOM["encode"]):
+        assert rc_.encode_result(orc, case) == want
+        if ref is not None:
+            assert rc_.encode_result(ref, case) == want
 
 
-@needs_ref
 def test_invert_vs_reference_random():
-    orc, ref = Oracle(), Reference()
-    rng = np.random.default_rng(5)
-    for _ in range(40):
-        n = int(rng.integers(1, 60))
-        mat = rng.integers(0, 256, (n, n), dtype=np.uint8)
-        if rng.random() < 0.3:  # force singular: duplicate a row
-            mat[n - 1] = mat[0]
-        r1, i1 = orc.invert_matrix(mat)
-        r2, i2 = ref.invert_matrix(mat)
-        assert r1 == r2
-        if r1 == 0:
-            assert (i1 == i2).all()
+    orc = Oracle()
+    ref = Reference() if have_reference() else None
+    cases = list(rc_.invert_cases())
+    assert len(cases) == len(REF_RANDOM["invert"]) == 40
+    for mat, want in zip(cases, REF_RANDOM["invert"]):
+        assert rc_.invert_result(orc, mat) == want
+        if ref is not None:
+            assert rc_.invert_result(ref, mat) == want
 
 
-@needs_ref
 def test_rs_and_cauchy_matrices_vs_reference():
-    orc, ref = Oracle(), Reference()
-    for m, k in ((9, 5), (20, 16), (96, 64), (120, 100), (250, 200)):
-        assert (orc.gen_rs_matrix(m, k) == ref.gen_rs_matrix(m, k)).all()
-        assert (orc.gen_cauchy1_matrix(m, k) == ref.gen_cauchy1_matrix(m, k)).all()
+    orc = Oracle()
+    ref = Reference() if have_reference() else None
+    assert len(REF_RANDOM["matrices"]) == len(rc_.MATRIX_SHAPES)
+    for (m, k), want in zip(rc_.MATRIX_SHAPES, REF_RANDOM["matrices"]):
+        assert rc_.matrices_result(orc, m, k) == want
+        if ref is not None:
+            assert rc_.matrices_result(ref, m, k) == want
 
 
 @needs_ref
@@ -204,22 +193,18 @@ def test_golden_general_decode(orc, case):
     assert all((rec[i] == rows[j]).all() for i, j in enumerate(case["err"]))
 
 
-@needs_ref
 def test_general_decode_matrix_vs_reference_random():
     """Random RS / Cauchy codes and erasure lists over data and parity rows:
     the restatement equals the reference's gf_gen_decode_matrix (compiled
     from erasure_code_base_test.c by oracle/Makefile) in status, survivors
-    and matrix."""
-    orc, ref = Oracle(), Reference()
-    rng = np.random.default_rng(13)
-    for trial in range(400):
-        k = int(rng.integers(1, 60))
-        p = int(rng.integers(1, 24))
-        m = k + p
-        enc = orc.gen_rs_matrix(m, k) if trial % 2 else orc.gen_cauchy1_matrix(m, k)
-        n = int(rng.integers(1, p + 1))
-        err = np.sort(rng.choice(m, n, replace=False)).astype(np.uint8)
-        a, b = orc.gen_decode_matrix(enc, err), ref.gen_decode_matrix(enc, err)
-        assert a[0] == b[0]
-        if a[0] == 0:
-            assert (a[1] == b[1]).all() and (a[2] == b[2]).all()
+    and matrix -- against its recorded digests, and against the library
+    itself where it is built."""
+    orc = Oracle()
+    ref = Reference() if have_reference() else None
+    cases = list(rc_.general_cases())
+    assert len(cases) == len(REF_RANDOM["general_decode_matrix"]) == 400
+    for (kind, k, m, err), want in zip(cases, REF_RANDOM["general_decode_matrix"]):
+        enc = orc.gen_rs_matrix(m, k) if kind == "rs" else orc.gen_cauchy1_matrix(m, k)
+        assert rc_.general_result(orc, enc, err) == want, (kind, k, m, err.tolist())
+        if ref is not None:
+            assert rc_.general_result(ref, enc, err) == want

@@ -9,7 +9,7 @@ for g in "16 0.5 8192 65535" "16 0.5 16384 65535" "64 0.5 32000 16384" "64 0.25 
   set -- $g
   for rep in 1 2 3; do
     for dk in generated one_matrix; do
-      $T python3 bench.py --no-cpu-baseline --steps 4 --warmup 1 --symbols $1 --loss-rate $2 --symbol-size $3 --blocks $4 --decode-kernel $dk > $O/k$1_l$2_L$3_${dk}_$rep.log 2>&1 || exit 1
+      $T python3 bench.py --full --no-cpu-baseline --steps 4 --warmup 1 --symbols $1 --loss-rate $2 --symbol-size $3 --blocks $4 --decode-kernel $dk > $O/k$1_l$2_L$3_${dk}_$rep.log 2>&1 || exit 1
     done
   done
 done

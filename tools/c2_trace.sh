@@ -6,5 +6,5 @@ TAG=${1:-x}
 O=$(pwd)/gpurun_out/c2trace_$TAG
 mkdir -p $O
 export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace -d $O/kt -o run --output-format csv -- python3 bench.py --config c2 --steps 300 --no-cpu-baseline $ARGS > $O/bench.log 2>&1 && \
+timeout -k 10 300 rocprofv3 --kernel-trace -d $O/kt -o run --output-format csv -- python3 bench.py --config c2 --steps 300 --full --no-cpu-baseline $ARGS > $O/bench.log 2>&1 && \
 python3 tools/trace_gaps.py $O/kt/run_kernel_trace.csv > $O/gaps.txt && cat $O/gaps.txt

@@ -22,7 +22,7 @@ for rep in $(seq 1 ${REPS:-3}); do
     st=5; [ $c = c2 ] && st=300; [ $c = c4 ] && st=1
     for spec in "$@"; do
       parse "$spec"
-      timeout -k 10 300 python3 tools/ab_lib.py --lib $lib $x --config $c --steps $st --no-cpu-baseline > $O/${n}_${c}_$rep.log 2>&1 || { tail -20 $O/${n}_${c}_$rep.log; exit 1; }
+      timeout -k 10 300 python3 tools/ab_lib.py --lib $lib $x --config $c --steps $st --full --no-cpu-baseline > $O/${n}_${c}_$rep.log 2>&1 || { tail -20 $O/${n}_${c}_$rep.log; exit 1; }
       grep '^{' $O/${n}_${c}_$rep.log | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('$n', '$c', $rep, d['value'], d['ms_per_step'], {k:round(v['avg_ms'],3) for k,v in d['kernels'].items()})"
     done
   done

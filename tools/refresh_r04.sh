@@ -14,4 +14,4 @@ bash tools/profile_round.sh $TAG && \
 bash tools/pmc_sq.sh $TAG && \
 python3 tools/pmc_summary.py gpurun_out/sq_$TAG > $O/sq_summary.txt 2>&1 && \
 $T 120 ./storage-benchmarks_amd/bin/rs_arithmetic --vectors 8 16 32 --runs 3 > $O/arithmetic.log 2>&1 && \
-$T 600 python3 bench.py --traffic gpurun_out/prof_$TAG/traffic.json --sq-counters $O/sq_summary.txt --host-io 64 > $O/bench.log 2>&1
+$T 600 python3 bench.py --full --traffic $O/../prof_$TAG/traffic.json --sq-counters $O/sq_summary.txt --host-io 64 > $O/bench.log 2>&1

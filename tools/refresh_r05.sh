@@ -14,9 +14,9 @@ $T 300 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 &
 bash tools/profile_round.sh $TAG && \
 bash tools/pmc_sq.sh $TAG && \
 python3 tools/pmc_summary.py gpurun_out/sq_$TAG > $O/sq_summary.txt 2>&1 && \
-$T 600 python3 bench.py --traffic gpurun_out/prof_$TAG/traffic.json --sq-counters $O/sq_summary.txt --host-io 64 > $O/bench.log 2>&1 && \
-$T 300 python3 bench.py > $O/bench_default.log 2>&1 && \
+$T 600 python3 bench.py --full --traffic $O/../prof_$TAG/traffic.json --sq-counters $O/sq_summary.txt --host-io 64 > $O/bench.log 2>&1 && \
+$T 300 python3 bench.py --full > $O/bench_default.log 2>&1 && \
 $T 300 python3 bench.py --config c1 > $O/c1.log 2>&1 && \
-$T 300 python3 bench.py --config c2 --steps 200 --warmup 20 --no-cpu-baseline > $O/c2.log 2>&1 && \
-$T 300 python3 bench.py --config c4 --no-cpu-baseline > $O/c4.log 2>&1 && \
-$T 300 python3 bench.py --config c5 --no-cpu-baseline > $O/c5.log 2>&1
+$T 300 python3 bench.py --config c2 --steps 200 --warmup 20 --full --no-cpu-baseline > $O/c2.log 2>&1 && \
+$T 300 python3 bench.py --config c4 --full --no-cpu-baseline > $O/c4.log 2>&1 && \
+$T 300 python3 bench.py --config c5 --full --no-cpu-baseline > $O/c5.log 2>&1

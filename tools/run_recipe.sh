@@ -25,10 +25,10 @@ for step in "$@"; do
     c2|c3|c4|c5)
       for rep in $(seq 1 ${REPS:-1}); do
         st=5; [ $step = c2 ] && st=300; [ $step = c4 ] && st=1
-        $T $B --config $step --steps $st --no-cpu-baseline $ARGS > $O/${step}_$rep.log 2>&1 || { tail -20 $O/${step}_$rep.log; exit 1; }
+        $T $B --full --config $step --steps $st --no-cpu-baseline $ARGS > $O/${step}_$rep.log 2>&1 || { tail -20 $O/${step}_$rep.log; exit 1; }
         summ $O/${step}_$rep.log
       done ;;
-    line) timeout -k 10 600 $B --host-io 64 $ARGS > $O/bench.log 2>&1 || exit 1; grep '^{' $O/bench.log > $O/bench.json; summ $O/bench.log ;;
+    line) timeout -k 10 600 $B --full --host-io 64 $ARGS > $O/bench.log 2>&1 || exit 1; grep '^{' $O/bench.log > $O/bench.json; summ $O/bench.log ;;
     sweep) bash tools/geom_sweep.sh $TAG || true ;;
     bound) bash tools/bound_run.sh $TAG || exit 1; cat gpurun_out/bound_$TAG/summary.log ;;
     prof) bash tools/profile_round.sh $TAG || exit 1 ;;

@@ -9,8 +9,8 @@ T="timeout -k 10 240"
 for g in "150 0.66666 400" "125 1.0 400" "160 0.40625 500" "128 0.5 497"; do
   set -- $g
   for rep in 1 2; do
-    $T python3 bench.py --no-cpu-baseline --steps 3 --warmup 1 --symbols $1 --loss-rate $2 --blocks $3 > $O/k$1_head_$rep.log 2>&1 || exit 1
-    $T python3 tools/ab_lib.py --lib $BASE --no-cpu-baseline --steps 3 --warmup 1 --symbols $1 --loss-rate $2 --blocks $3 > $O/k$1_base_$rep.log 2>&1 || exit 1
+    $T python3 bench.py --full --no-cpu-baseline --steps 3 --warmup 1 --symbols $1 --loss-rate $2 --blocks $3 > $O/k$1_head_$rep.log 2>&1 || exit 1
+    $T python3 tools/ab_lib.py --lib $BASE --full --no-cpu-baseline --steps 3 --warmup 1 --symbols $1 --loss-rate $2 --blocks $3 > $O/k$1_base_$rep.log 2>&1 || exit 1
   done
 done
 for f in $O/*.log; do echo $f; grep '^{' $f | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['verified'], d['config']['erased'], d['ms_per_step'], {k:(v['avg_ms'],v['launches']) for k,v in d['kernels'].items()})"; done
