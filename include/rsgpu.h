@@ -271,6 +271,70 @@ int rsgpu_verify_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, 
                         const unsigned char *d_src, const unsigned char *d_out,
                         const unsigned char *d_err, unsigned long long *d_mismatch);
 
+/* ---- parity scrub: are the k + e rows of a block still consistent? ------- */
+
+/* Per byte column i of a block, with the e x k parity matrix c (`coef`, or
+ * rows k..k+e-1 of gf_gen_rs_matrix(k+e, k) when NULL), the syndromes are
+ *   s_p = parity[p][i] ^ XOR_j c[p][j] * src[j][i],   p < e,
+ * and the column is BAD when any s_p != 0.  A bad column is explained by
+ *   source row r < k    when some x != 0 has s_p = c[p][r] * x for every p,
+ *   parity row k + p0   when s_p != 0 exactly for p = p0.
+ * A matrix is LOCATABLE when e >= 2, its rows 0 and 1 have no zero entry and
+ * the k ratios c[1][j] / c[0][j] are pairwise distinct: then at most one row
+ * explains a column (the gf_gen_rs_matrix code, ratios 2^j, and
+ * gf_gen_cauchy1_matrix both are).
+ *
+ * The report of a block (overwritten by every call, never accumulated):
+ *   CLEAN     no bad column
+ *   ONE_ROW   (RSGPU_SCRUB_LOCATE only) every bad column is explained by the
+ *             same row, `row` in [0, k + e)
+ *   DAMAGED   anything else: a column no row explains, two columns that point
+ *             at different rows, or any bad column without RSGPU_SCRUB_LOCATE
+ * ONE_ROW names the most likely explanation, not a proof: a code of distance
+ * e + 1 tells damage in one row of a column from damage in up to e - 1 rows,
+ * so with e = 2 two damaged rows in one column can look like a third. */
+#define RSGPU_SCRUB_CLEAN 0
+#define RSGPU_SCRUB_ONE_ROW 1
+#define RSGPU_SCRUB_DAMAGED 2
+typedef struct rsgpu_scrub_report {
+    unsigned long long bad_columns; /* number of bad byte columns in [0, len) */
+    int status;                     /* RSGPU_SCRUB_CLEAN / _ONE_ROW / _DAMAGED */
+    int row;                        /* ONE_ROW: the row in [0, k+e); otherwise -1 */
+} rsgpu_scrub_report;
+
+#define RSGPU_SCRUB_LOCATE 1 /* flags: name the one damaged row where there is one */
+
+/* Scrubs `blocks` blocks (layout as rsgpu_encode_blocks; d_src and d_parity
+ * are only read) into d_report [blocks] (DEVICE memory, 8-byte aligned).
+ * Enqueued on the context's stream, no synchronisation.  Any geometry
+ * rsgpu_encode_blocks accepts; e == 0 or len == 0 reports every block CLEAN.
+ * RSGPU_SCRUB_LOCATE with a matrix that is not locatable (e < 2 included)
+ * returns RSGPU_ERR_UNSUPPORTED and enqueues nothing. */
+int rsgpu_scrub_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                       const unsigned char *d_src, const unsigned char *d_parity,
+                       const unsigned char *coef, int flags, rsgpu_scrub_report *d_report);
+
+/* Host only: 1 when the e x k matrix `coef` (NULL: the gf_gen_rs_matrix
+ * code) is locatable by the rule above, else 0. */
+int rsgpu_scrub_locatable(int k, int e, const unsigned char *coef);
+
+/* Scrub kernel of rsgpu_scrub_blocks (per context; every choice writes the
+ * same reports):
+ *   AUTO      FUSED wherever it applies, otherwise TWO_PASS
+ *   FUSED     k_rs_bs_scrub: the compiled encode programs ((16,4) (16,8)
+ *             (64,32) (64,16) (100,20) (5,4) (20,7), no `coef`, 16-byte
+ *             aligned rows, len % 32 == 0) with the stored parity read and
+ *             compared in registers; a clean tile writes nothing
+ *   TWO_PASS  the parity of a slice of blocks computed into context-owned
+ *             scratch (at most 128 MiB, or one block's parity when that is
+ *             larger) by the encode dispatch, then k_scrub_compare; any
+ *             geometry
+ * A choice that does not apply falls back to TWO_PASS. */
+#define RSGPU_SCRUB_AUTO 0
+#define RSGPU_SCRUB_FUSED 1
+#define RSGPU_SCRUB_TWO_PASS 2
+int rsgpu_set_scrub_kernel(rsgpu_ctx *ctx, int kernel);
+
 /* ---- host-resident blocks (the reference's buffers, isa.cpp:46-58) ------- */
 
 /* Page-locked host memory for the host-resident calls: their copies then run

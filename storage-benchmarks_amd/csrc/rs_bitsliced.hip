@@ -33,6 +33,10 @@
 // the lane's 8 dwords (12 block swaps), and the same routine converts the
 // accumulators back to bytes.
 //
+// The parity scrub of these codes (k_rs_bs_scrub) is the same accumulation
+// with another epilogue: the stored parity read and compared in registers
+// instead of the computed one written (scrub_tile).
+//
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -142,6 +146,7 @@ __device__ __forceinline__ void consume(uint32_t (&acc)[NR][8], const uint32_t (
 }
 
 struct Args {
+    static constexpr bool kScrub = false;  // run_group's epilogue stores the parity rows
     const uint8_t* src;   // [B][K] rows
     uint8_t* out;         // [B][E] rows
     long long pitch, len;
@@ -162,7 +167,8 @@ struct TilePos {
     int db;
     bool inb;
 };
-__device__ __forceinline__ TilePos tile_pos(const Args& a, int lane)
+template <class A>
+__device__ __forceinline__ TilePos tile_pos(const A& a, int lane)
 {
     TilePos p;
     if (!a.flat) {
@@ -234,12 +240,163 @@ __device__ __forceinline__ void consume_part(uint32_t (&acc)[NR][8], uint32_t (&
     }(std::make_integer_sequence<int, S>{});
 }
 
+// ---------------------------------------------------------------------------
+// Parity scrub of the compiled codes (rsgpu_scrub_blocks, k_rs_bs_scrub):
+// run_group's accumulation, then this epilogue in place of the parity store.
+// One workgroup per (tile, block), never the flat layout: everything a
+// workgroup reduces belongs to one block.
+struct ScrubArgs {
+    static constexpr bool kScrub = true;
+    static constexpr int flat = 0;
+    const uint8_t* src;  // [B][K] rows
+    const uint8_t* par;  // [B][E] rows, the stored parity
+    long long pitch, len;
+    long long blocks;
+    ScrubFold* fold;  // [B], zeroed before the launch (rs_kernels.h)
+    int locate;
+};
+
+// log / antilog tables of the cold paths (the scrub's row location, the
+// small-batch decode's solve below)
+alignas(16) __device__ const GfTables kGfBs = make_gf_tables();
+
+// Wave G's rows [R0, R0 + NR) of one tile.  The lane's 32 bytes of each
+// stored parity row, as planes, XORed into the accumulators: the syndromes,
+// in place.  Their OR over planes and rows gives the lane's bad-byte mask
+// (idle lanes, which re-read the row head, give none); the NW waves' masks
+// meet in LDS.  A clean tile ends there and writes nothing.  Otherwise wave
+// 0 adds the tile's bad-column count to the block,
+// and with `locate` the cold path names each bad column's row (rsgpu.h).  It
+// is small code, not fast code: in four passes the waves lay 8 bytes per lane
+// of all E syndrome rows into LDS (syn [E][512]), and the workgroup's threads
+// walk the 512 columns byte by byte.  The code's ratios are c[1][j] / c[0][j]
+// = 2^j, so the only source row that can explain (s_0, s_1) is r = log(s_1 /
+// s_0), with x = s_0 (c[0][r] = 1), and it does when s_p == 2^(p r) x for
+// every p; r >= K: no row; s_0 or s_1 zero: parity row k + p when s_p is the
+// only non-zero syndrome.  The maxima of row + 1 and of kScrubBias - row go
+// into the block's fold (order-independent atomics, one pair per wave).
+// LDS, in the part buffers: masks [NW][64] u32 | syn = 1 + E / 2 KiB of the 32.
+template <int K, int E, int NW, int G, int R0, int NR>
+__device__ __forceinline__ void scrub_tile(const ScrubArgs& a, uint32_t (&acc)[NR][8], bool inb, long long wo,
+                                           long long wb, long long blk, int lane, uint4* ldsv, uint32_t m4,
+                                           uint32_t m2, uint32_t m1)
+{
+    static_assert(E >= 2 && 1024 + E * 512 <= 2 * S * 2 * 64 * 16, "scrub LDS fits the part buffers");
+    uint32_t* wmask = reinterpret_cast<uint32_t*>(ldsv);
+    uint8_t* syn = reinterpret_cast<uint8_t*>(ldsv) + 1024;
+    const uint8_t* pb = a.par + (size_t)wb * E * a.pitch;
+    // The stored row goes to planes (one tr8, as the store epilogue spends on
+    // the accumulators) and the syndromes stay planes: a byte is non-zero
+    // when any of its 8 plane bits is, so the OR of a row's planes IS its
+    // bad-byte mask (bit 8 q + w: byte 4 w + q), one register for all rows.
+    // The stored row r + 1 is in flight while row r is transposed: one row
+    // ahead, no further (the scheduler would otherwise hoist all NR rows'
+    // loads, 8 VGPRs each, over the accumulators).
+    // (An idle lane reads the row head, as it does of the sources: no branch
+    // around the loads.)
+    uint32_t mine = 0;
+    uint32_t Pn[8];
+    const long long po = inb ? wo : 0;
+    load32(pb + (size_t)R0 * a.pitch, po, true, Pn);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        uint32_t Pw[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            Pw[q] = Pn[q];
+        if (r + 1 < NR)
+            load32(pb + (size_t)(R0 + r + 1) * a.pitch, po, true, Pn);
+        tr8(Pw, m4, m2, m1);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            acc[r][q] ^= Pw[q];
+            mine |= acc[r][q];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    wmask[G * 64 + lane] = inb ? mine : 0u;
+    __syncthreads();
+    uint32_t tm = 0;
+#pragma unroll
+    for (int g = 0; g < NW; ++g)
+        tm |= wmask[g * 64 + lane];
+    if (__ballot(tm != 0) == 0)
+        return;  // the same for every wave of the workgroup
+    ScrubFold* f = a.fold + blk;
+    if constexpr (G == 0) {
+        unsigned n = __builtin_popcount(tm);
+        for (int off = 32; off > 0; off >>= 1)
+            n += __shfl_down(n, off, 64);
+        if (lane == 0)
+            atomicAdd(&f->bad, (unsigned long long)n);
+    }
+    if (!a.locate)
+        return;
+    const uint8_t* gexp = kGfBs.exp;
+    const uint8_t* glog = kGfBs.log;
+    const int tid = G * 64 + lane;
+    unsigned hi1 = 0, lo1 = 0;
+#pragma unroll
+    for (int rr = 0; rr < NR; ++rr)
+        tr8(acc[rr], m4, m2, m1);  // syndrome planes -> bytes, in place
+    for (int pass = 0; pass < 4; ++pass) {
+        // the lane's bytes 8 pass .. 8 pass + 7 of every row (zeros from an idle lane)
+        [&]<int... Ps>(std::integer_sequence<int, Ps...>) {
+            ((pass == Ps ? [&] {
+#pragma unroll
+                for (int rr = 0; rr < NR; ++rr)
+                    *reinterpret_cast<uint2*>(syn + (R0 + rr) * 512 + lane * 8) =
+                        inb ? make_uint2(acc[rr][2 * Ps], acc[rr][2 * Ps + 1]) : make_uint2(0u, 0u);
+            }()
+                         : void()),
+             ...);
+        }(std::make_integer_sequence<int, 4>{});
+        __syncthreads();
+        for (int c = tid; c < 512; c += 64 * NW) {
+            const uint32_t s0 = syn[c], s1 = syn[512 + c];
+            int nz = 0, p0 = 0;
+            for (int p = 0; p < E; ++p) {
+                const bool on = syn[p * 512 + c] != 0;
+                nz += on;
+                p0 = on ? p : p0;
+            }
+            if (!nz)
+                continue;
+            int row = -1;
+            if (s0 && s1) {
+                int r = (int)glog[s1] + 255 - (int)glog[s0];  // c[1][r] / c[0][r] = 2^r
+                r = r >= 255 ? r - 255 : r;
+                if (r < K) {
+                    const int lx = glog[s0];  // x = s_0: c[0][r] = 1
+                    bool ok = true;
+                    for (int p = 2; p < E; ++p)
+                        ok &= syn[p * 512 + c] == gexp[(p * r) % 255 + lx];
+                    row = ok ? r : -1;
+                }
+            } else if (nz == 1) {
+                row = K + p0;
+            }
+            hi1 = max(hi1, row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
+            lo1 = max(lo1, row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
+        }
+        __syncthreads();  // the next pass overwrites syn
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        hi1 = max(hi1, (unsigned)__shfl_down((int)hi1, off, 64));
+        lo1 = max(lo1, (unsigned)__shfl_down((int)lo1, off, 64));
+    }
+    if (lane == 0 && hi1) {
+        atomicMax(&f->hi1, hi1);
+        atomicMax(&f->lo1, lo1);
+    }
+}
+
 // One wave group: rows [R0, R0+NR).  The workgroup streams the sources
 // chunk by chunk (Horner order, last chunk first) through the LDS parts:
 // while part n is transposed in place and consumed, part n+1 is already in
 // flight by LDS-DMA (global_load_lds_dwordx4, counted vmcnt, raw barriers).
-template <int K, int E, int C, int NW, int G, bool PRIO>
-__device__ __forceinline__ void run_group(const Args& a, uint4 (*lds)[S * 2 * 64])
+template <int K, int E, int C, int NW, int G, bool PRIO, class A = Args>
+__device__ __forceinline__ void run_group(const A& a, uint4 (*lds)[S * 2 * 64])
 {
     using P = PlanHolder<K, E, C>;
     constexpr int OPW = (E + NW - 1) / NW;
@@ -337,18 +494,23 @@ __device__ __forceinline__ void run_group(const Args& a, uint4 (*lds)[S * 2 * 64
         bs::barrier_lds();  // part buffer n & 1 is refilled by step n + 2
     }
 
-    if (!inb)
-        return;
-    uint8_t* ob = a.out + (size_t)wb * E * a.pitch;
-    const long long ooff = tp.db * (long long)E * a.pitch + wo;
+    if constexpr (A::kScrub) {
+        // the part buffers are free: every wave is past the last step's barrier
+        scrub_tile<K, E, NW, G, R0, NR>(a, acc, inb, wo, wb, tp.b0, lane, &lds[0][0], m4, m2, m1);
+    } else {
+        if (!inb)
+            return;
+        uint8_t* ob = a.out + (size_t)wb * E * a.pitch;
+        const long long ooff = tp.db * (long long)E * a.pitch + wo;
 #pragma unroll
-    for (int r = 0; r < NR; ++r) {
-        uint32_t W[8];
+        for (int r = 0; r < NR; ++r) {
+            uint32_t W[8];
 #pragma unroll
-        for (int q = 0; q < 8; ++q)
-            W[q] = acc[r][q];
-        tr8(W, m4, m2, m1);
-        store32(ob + (size_t)(R0 + r) * a.pitch, ooff, W);
+            for (int q = 0; q < 8; ++q)
+                W[q] = acc[r][q];
+            tr8(W, m4, m2, m1);
+            store32(ob + (size_t)(R0 + r) * a.pitch, ooff, W);
+        }
     }
 }
 
@@ -372,6 +534,26 @@ __global__ __launch_bounds__(64 * NW, (bs_waves_per_simd<E, NW>())) void k_rs_bs
         ((wave == Gs ? run_group<K, E, C, NW, Gs, PRIO>(a, lds) : void()), ...);
     }(std::make_integer_sequence<int, NW>{});
     RSGPU_DIAG_END();
+}
+
+// The scrub: k_rs_bs's accumulation (wave priority window on) with
+// scrub_tile as the epilogue.
+template <int K, int E, int C, int NW>
+__global__ __launch_bounds__(64 * NW, (bs_waves_per_simd<E, NW>())) void k_rs_bs_scrub(ScrubArgs a)
+{
+    __shared__ uint4 lds[2][S * 2 * 64];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    [&]<int... Gs>(std::integer_sequence<int, Gs...>) {
+        ((wave == Gs ? run_group<K, E, C, NW, Gs, true, ScrubArgs>(a, lds) : void()), ...);
+    }(std::make_integer_sequence<int, NW>{});
+}
+
+template <int K, int E, int C, int NW>
+hipError_t launch_scrub(const ScrubArgs& a, hipStream_t st)
+{
+    dim3 grid((unsigned)((a.len + 2047) / 2048), (unsigned)a.blocks);
+    hipLaunchKernelGGL((k_rs_bs_scrub<K, E, C, NW>), grid, dim3(64 * NW), 0, st, a);
+    return hipGetLastError();
 }
 
 // Small batches of a single-chunk code (C == K, E <= 8; C2: one block of
@@ -474,8 +656,7 @@ hipError_t launch_split(const uint8_t* src, uint8_t* out, long long pitch, long 
 // sources as k_rs_bs_split; the partial syndromes meet in LDS, each wave
 // XORing its partials into one zeroed copy (ds_xor_b32), so the output phase
 // reads every syndrome once instead of once per wave: C2 698-701 vs 687-689
-// GiB/s, same box x4 (profiles/r04_spl/ldsx_*).
-alignas(16) __device__ const GfTables kGfBs = make_gf_tables();
+// GiB/s, same box x4 (profiles/r04_spl/ldsx_*).  (The tables: kGfBs, above.)
 
 // parity rows p = G, G + SPL, ... of wave G: they survive whatever the
 // erasure list says, so their loads go out before the list arrives
@@ -752,6 +933,25 @@ hipError_t launch_rs_bitsliced(int k, int e, const uint8_t* src, uint8_t* out, l
     if (k == 100 && e == 20) return bs::launch<100, 20, 20, 4>(src, out, pitch, len, blocks, st, prio);
     if (k == 5 && e == 4) return bs::launch<5, 4, 5, 1>(src, out, pitch, len, blocks, st, prio);
     if (k == 20 && e == 7) return bs::launch<20, 7, 20, 1>(src, out, pitch, len, blocks, st, prio);
+    return hipErrorInvalidValue;
+}
+
+// the plans (K, E, C, NW) of launch_rs_bitsliced
+hipError_t launch_rs_bitsliced_scrub(int k, int e, const uint8_t* src, const uint8_t* par, long long pitch,
+                                     long long len, long long blocks, ScrubFold* fold, int locate,
+                                     hipStream_t st)
+{
+    if (blocks <= 0 || blocks > 65535 || len <= 0 || len % 32 != 0 || len >= (1ll << 32) || pitch < len ||
+        !src || !par || !fold)
+        return hipErrorInvalidValue;
+    const bs::ScrubArgs a{src, par, pitch, len, blocks, fold, locate};
+    if (k == 16 && e == 4) return bs::launch_scrub<16, 4, 16, 1>(a, st);
+    if (k == 16 && e == 8) return bs::launch_scrub<16, 8, 16, 1>(a, st);
+    if (k == 64 && e == 32) return bs::launch_scrub<64, 32, 16, 4>(a, st);
+    if (k == 64 && e == 16) return bs::launch_scrub<64, 16, 16, 2>(a, st);
+    if (k == 100 && e == 20) return bs::launch_scrub<100, 20, 20, 4>(a, st);
+    if (k == 5 && e == 4) return bs::launch_scrub<5, 4, 5, 1>(a, st);
+    if (k == 20 && e == 7) return bs::launch_scrub<20, 7, 20, 1>(a, st);
     return hipErrorInvalidValue;
 }
 

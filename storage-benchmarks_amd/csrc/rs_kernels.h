@@ -87,6 +87,42 @@ hipError_t launch_rs_syn_split(int k, int e, const SynArgs& a, long long blocks,
 hipError_t launch_rs_bitsliced_split(int k, int e, const uint8_t* src, uint8_t* out, long long pitch,
                                      long long len, long long blocks, hipStream_t st);
 
+// Parity scrub (rsgpu_scrub_blocks).  While a call is in flight a block's
+// 16-byte report holds the fold of its tiles, every field zero at the start
+// (one memset) and only ever raised by order-independent atomics:
+//   bytes 0-7   bad columns so far (atomicAdd)
+//   bytes 8-11  max over bad columns of row + 1          (kScrubNoRow when no
+//   bytes 12-15 max over bad columns of kScrubBias - row   row explains one)
+// so the block has one damaged row exactly when the two maxima name the same
+// row; k_scrub_finalise turns the fold into (status, row).
+constexpr unsigned kScrubBias = 1024;   // > any row index (k + e <= 250)
+constexpr unsigned kScrubNoRow = 2000;  // > kScrubBias: never equal to a row's pair
+struct ScrubFold {
+    unsigned long long bad;
+    unsigned hi1, lo1;
+};
+// Two-pass compare: the syndromes are calc ^ par (any alignment; 16 bytes per
+// load when the rows allow); rowtab [256] maps the ratio s_1 / s_0 to a source row (255:
+// none), coef is the e x k matrix (both device memory, read only with locate).
+struct ScrubCmpArgs {
+    const uint8_t* calc;  // [B][e] rows: the parity of the sources, recomputed
+    const uint8_t* par;   // [B][e] rows: the stored parity
+    long long pitch, len, blocks;
+    int k, e;
+    const uint8_t* rowtab;
+    const uint8_t* coef;
+    ScrubFold* fold;  // [B]
+    int locate;
+};
+hipError_t launch_scrub_compare(const ScrubCmpArgs& a, hipStream_t st);
+hipError_t launch_scrub_finalise(void* report, long long blocks, int locate, hipStream_t st);
+// The fused scrub of the compiled codes (rs_bitsliced.hip k_rs_bs_scrub): the
+// encode's accumulation, then the stored parity read and compared in
+// registers.  len % 32 == 0, len < 2^32, 16-byte aligned rows, blocks <= 65535.
+hipError_t launch_rs_bitsliced_scrub(int k, int e, const uint8_t* src, const uint8_t* par, long long pitch,
+                                     long long len, long long blocks, ScrubFold* fold, int locate,
+                                     hipStream_t st);
+
 // Closed-form decode prepare for the gf_gen_rs_matrix code with e erased
 // originals and all e parity rows surviving, per block: erasure list
 // validation (strictly ascending, < k; else status -2), srcs [B][k] =

@@ -28,18 +28,25 @@
 //                     case (erased originals, all parity rows surviving).
 //   k_fill_synth      seeded synthetic symbols (counter-based, see rs_synth.h).
 //   k_compare_rows    verify_data (isa.cpp:215-229) on the device.
+//   k_scrub_compare   the parity scrub's two-pass path: recomputed vs stored
+//                     parity, bad columns counted and located per block;
+//                     k_scrub_finalise turns a block's fold into its report.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
 #include <utility>
 
+#include "../../include/rsgpu.h"
 #include "gf256.h"
 #include "rs_jit.h"
 #include "rs_kernels.h"
 #include "rs_synth.h"
 
 namespace rsgpu {
+
+static_assert(sizeof(ScrubFold) == sizeof(rsgpu_scrub_report) && sizeof(ScrubFold) == 16,
+              "a block's fold lives in its report");
 
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
 {
@@ -668,8 +675,151 @@ __global__ __launch_bounds__(256) void k_compare_rows(const uint8_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------
+// Parity scrub, two-pass path (rsgpu_scrub_blocks): the encode dispatch has
+// written the parity of the sources to `calc`; the syndromes of byte column i
+// are calc[p][i] ^ par[p][i].  A thread walks columns; per bad column it
+// counts, and with `locate` names the row that explains it (rsgpu.h): the
+// ratio s_1 / s_0 picks the only source row r that can (rowtab, built on the
+// host), x = s_0 / c[0][r], and every other syndrome must equal c[p][r] x; a
+// column with exactly one non-zero syndrome is parity row k + p.  Per-block
+// results fold through the report's own 16 bytes (rs_kernels.h ScrubFold).
+// Any alignment, any length; this path is the yardstick, the compiled codes
+// scrub in k_rs_bs_scrub.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint8_t scrub_mul(uint8_t a, uint8_t b)
+{
+    return (a && b) ? kGfTables.exp[kGfTables.log[a] + kGfTables.log[b]] : 0;
+}
+// a / b, b != 0
+__device__ __forceinline__ uint8_t scrub_div(uint8_t a, uint8_t b)
+{
+    return a ? kGfTables.exp[kGfTables.log[a] + 255 - kGfTables.log[b]] : 0;
+}
+
+// one atomic per wave and field, none for a wave without a bad column
+__device__ __forceinline__ void scrub_fold_wave(ScrubFold* f, unsigned long long bad, unsigned hi1, unsigned lo1)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        bad += __shfl_down(bad, off, 64);
+        hi1 = max(hi1, (unsigned)__shfl_down((int)hi1, off, 64));
+        lo1 = max(lo1, (unsigned)__shfl_down((int)lo1, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0 && bad) {
+        atomicAdd(&f->bad, bad);
+        if (hi1) {
+            atomicMax(&f->hi1, hi1);
+            atomicMax(&f->lo1, lo1);
+        }
+    }
+}
+
+// byte column i of a block: counted when bad and, with locate, its row folded
+__device__ __forceinline__ void scrub_column(const ScrubCmpArgs& a, const uint8_t* calc, const uint8_t* par,
+                                             long long i, unsigned long long& bad, unsigned& hi1, unsigned& lo1)
+{
+    int nz = 0, p0 = 0;
+    uint8_t s0 = 0, s1 = 0;
+    for (int p = 0; p < a.e; ++p) {
+        const uint8_t s = calc[(size_t)p * a.pitch + i] ^ par[(size_t)p * a.pitch + i];
+        s0 = p == 0 ? s : s0;
+        s1 = p == 1 ? s : s1;
+        if (s) {
+            ++nz;
+            p0 = p;
+        }
+    }
+    if (!nz)
+        return;
+    ++bad;
+    if (!a.locate)
+        return;
+    int row = -1;
+    if (s0 && s1) {
+        const int r = a.rowtab[scrub_div(s1, s0)];
+        if (r != 255) {
+            const uint8_t x = scrub_div(s0, a.coef[r]);  // c[0][r] != 0: the matrix is locatable
+            bool ok = true;
+            for (int p = 2; p < a.e; ++p)
+                ok &= (uint8_t)(calc[(size_t)p * a.pitch + i] ^ par[(size_t)p * a.pitch + i]) ==
+                      scrub_mul(a.coef[(size_t)p * a.k + r], x);
+            row = ok ? r : -1;
+        }
+    } else if (nz == 1) {
+        row = a.k + p0;
+    }
+    hi1 = max(hi1, row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
+    lo1 = max(lo1, row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
+}
+
+// 16-byte aligned rows: a thread first ORs the syndromes of 16 columns, 16
+// bytes per row and load, and walks those columns only when one is bad; the
+// tail of the row, and every column of unaligned rows, go byte by byte.
+__global__ __launch_bounds__(256) void k_scrub_compare(ScrubCmpArgs a)
+{
+    const size_t b = blockIdx.y;
+    const uint8_t* calc = a.calc + b * a.e * a.pitch;
+    const uint8_t* par = a.par + b * a.e * a.pitch;
+    unsigned long long bad = 0;
+    unsigned hi1 = 0, lo1 = 0;
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long nthr = (long long)gridDim.x * blockDim.x;
+    const bool vec = ((reinterpret_cast<uintptr_t>(calc) | reinterpret_cast<uintptr_t>(par) |
+                       (uintptr_t)a.pitch) & 15) == 0;
+    const long long head = vec ? a.len & ~15LL : 0;
+    for (long long i = tid * 16; i < head; i += nthr * 16) {
+        uint4 any = make_uint4(0, 0, 0, 0);
+        for (int p = 0; p < a.e; ++p) {
+            const uint4 x = *reinterpret_cast<const uint4*>(calc + (size_t)p * a.pitch + i);
+            const uint4 y = *reinterpret_cast<const uint4*>(par + (size_t)p * a.pitch + i);
+            any.x |= x.x ^ y.x;
+            any.y |= x.y ^ y.y;
+            any.z |= x.z ^ y.z;
+            any.w |= x.w ^ y.w;
+        }
+        if ((any.x | any.y | any.z | any.w) == 0)
+            continue;
+        for (int j = 0; j < 16; ++j)
+            scrub_column(a, calc, par, i + j, bad, hi1, lo1);
+    }
+    for (long long i = head + tid; i < a.len; i += nthr)
+        scrub_column(a, calc, par, i, bad, hi1, lo1);
+    scrub_fold_wave(&a.fold[b], bad, hi1, lo1);
+}
+
+// the fold of every block into its report
+__global__ __launch_bounds__(256) void k_scrub_finalise(void* report, long long blocks, int locate)
+{
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= blocks)
+        return;
+    const ScrubFold f = static_cast<const ScrubFold*>(report)[b];
+    rsgpu_scrub_report r;
+    r.bad_columns = f.bad;
+    const bool one = locate && f.hi1 >= 1 && f.hi1 < kScrubNoRow && f.hi1 - 1 == kScrubBias - f.lo1;
+    r.status = f.bad == 0 ? RSGPU_SCRUB_CLEAN : one ? RSGPU_SCRUB_ONE_ROW : RSGPU_SCRUB_DAMAGED;
+    r.row = (f.bad != 0 && one) ? (int)f.hi1 - 1 : -1;
+    static_cast<rsgpu_scrub_report*>(report)[b] = r;
+}
+
+// ---------------------------------------------------------------------------
 // Host launch wrappers (declared in rs_kernels.h)
 // ---------------------------------------------------------------------------
+
+hipError_t launch_scrub_compare(const ScrubCmpArgs& a, hipStream_t st)
+{
+    if (a.blocks <= 0 || a.blocks > 65535 || a.len <= 0 || a.e <= 0)
+        return hipErrorInvalidValue;
+    const long long gx = std::min<long long>((a.len + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_scrub_compare, dim3((unsigned)gx, (unsigned)a.blocks), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_scrub_finalise(void* report, long long blocks, int locate, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_scrub_finalise, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, report,
+                       blocks, locate);
+    return hipGetLastError();
+}
 
 template <int R>
 static hipError_t launch_generic_R(const DotArgs& a, hipStream_t st)

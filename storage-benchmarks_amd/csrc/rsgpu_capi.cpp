@@ -609,6 +609,8 @@ int rsgpu_destroy(rsgpu_ctx* ctx)
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->d_scratch)
         (void)hipFree(ctx->d_scratch);
+    if (ctx->d_scrub)
+        (void)hipFree(ctx->d_scrub);
     if (ctx->h_stage)
         (void)hipHostFree(ctx->h_stage);
     if (ctx->stage_done)
@@ -1726,6 +1728,196 @@ int rsgpu_verify_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
     }
     RS_HIP(ctx, launch_compare_rows(d_src, (long long)pitch, k, d_out, (long long)pitch, e, d_err,
                                     (long long)len, (long long)blocks, d_mismatch, ctx->stream));
+    return RSGPU_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// ---- parity scrub ------------------------------------------------------------
+
+// the e x k parity matrix of a scrub: `coef`, or the gf_gen_rs_matrix rows
+std::vector<uint8_t> scrub_matrix(int k, int e, const unsigned char* coef)
+{
+    std::vector<uint8_t> c((size_t)e * k);
+    if (coef) {
+        std::memcpy(c.data(), coef, c.size());
+    } else {
+        std::vector<uint8_t> a((size_t)(k + e) * k);
+        rsgpu_gf_gen_rs_matrix(a.data(), k + e, k);
+        std::memcpy(c.data(), a.data() + (size_t)k * k, c.size());
+    }
+    return c;
+}
+
+// rsgpu.h's rule: e >= 2, no zero in rows 0 and 1, the ratios c[1][j] / c[0][j]
+// pairwise distinct.  tab (256 bytes, optional): ratio -> j, 255 for none.
+bool scrub_locatable(int k, int e, const uint8_t* c, uint8_t* tab)
+{
+    uint8_t t[256];
+    std::memset(t, 255, sizeof t);
+    bool ok = e >= 2 && k <= 255;
+    for (int j = 0; ok && j < k; ++j) {
+        const uint8_t c0 = c[j], c1 = c[(size_t)k + j];
+        if (!c0 || !c1) {
+            ok = false;
+            break;
+        }
+        const uint8_t ratio = hmul(c1, rsgpu_gf_inv(c0));
+        ok = t[ratio] == 255;
+        t[ratio] = (uint8_t)j;
+    }
+    if (ok && tab)
+        std::memcpy(tab, t, sizeof t);
+    return ok;
+}
+
+// Two-pass scratch: [rowtab 256 B | matrix e x k | pad to kScrubTabBytes |
+// computed parity of a slice].  The parity part is bounded: a slice holds as
+// many blocks as fit kScrubParityBytes (4 blocks of C3's 32 x 1 MB parity;
+// enough workgroups per launch to fill the device), one block when a single
+// block's parity is larger.
+constexpr size_t kScrubTabBytes = 16384;  // 256 + e k <= 256 + 125 * 125
+constexpr size_t kScrubParityBytes = 128u << 20;
+
+int ensure_scrub(rsgpu_ctx* ctx, size_t bytes)
+{
+    if (ctx->scrub_bytes >= bytes)
+        return RSGPU_OK;
+    if (ctx->d_scrub) {
+        // every kernel that reads the old buffer is on the context's stream
+        RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        RS_HIP(ctx, hipFree(ctx->d_scrub));
+        ctx->d_scrub = nullptr;
+        ctx->scrub_bytes = 0;
+    }
+    ctx->scrub_key.clear();
+    RS_HIP(ctx, hipMalloc(&ctx->d_scrub, bytes));
+    ctx->scrub_bytes = bytes;
+    return RSGPU_OK;
+}
+
+int scrub_two_pass(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks, const uint8_t* d_src,
+                   const uint8_t* d_parity, const unsigned char* coef, const std::vector<uint8_t>& c,
+                   const uint8_t* rowtab, bool locate, ScrubFold* fold)
+{
+    const size_t per_block = (size_t)e * pitch;
+    const size_t slice = std::max<size_t>(1, std::min(blocks, kScrubParityBytes / per_block));
+    int rc = ensure_scrub(ctx, kScrubTabBytes + slice * per_block);
+    if (rc)
+        return rc;
+    uint8_t* d = (uint8_t*)ctx->d_scrub;
+    if (locate) {
+        std::vector<uint8_t> key(8 + c.size());
+        std::memcpy(key.data(), &k, 4);
+        std::memcpy(key.data() + 4, &e, 4);
+        std::memcpy(key.data() + 8, c.data(), c.size());
+        if (key != ctx->scrub_key) {  // the tables of another matrix: upload once
+            void* stage;
+            rc = get_stage(ctx, 256 + c.size(), &stage);
+            if (rc)
+                return rc;
+            std::memcpy(stage, rowtab, 256);
+            std::memcpy((char*)stage + 256, c.data(), c.size());
+            rc = upload(ctx, d, 256 + c.size());
+            if (rc)
+                return rc;
+            ctx->scrub_key = std::move(key);
+        }
+    }
+    uint8_t* calc = d + kScrubTabBytes;
+    for (size_t b0 = 0; b0 < blocks; b0 += slice) {
+        const size_t nb = std::min(slice, blocks - b0);
+        rc = rsgpu_encode_blocks(ctx, k, e, len, pitch, nb, d_src + b0 * k * pitch, calc, coef);
+        if (rc)
+            return rc;
+        ScrubCmpArgs a{};
+        a.calc = calc;
+        a.par = d_parity + b0 * per_block;
+        a.pitch = (long long)pitch;
+        a.len = (long long)len;
+        a.blocks = (long long)nb;
+        a.k = k;
+        a.e = e;
+        a.rowtab = d;
+        a.coef = d + 256;
+        a.fold = fold + b0;
+        a.locate = locate ? 1 : 0;
+        KTimer kt(ctx, "k_scrub_compare", nb);
+        RS_HIP(ctx, launch_scrub_compare(a, ctx->stream));
+    }
+    return RSGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rsgpu_scrub_locatable(int k, int e, const unsigned char* coef)
+{
+    if (k <= 0 || e < 0 || k + e > RSGPU_MAX_SOURCES)
+        return 0;
+    if (e < 2)
+        return 0;
+    const std::vector<uint8_t> c = scrub_matrix(k, e, coef);
+    return scrub_locatable(k, e, c.data(), nullptr) ? 1 : 0;
+}
+
+int rsgpu_set_scrub_kernel(rsgpu_ctx* ctx, int kernel)
+{
+    if (!ctx || kernel < RSGPU_SCRUB_AUTO || kernel > RSGPU_SCRUB_TWO_PASS)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_scrub_kernel: unknown kernel");
+    ctx->scrub_kernel = kernel;
+    return RSGPU_OK;
+}
+
+int rsgpu_scrub_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                       const unsigned char* d_src, const unsigned char* d_parity,
+                       const unsigned char* coef, int flags, rsgpu_scrub_report* d_report)
+{
+    int rc = check_geom(ctx, k, e, len, pitch, blocks);
+    if (rc)
+        return rc;
+    if (!d_report || (uintptr_t)d_report % 8 != 0 || (flags & ~RSGPU_SCRUB_LOCATE) != 0)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_scrub_blocks: bad report pointer or flags");
+    const bool locate = (flags & RSGPU_SCRUB_LOCATE) != 0;
+    const bool work = e > 0 && len > 0;
+    if (work && (!d_src || !d_parity))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_scrub_blocks: null rows");
+    std::vector<uint8_t> c;
+    uint8_t rowtab[256];
+    if (locate) {
+        if (e >= 2)
+            c = scrub_matrix(k, e, coef);
+        if (e < 2 || !scrub_locatable(k, e, c.data(), rowtab))
+            return fail(ctx, RSGPU_ERR_UNSUPPORTED,
+                        "rsgpu_scrub_blocks: RSGPU_SCRUB_LOCATE needs a locatable matrix (rsgpu_scrub_locatable)");
+    }
+    ScrubFold* fold = reinterpret_cast<ScrubFold*>(d_report);
+    RS_HIP(ctx, hipMemsetAsync(d_report, 0, blocks * sizeof(rsgpu_scrub_report), ctx->stream));
+    if (work) {
+        const bool fused = ctx->scrub_kernel != RSGPU_SCRUB_TWO_PASS && !coef && rs_bitsliced_available(k, e) &&
+                           len % 32 == 0 && len < (1ull << 32) && pitch % 16 == 0 &&
+                           (uintptr_t)d_src % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
+        // block index in grid.y: larger batches as consecutive slices
+        for (size_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks) {
+            const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
+            const uint8_t* src = d_src + b0 * k * pitch;
+            const uint8_t* par = d_parity + b0 * e * pitch;
+            if (fused) {
+                KTimer kt(ctx, "k_rs_bs_scrub", nb);
+                RS_HIP(ctx, launch_rs_bitsliced_scrub(k, e, src, par, (long long)pitch, (long long)len,
+                                                      (long long)nb, fold + b0, locate ? 1 : 0, ctx->stream));
+            } else {
+                rc = scrub_two_pass(ctx, k, e, len, pitch, nb, src, par, coef, c, rowtab, locate, fold + b0);
+                if (rc)
+                    return rc;
+            }
+        }
+    }
+    KTimer kt(ctx, "k_scrub_finalise", blocks);
+    RS_HIP(ctx, launch_scrub_finalise(d_report, (long long)blocks, locate ? 1 : 0, ctx->stream));
     return RSGPU_OK;
 }
 

@@ -72,6 +72,14 @@ struct rsgpu_ctx {
     // grow-only device scratch for pointer tables / coefficient tables
     void* d_scratch = nullptr;
     size_t scratch_bytes = 0;
+    // parity scrub (rsgpu_scrub_blocks): the kernel choice, and the two-pass
+    // path's grow-only device buffer [ratio -> row table | e x k matrix |
+    // computed parity of a slice]; scrub_key = the (k, e, matrix) whose
+    // tables the buffer holds
+    int scrub_kernel = RSGPU_SCRUB_AUTO;
+    void* d_scrub = nullptr;
+    size_t scrub_bytes = 0;
+    std::vector<uint8_t> scrub_key;
     // pinned host staging for small uploads, guarded by an event
     void* h_stage = nullptr;
     size_t stage_bytes = 0;

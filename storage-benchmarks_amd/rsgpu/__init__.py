@@ -35,7 +35,8 @@ __all__ = [
     "RsGpuError", "lib", "Context", "GpuEncoder", "GpuDecoder", "ThroughputBenchmark",
     "gf_mul", "gf_inv", "gf_gen_rs_matrix", "gf_gen_cauchy1_matrix", "gf_invert_matrix",
     "gf_vect_mul_init", "ec_init_tables", "erasure_patterns", "EXPORTED_SYMBOLS",
-    "LIB_PATH",
+    "LIB_PATH", "scrub_locatable", "SCRUB_REPORT_DTYPE", "SCRUB_LOCATE", "SCRUB_CLEAN",
+    "SCRUB_ONE_ROW", "SCRUB_DAMAGED",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -52,6 +53,12 @@ DECODE_KERNELS = {"auto": 0, "one_matrix": 1, "general": 3, "generated": 4,
                   "fused": 2}  # deprecated alias of one_matrix (rsgpu.h RSGPU_DECODE_FUSED)
 # rsgpu_set_encode_kernel choices (include/rsgpu.h)
 ENCODE_KERNELS = {"auto": 0, "compiled": 1, "generated": 2, "threaded": 3}
+# rsgpu_set_scrub_kernel choices, rsgpu_scrub_blocks' flag and report
+# (include/rsgpu.h rsgpu_scrub_report)
+SCRUB_KERNELS = {"auto": 0, "fused": 1, "two_pass": 2}
+SCRUB_LOCATE = 1
+SCRUB_CLEAN, SCRUB_ONE_ROW, SCRUB_DAMAGED = 0, 1, 2
+SCRUB_REPORT_DTYPE = np.dtype([("bad_columns", "<u8"), ("status", "<i4"), ("row", "<i4")])
 
 vp = C.c_void_p
 sz = C.c_size_t
@@ -98,6 +105,9 @@ _SIGS = {
                                        vp]),
     "rsgpu_decode_apply": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, vp, vp]),
     "rsgpu_verify_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, vp]),
+    "rsgpu_scrub_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp]),
+    "rsgpu_scrub_locatable": (C.c_int, [C.c_int, C.c_int, vp]),
+    "rsgpu_set_scrub_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_host_alloc": (C.c_int, [vp, C.POINTER(vp), sz]),
     "rsgpu_host_free": (C.c_int, [vp, vp]),
     "rsgpu_encode_blocks_host": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp]),
@@ -204,6 +214,18 @@ def ec_init_tables(k: int, rows: int, a: np.ndarray) -> np.ndarray:
     g = np.zeros(32 * k * max(rows, 1), np.uint8)
     lib().rsgpu_ec_init_tables(k, rows, a.ctypes.data, g.ctypes.data)
     return g
+
+
+def scrub_locatable(k: int, e: int, coef=None) -> bool:
+    """Whether rsgpu_scrub_blocks can name a damaged row for the e x k parity
+    matrix ``coef`` (None: the gf_gen_rs_matrix code); include/rsgpu.h."""
+    cptr = None
+    if coef is not None:
+        coef = np.ascontiguousarray(coef, np.uint8)
+        if coef.size != k * e:
+            raise ValueError("coef must be e x k")
+        cptr = coef.ctypes.data
+    return bool(lib().rsgpu_scrub_locatable(k, e, cptr))
 
 
 def erasure_patterns(seed: int, blk0: int, blocks: int, k: int, e: int) -> np.ndarray:
@@ -384,6 +406,25 @@ class Context:
                                              _ptr(d_out), _ptr(d_err), _ptr(d_mism)),
                    "rsgpu_verify_blocks")
 
+    def set_scrub_kernel(self, kernel: str) -> None:
+        """Scrub kernel of scrub_blocks: auto | fused | two_pass
+        (include/rsgpu.h rsgpu_set_scrub_kernel)."""
+        self.check(lib().rsgpu_set_scrub_kernel(self._h, SCRUB_KERNELS[kernel]),
+                   "rsgpu_set_scrub_kernel")
+
+    def scrub_blocks(self, k, e, length, pitch, blocks, d_src, d_par, d_report, coef=None,
+                     locate: bool = True) -> None:
+        """Parity scrub (include/rsgpu.h rsgpu_scrub_blocks): d_report is
+        device memory of blocks x 16 bytes, 8-byte aligned, read back as
+        SCRUB_REPORT_DTYPE.  Enqueued on the context's stream."""
+        cptr = None
+        if coef is not None:
+            coef = np.ascontiguousarray(coef, np.uint8)
+            cptr = coef.ctypes.data
+        self.check(lib().rsgpu_scrub_blocks(self._h, k, e, length, pitch, blocks, _ptr(d_src),
+                                            _ptr(d_par), cptr, SCRUB_LOCATE if locate else 0,
+                                            _ptr(d_report)), "rsgpu_scrub_blocks")
+
     def fill_synthetic(self, d_rows, rows, length, pitch, seed, row0=0) -> None:
         self.check(lib().rsgpu_fill_synthetic(self._h, _ptr(d_rows), rows, length, pitch, seed,
                                               row0), "rsgpu_fill_synthetic")
@@ -443,6 +484,18 @@ class GpuEncoder:
 
     def encode_all(self) -> None:
         self.ctx.encode_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par)
+
+    def scrub(self, locate: bool = True) -> np.ndarray:
+        """Scrubs this encoder's blocks against their stored parity; the
+        per-block reports as a structured array (SCRUB_REPORT_DTYPE).
+        Synchronises (the reports are copied to the host)."""
+        import torch
+        rep = torch.empty(max(1, self.B) * SCRUB_REPORT_DTYPE.itemsize, dtype=torch.uint8,
+                          device=self.src.device)
+        self.ctx.scrub_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, rep,
+                              locate=locate)
+        self.ctx.synchronize()
+        return rep.cpu().numpy().view(SCRUB_REPORT_DTYPE)[: self.B].copy()
 
     def block_size(self) -> int:
         return self.m_block_size
