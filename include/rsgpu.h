@@ -335,6 +335,70 @@ int rsgpu_scrub_locatable(int k, int e, const unsigned char *coef);
 #define RSGPU_SCRUB_TWO_PASS 2
 int rsgpu_set_scrub_kernel(rsgpu_ctx *ctx, int kernel);
 
+/* ---- repair in place of what the scrub locates ---------------------------- */
+
+/* "Bad", "explains" and "locatable" as for the scrub above.  A bad column is
+ * CORRECTED only when exactly one row explains it:
+ *   source row r < k    src[r][i]     ^= s_0 / c[0][r]
+ *   parity row k + p0   parity[p0][i] ^= s_p0
+ * after which all its syndromes are zero.  Modes:
+ *   ONE_ROW   conservative: a block is written only when every bad column of
+ *             it names the same row (the scrub's ONE_ROW).  Such a block
+ *             reports REPAIRED, repaired_columns == bad_columns and `row`;
+ *             any other bad block reports DAMAGED, repaired_columns == 0,
+ *             row == -1, and none of its bytes is touched.
+ *   COLUMNS   every bad column that exactly one row explains is corrected,
+ *             whatever the block's other columns say; a column no row
+ *             explains stays as it was.  REPAIRED when every bad column was
+ *             corrected, DAMAGED when none, otherwise PARTIAL; `row` is the
+ *             common row of the corrected columns, -1 when they lie in
+ *             several rows or there is none.  Needs e >= 3: correcting one
+ *             error per column while still detecting two takes distance
+ *             e + 1 >= 2 * 1 + 2 = 4; with e = 2 (distance 3) a two-row
+ *             error of a column can be exactly the syndrome pair of a third
+ *             row, and only the agreement of the block's columns (ONE_ROW)
+ *             speaks against it.
+ * As the scrub's ONE_ROW, a correction follows the most likely explanation,
+ * not a proof: e - 1 or more damaged rows in one column can look like another
+ * single row and are then "corrected" into a consistent but wrong column.  In
+ * particular ONE_ROW mode with e = 2 can still miscorrect two damaged rows of
+ * one column.
+ *
+ * The report of a block is overwritten by every call, never accumulated.
+ * Bytes in [len, pitch) are never written, nor is any byte of a row that is
+ * not corrected, nor any byte of a column that is not bad. */
+#define RSGPU_REPAIR_CLEAN 0    /* no bad column */
+#define RSGPU_REPAIR_REPAIRED 1 /* every bad column corrected */
+#define RSGPU_REPAIR_PARTIAL 2  /* COLUMNS only: some corrected, some left as they were */
+#define RSGPU_REPAIR_DAMAGED 3  /* bad columns, nothing written to this block */
+typedef struct rsgpu_repair_report {
+    unsigned long long bad_columns;      /* before the repair */
+    unsigned long long repaired_columns; /* columns whose byte was corrected */
+    int status;
+    int row; /* the one row every corrected column lay in; -1 when none or several */
+} rsgpu_repair_report;                   /* 24 bytes */
+
+#define RSGPU_REPAIR_ONE_ROW 0 /* mode: correct only blocks the scrub would call ONE_ROW */
+#define RSGPU_REPAIR_COLUMNS 1 /* mode: correct every bad column exactly one row explains */
+
+/* Scrubs `blocks` blocks as rsgpu_scrub_blocks with RSGPU_SCRUB_LOCATE does
+ * (same layout, geometries, kernel choice by rsgpu_set_scrub_kernel) and
+ * corrects d_src / d_parity in place on the device; d_report [blocks] is
+ * DEVICE memory, 8-byte aligned.  Enqueued on the context's stream, no
+ * synchronisation and no host decision between locating and writing.
+ * e == 0: every block CLEAN.  Otherwise a matrix that is not locatable
+ * (e < 2 included), or COLUMNS with e < 3, returns RSGPU_ERR_UNSUPPORTED:
+ * nothing is enqueued, the report is untouched.  len == 0: every block CLEAN.
+ * Null rows, a null or misaligned report, an unknown mode: RSGPU_ERR_ARG,
+ * likewise with nothing enqueued and the report untouched.  After any other
+ * error (RSGPU_ERR_HIP, RSGPU_ERR_NOMEM: work may already be enqueued) the
+ * report's contents are undefined and must not be read as verdicts; rows are
+ * only ever written as described above, so a block is either as it was or
+ * corrected. */
+int rsgpu_repair_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                        unsigned char *d_src, unsigned char *d_parity,
+                        const unsigned char *coef, int mode, rsgpu_repair_report *d_report);
+
 /* ---- host-resident blocks (the reference's buffers, isa.cpp:46-58) ------- */
 
 /* Page-locked host memory for the host-resident calls: their copies then run

@@ -35,7 +35,9 @@
 //
 // The parity scrub of these codes (k_rs_bs_scrub) is the same accumulation
 // with another epilogue: the stored parity read and compared in registers
-// instead of the computed one written (scrub_tile).
+// instead of the computed one written (scrub_tile).  The repair
+// (k_rs_bs_repair) is that epilogue with the rows writable: a bad column's
+// byte is corrected where its row and error value are found.
 //
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -247,6 +249,7 @@ __device__ __forceinline__ void consume_part(uint32_t (&acc)[NR][8], uint32_t (&
 // workgroup reduces belongs to one block.
 struct ScrubArgs {
     static constexpr bool kScrub = true;
+    static constexpr bool kRepair = false;  // scrub_tile only reads the rows
     static constexpr int flat = 0;
     const uint8_t* src;  // [B][K] rows
     const uint8_t* par;  // [B][E] rows, the stored parity
@@ -254,6 +257,21 @@ struct ScrubArgs {
     long long blocks;
     ScrubFold* fold;  // [B], zeroed before the launch (rs_kernels.h)
     int locate;
+};
+
+// The repair (rsgpu_repair_blocks, k_rs_bs_repair): the scrub's arguments
+// with writable rows, the 24-byte fold and a mode (rs_kernels.h kRepair*).
+struct RepairArgs {
+    static constexpr bool kScrub = true;
+    static constexpr bool kRepair = true;  // scrub_tile corrects what it locates
+    static constexpr int flat = 0;
+    static constexpr int locate = 1;
+    uint8_t* src;  // [B][K] rows
+    uint8_t* par;  // [B][E] rows, the stored parity
+    long long pitch, len;
+    long long blocks;
+    RepairFold* fold;  // [B]: zeroed (kRepairLocate, kRepairColumns) or the final reports (kRepairGated)
+    int mode;
 };
 
 // log / antilog tables of the cold paths (the scrub's row location, the
@@ -276,8 +294,28 @@ alignas(16) __device__ const GfTables kGfBs = make_gf_tables();
 // only non-zero syndrome.  The maxima of row + 1 and of kScrubBias - row go
 // into the block's fold (order-independent atomics, one pair per wave).
 // LDS, in the part buffers: masks [NW][64] u32 | syn = 1 + E / 2 KiB of the 32.
-template <int K, int E, int NW, int G, int R0, int NR>
-__device__ __forceinline__ void scrub_tile(const ScrubArgs& a, uint32_t (&acc)[NR][8], bool inb, long long wo,
+//
+// The repair (A::kRepair) corrects in that walk: the thread at column c of
+// pass `pass` has the row and the error value x (s_0 for a source row, s_p0
+// for parity row K + p0), and column c is byte 8 pass + c % 8 of lane c / 8's
+// 32 bytes of the tile, so it XORs x into that byte of the global row: one
+// byte read and written per bad column, in the cold path only.  In place is
+// safe: by the barrier before the first pass every wave of the workgroup has
+// read all it reads of the tile (the sources before run_group's last barrier,
+// the stored parity before the mask barrier), and no other workgroup uses
+// those bytes -- the idle lanes of a row's tail tile do re-read the row head,
+// which the head's workgroup may be correcting, but what they read is
+// discarded (`inb`).  An idle lane's syndromes are zeros, so none of its
+// columns is bad; the lane bound is checked all the same before a write.
+// kRepairLocate writes nothing, kRepairGated folds nothing (the block's
+// report is final), kRepairColumns folds `row` over the corrected columns
+// only and counts them, one atomic per wave.  The walk's repair part is one
+// divergent region on purpose (address and value by selects, one `if` around
+// the store, the fold by selects): every nesting level keeps a saved exec
+// mask in an SGPR pair, and nested branches here cost the (64, 32) kernel 9
+// SGPR spills in its main loop and 1 % of its time (profiles/repair).
+template <int K, int E, int NW, int G, int R0, int NR, class A>
+__device__ __forceinline__ void scrub_tile(const A& a, uint32_t (&acc)[NR][8], bool inb, long long wo,
                                            long long wb, long long blk, int lane, uint4* ldsv, uint32_t m4,
                                            uint32_t m2, uint32_t m1)
 {
@@ -322,12 +360,15 @@ __device__ __forceinline__ void scrub_tile(const ScrubArgs& a, uint32_t (&acc)[N
         tm |= wmask[g * 64 + lane];
     if (__ballot(tm != 0) == 0)
         return;  // the same for every wave of the workgroup
-    ScrubFold* f = a.fold + blk;
+    auto* f = a.fold + blk;
     if constexpr (G == 0) {
         unsigned n = __builtin_popcount(tm);
         for (int off = 32; off > 0; off >>= 1)
             n += __shfl_down(n, off, 64);
-        if (lane == 0)
+        bool count = lane == 0;
+        if constexpr (A::kRepair)
+            count = count && a.mode != kRepairGated;
+        if (count)
             atomicAdd(&f->bad, (unsigned long long)n);
     }
     if (!a.locate)
@@ -336,6 +377,7 @@ __device__ __forceinline__ void scrub_tile(const ScrubArgs& a, uint32_t (&acc)[N
     const uint8_t* glog = kGfBs.log;
     const int tid = G * 64 + lane;
     unsigned hi1 = 0, lo1 = 0;
+    [[maybe_unused]] unsigned nrep = 0;
 #pragma unroll
     for (int rr = 0; rr < NR; ++rr)
         tr8(acc[rr], m4, m2, m1);  // syndrome planes -> bytes, in place
@@ -376,6 +418,25 @@ __device__ __forceinline__ void scrub_tile(const ScrubArgs& a, uint32_t (&acc)[N
             } else if (nz == 1) {
                 row = K + p0;
             }
+            if constexpr (A::kRepair) {
+                // the tile's byte offset of lane c / 8, and the column in it
+                const long long lo = (long long)blockIdx.x * 2048 + (c >> 3) * 32;
+                const bool src_row = row < K;
+                uint8_t* g = (src_row ? a.src : a.par) +
+                             ((size_t)wb * (src_row ? K : E) + (src_row ? row : row - K)) * a.pitch + lo +
+                             8 * pass + (c & 7);
+                const uint8_t x = src_row ? (uint8_t)s0 : syn[(row >= K ? row - K : 0) * 512 + c];
+                if (a.mode != kRepairLocate && row >= 0 && lo + 32 <= a.len) {
+                    *g ^= x;
+                    ++nrep;
+                }
+                // what folds into `row`: every bad column (kRepairLocate), the
+                // corrected ones (kRepairColumns), none (kRepairGated)
+                const bool folds = a.mode == kRepairLocate || (a.mode == kRepairColumns && row >= 0);
+                hi1 = max(hi1, !folds ? 0u : row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
+                lo1 = max(lo1, !folds ? 0u : row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
+                continue;
+            }
             hi1 = max(hi1, row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
             lo1 = max(lo1, row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
         }
@@ -388,6 +449,12 @@ __device__ __forceinline__ void scrub_tile(const ScrubArgs& a, uint32_t (&acc)[N
     if (lane == 0 && hi1) {
         atomicMax(&f->hi1, hi1);
         atomicMax(&f->lo1, lo1);
+    }
+    if constexpr (A::kRepair) {
+        for (int off = 32; off > 0; off >>= 1)
+            nrep += __shfl_down(nrep, off, 64);
+        if (lane == 0 && nrep && a.mode == kRepairColumns)
+            atomicAdd(&f->rep, (unsigned long long)nrep);
     }
 }
 
@@ -553,6 +620,30 @@ hipError_t launch_scrub(const ScrubArgs& a, hipStream_t st)
 {
     dim3 grid((unsigned)((a.len + 2047) / 2048), (unsigned)a.blocks);
     hipLaunchKernelGGL((k_rs_bs_scrub<K, E, C, NW>), grid, dim3(64 * NW), 0, st, a);
+    return hipGetLastError();
+}
+
+// The repair: k_rs_bs_scrub with the correcting epilogue.  kRepairGated runs
+// after the finalise of a kRepairLocate pass on the same stream: the block's
+// verdict is read (a scalar load, the block index is uniform) and a workgroup
+// whose block is not to be written leaves before it loads anything.
+template <int K, int E, int C, int NW>
+__global__ __launch_bounds__(64 * NW, (bs_waves_per_simd<E, NW>())) void k_rs_bs_repair(RepairArgs a)
+{
+    __shared__ uint4 lds[2][S * 2 * 64];
+    if (a.mode == kRepairGated && a.fold[blockIdx.y].hi1 != kRepairGate)
+        return;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    [&]<int... Gs>(std::integer_sequence<int, Gs...>) {
+        ((wave == Gs ? run_group<K, E, C, NW, Gs, true, RepairArgs>(a, lds) : void()), ...);
+    }(std::make_integer_sequence<int, NW>{});
+}
+
+template <int K, int E, int C, int NW>
+hipError_t launch_repair(const RepairArgs& a, hipStream_t st)
+{
+    dim3 grid((unsigned)((a.len + 2047) / 2048), (unsigned)a.blocks);
+    hipLaunchKernelGGL((k_rs_bs_repair<K, E, C, NW>), grid, dim3(64 * NW), 0, st, a);
     return hipGetLastError();
 }
 
@@ -952,6 +1043,23 @@ hipError_t launch_rs_bitsliced_scrub(int k, int e, const uint8_t* src, const uin
     if (k == 100 && e == 20) return bs::launch_scrub<100, 20, 20, 4>(a, st);
     if (k == 5 && e == 4) return bs::launch_scrub<5, 4, 5, 1>(a, st);
     if (k == 20 && e == 7) return bs::launch_scrub<20, 7, 20, 1>(a, st);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_rs_bitsliced_repair(int k, int e, uint8_t* src, uint8_t* par, long long pitch, long long len,
+                                      long long blocks, RepairFold* fold, int mode, hipStream_t st)
+{
+    if (blocks <= 0 || blocks > 65535 || len <= 0 || len % 32 != 0 || len >= (1ll << 32) || pitch < len ||
+        !src || !par || !fold || mode < kRepairLocate || mode > kRepairColumns)
+        return hipErrorInvalidValue;
+    const bs::RepairArgs a{src, par, pitch, len, blocks, fold, mode};
+    if (k == 16 && e == 4) return bs::launch_repair<16, 4, 16, 1>(a, st);
+    if (k == 16 && e == 8) return bs::launch_repair<16, 8, 16, 1>(a, st);
+    if (k == 64 && e == 32) return bs::launch_repair<64, 32, 16, 4>(a, st);
+    if (k == 64 && e == 16) return bs::launch_repair<64, 16, 16, 2>(a, st);
+    if (k == 100 && e == 20) return bs::launch_repair<100, 20, 20, 4>(a, st);
+    if (k == 5 && e == 4) return bs::launch_repair<5, 4, 5, 1>(a, st);
+    if (k == 20 && e == 7) return bs::launch_repair<20, 7, 20, 1>(a, st);
     return hipErrorInvalidValue;
 }
 

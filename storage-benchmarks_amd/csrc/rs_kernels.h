@@ -105,6 +105,7 @@ struct ScrubFold {
 // load when the rows allow); rowtab [256] maps the ratio s_1 / s_0 to a source row (255:
 // none), coef is the e x k matrix (both device memory, read only with locate).
 struct ScrubCmpArgs {
+    static constexpr bool kRepair = false;  // scrub_column only reads
     const uint8_t* calc;  // [B][e] rows: the parity of the sources, recomputed
     const uint8_t* par;   // [B][e] rows: the stored parity
     long long pitch, len, blocks;
@@ -122,6 +123,49 @@ hipError_t launch_scrub_finalise(void* report, long long blocks, int locate, hip
 hipError_t launch_rs_bitsliced_scrub(int k, int e, const uint8_t* src, const uint8_t* par, long long pitch,
                                      long long len, long long blocks, ScrubFold* fold, int locate,
                                      hipStream_t st);
+
+// Repair in place (rsgpu_repair_blocks): the scrub's kernels with writable
+// rows, correcting the byte of a bad column where its row and error value are
+// already at hand.  A block's 24-byte report holds its fold while a call is in
+// flight (zeroed by one memset, as the scrub's):
+//   bytes 0-7    bad columns (atomicAdd)
+//   bytes 8-15   corrected columns (atomicAdd; COLUMNS only)
+//   bytes 16-19  max of row + 1          over the columns that count for `row`:
+//   bytes 20-23  max of kScrubBias - row   every bad one (ONE_ROW, kScrubNoRow
+//                where no row explains it), the corrected ones (COLUMNS)
+// k_repair_finalise turns it into the report.  The kernels run in one of
+// three modes:
+//   kRepairLocate   ONE_ROW pass 1: fold, write no row byte
+//   kRepairGated    ONE_ROW pass 2, after the finalise: a workgroup whose
+//                   block's report is not REPAIRED (bytes 16-19 != kRepairGate)
+//                   leaves before it loads anything; the others correct and
+//                   touch no report
+//   kRepairColumns  COLUMNS: fold and correct in one pass
+constexpr int kRepairLocate = 0, kRepairGated = 1, kRepairColumns = 2;
+constexpr unsigned kRepairGate = 1;  // RSGPU_REPAIR_REPAIRED
+struct RepairFold {
+    unsigned long long bad, rep;
+    unsigned hi1, lo1;
+};
+struct RepairCmpArgs {
+    static constexpr bool kRepair = true;
+    static constexpr int locate = 1;
+    const uint8_t* calc;  // [B][e] rows: the parity of the sources, recomputed
+    uint8_t* src;         // [B][k] rows
+    uint8_t* par;         // [B][e] rows: the stored parity
+    long long pitch, len, blocks;
+    int k, e;
+    const uint8_t* rowtab;
+    const uint8_t* coef;
+    RepairFold* fold;  // [B]
+    int mode;
+};
+hipError_t launch_repair_compare(const RepairCmpArgs& a, hipStream_t st);
+// mode: RSGPU_REPAIR_ONE_ROW / _COLUMNS
+hipError_t launch_repair_finalise(void* report, long long blocks, int mode, hipStream_t st);
+// k_rs_bs_repair: k_rs_bs_scrub's conditions
+hipError_t launch_rs_bitsliced_repair(int k, int e, uint8_t* src, uint8_t* par, long long pitch, long long len,
+                                      long long blocks, RepairFold* fold, int mode, hipStream_t st);
 
 // Closed-form decode prepare for the gf_gen_rs_matrix code with e erased
 // originals and all e parity rows surviving, per block: erasure list

@@ -31,7 +31,11 @@
 //   k_scrub_compare   the parity scrub's two-pass path: recomputed vs stored
 //                     parity, bad columns counted and located per block;
 //                     k_scrub_finalise turns a block's fold into its report.
+//   k_repair_compare  the same compare over writable rows: corrects the byte
+//                     of a bad column in the row that explains it
+//                     (rsgpu_repair_blocks); k_repair_finalise.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -47,6 +51,10 @@ namespace rsgpu {
 
 static_assert(sizeof(ScrubFold) == sizeof(rsgpu_scrub_report) && sizeof(ScrubFold) == 16,
               "a block's fold lives in its report");
+static_assert(sizeof(RepairFold) == sizeof(rsgpu_repair_report) && sizeof(RepairFold) == 24 &&
+                  offsetof(rsgpu_repair_report, status) == offsetof(RepairFold, hi1) &&
+                  kRepairGate == RSGPU_REPAIR_REPAIRED,
+              "a block's fold lives in its report, and the report's status is the gate");
 
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
 {
@@ -713,9 +721,16 @@ __device__ __forceinline__ void scrub_fold_wave(ScrubFold* f, unsigned long long
     }
 }
 
-// byte column i of a block: counted when bad and, with locate, its row folded
-__device__ __forceinline__ void scrub_column(const ScrubCmpArgs& a, const uint8_t* calc, const uint8_t* par,
-                                             long long i, unsigned long long& bad, unsigned& hi1, unsigned& lo1)
+// byte column i of a block: counted when bad and, with locate, its row folded.
+// The repair (A::kRepair; wsrc, wpar: the block's writable rows) corrects the
+// column's byte in the row that explains it, src[r][i] ^= x or parity[p0][i]
+// ^= s_p0, and counts it in rep.  Only this thread reads or writes column i.
+template <class A>
+__device__ __forceinline__ void scrub_column(const A& a, const uint8_t* calc, const uint8_t* par, long long i,
+                                             unsigned long long& bad, unsigned& hi1, unsigned& lo1,
+                                             [[maybe_unused]] uint8_t* wsrc = nullptr,
+                                             [[maybe_unused]] uint8_t* wpar = nullptr,
+                                             [[maybe_unused]] unsigned long long* rep = nullptr)
 {
     int nz = 0, p0 = 0;
     uint8_t s0 = 0, s1 = 0;
@@ -746,6 +761,18 @@ __device__ __forceinline__ void scrub_column(const ScrubCmpArgs& a, const uint8_
         }
     } else if (nz == 1) {
         row = a.k + p0;
+    }
+    if constexpr (A::kRepair) {
+        if (a.mode != kRepairLocate && row >= 0) {
+            if (row < a.k)
+                wsrc[(size_t)row * a.pitch + i] ^= scrub_div(s0, a.coef[row]);  // x, as above
+            else  // the stored byte becomes the computed one
+                wpar[(size_t)p0 * a.pitch + i] = calc[(size_t)p0 * a.pitch + i];
+            ++*rep;
+        }
+        // `row` of a COLUMNS report: the common row of the corrected columns
+        if (a.mode == kRepairColumns && row < 0)
+            return;
     }
     hi1 = max(hi1, row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
     lo1 = max(lo1, row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
@@ -786,6 +813,64 @@ __global__ __launch_bounds__(256) void k_scrub_compare(ScrubCmpArgs a)
     scrub_fold_wave(&a.fold[b], bad, hi1, lo1);
 }
 
+// The repair's compare: k_scrub_compare over writable rows (rs_kernels.h
+// RepairCmpArgs for the modes).  A gated workgroup reads its block's verdict,
+// written by the finalise before it on the stream, and leaves when the block
+// is not to be written.  Writing in place is safe: a column's bytes are read
+// and written by one thread only, and `calc` still holds the parity of the
+// sources as they were.
+__global__ __launch_bounds__(256) void k_repair_compare(RepairCmpArgs a)
+{
+    const size_t b = blockIdx.y;
+    if (a.mode == kRepairGated && a.fold[b].hi1 != kRepairGate)
+        return;
+    const uint8_t* calc = a.calc + b * a.e * a.pitch;
+    uint8_t* src = a.src + b * a.k * a.pitch;
+    uint8_t* par = a.par + b * a.e * a.pitch;
+    unsigned long long bad = 0, rep = 0;
+    unsigned hi1 = 0, lo1 = 0;
+    const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long nthr = (long long)gridDim.x * blockDim.x;
+    const bool vec = ((reinterpret_cast<uintptr_t>(calc) | reinterpret_cast<uintptr_t>(par) |
+                       (uintptr_t)a.pitch) & 15) == 0;
+    const long long head = vec ? a.len & ~15LL : 0;
+    for (long long i = tid * 16; i < head; i += nthr * 16) {
+        uint4 any = make_uint4(0, 0, 0, 0);
+        for (int p = 0; p < a.e; ++p) {
+            const uint4 x = *reinterpret_cast<const uint4*>(calc + (size_t)p * a.pitch + i);
+            const uint4 y = *reinterpret_cast<const uint4*>(par + (size_t)p * a.pitch + i);
+            any.x |= x.x ^ y.x;
+            any.y |= x.y ^ y.y;
+            any.z |= x.z ^ y.z;
+            any.w |= x.w ^ y.w;
+        }
+        if ((any.x | any.y | any.z | any.w) == 0)
+            continue;
+        for (int j = 0; j < 16; ++j)
+            scrub_column(a, calc, par, i + j, bad, hi1, lo1, src, par, &rep);
+    }
+    for (long long i = head + tid; i < a.len; i += nthr)
+        scrub_column(a, calc, par, i, bad, hi1, lo1, src, par, &rep);
+    if (a.mode == kRepairGated)
+        return;  // the report is final
+    for (int off = 32; off > 0; off >>= 1) {
+        bad += __shfl_down(bad, off, 64);
+        rep += __shfl_down(rep, off, 64);
+        hi1 = max(hi1, (unsigned)__shfl_down((int)hi1, off, 64));
+        lo1 = max(lo1, (unsigned)__shfl_down((int)lo1, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0 && bad) {
+        RepairFold* f = &a.fold[b];
+        atomicAdd(&f->bad, bad);
+        if (rep)
+            atomicAdd(&f->rep, rep);
+        if (hi1) {
+            atomicMax(&f->hi1, hi1);
+            atomicMax(&f->lo1, lo1);
+        }
+    }
+}
+
 // the fold of every block into its report
 __global__ __launch_bounds__(256) void k_scrub_finalise(void* report, long long blocks, int locate)
 {
@@ -801,9 +886,52 @@ __global__ __launch_bounds__(256) void k_scrub_finalise(void* report, long long 
     static_cast<rsgpu_scrub_report*>(report)[b] = r;
 }
 
+// The repair's fold into its report (rs_kernels.h RepairFold).  ONE_ROW: the
+// scrub's verdict, REPAIRED standing for ONE_ROW, and the pass that follows
+// corrects every bad column of exactly those blocks.  COLUMNS: the status by
+// the two counts.
+__global__ __launch_bounds__(256) void k_repair_finalise(void* report, long long blocks, int mode)
+{
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= blocks)
+        return;
+    const RepairFold f = static_cast<const RepairFold*>(report)[b];
+    const bool one = f.hi1 >= 1 && f.hi1 < kScrubNoRow && f.hi1 - 1 == kScrubBias - f.lo1;
+    rsgpu_repair_report r;
+    r.bad_columns = f.bad;
+    if (mode == RSGPU_REPAIR_ONE_ROW) {
+        r.repaired_columns = one ? f.bad : 0;
+        r.status = f.bad == 0 ? RSGPU_REPAIR_CLEAN : one ? RSGPU_REPAIR_REPAIRED : RSGPU_REPAIR_DAMAGED;
+    } else {
+        r.repaired_columns = f.rep;
+        r.status = f.bad == 0       ? RSGPU_REPAIR_CLEAN
+                   : f.rep == f.bad ? RSGPU_REPAIR_REPAIRED
+                   : f.rep == 0     ? RSGPU_REPAIR_DAMAGED
+                                    : RSGPU_REPAIR_PARTIAL;
+    }
+    r.row = (f.bad != 0 && one) ? (int)f.hi1 - 1 : -1;
+    static_cast<rsgpu_repair_report*>(report)[b] = r;
+}
+
 // ---------------------------------------------------------------------------
 // Host launch wrappers (declared in rs_kernels.h)
 // ---------------------------------------------------------------------------
+
+hipError_t launch_repair_compare(const RepairCmpArgs& a, hipStream_t st)
+{
+    if (a.blocks <= 0 || a.blocks > 65535 || a.len <= 0 || a.e <= 0 || !a.src || !a.par || !a.calc || !a.fold)
+        return hipErrorInvalidValue;
+    const long long gx = std::min<long long>((a.len + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_repair_compare, dim3((unsigned)gx, (unsigned)a.blocks), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_repair_finalise(void* report, long long blocks, int mode, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_repair_finalise, dim3((unsigned)((blocks + 255) / 256)), dim3(256), 0, st, report,
+                       blocks, mode);
+    return hipGetLastError();
+}
 
 hipError_t launch_scrub_compare(const ScrubCmpArgs& a, hipStream_t st)
 {

@@ -1798,6 +1798,29 @@ int ensure_scrub(rsgpu_ctx* ctx, size_t bytes)
     return RSGPU_OK;
 }
 
+// the ratio -> row table and the matrix at the head of the scrub buffer
+int scrub_tables(rsgpu_ctx* ctx, int k, int e, const std::vector<uint8_t>& c, const uint8_t* rowtab)
+{
+    std::vector<uint8_t> key(8 + c.size());
+    std::memcpy(key.data(), &k, 4);
+    std::memcpy(key.data() + 4, &e, 4);
+    std::memcpy(key.data() + 8, c.data(), c.size());
+    if (key == ctx->scrub_key)
+        return RSGPU_OK;
+    // the tables of another matrix: upload once
+    void* stage;
+    int rc = get_stage(ctx, 256 + c.size(), &stage);
+    if (rc)
+        return rc;
+    std::memcpy(stage, rowtab, 256);
+    std::memcpy((char*)stage + 256, c.data(), c.size());
+    rc = upload(ctx, ctx->d_scrub, 256 + c.size());
+    if (rc)
+        return rc;
+    ctx->scrub_key = std::move(key);
+    return RSGPU_OK;
+}
+
 int scrub_two_pass(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks, const uint8_t* d_src,
                    const uint8_t* d_parity, const unsigned char* coef, const std::vector<uint8_t>& c,
                    const uint8_t* rowtab, bool locate, ScrubFold* fold)
@@ -1809,22 +1832,9 @@ int scrub_two_pass(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_
         return rc;
     uint8_t* d = (uint8_t*)ctx->d_scrub;
     if (locate) {
-        std::vector<uint8_t> key(8 + c.size());
-        std::memcpy(key.data(), &k, 4);
-        std::memcpy(key.data() + 4, &e, 4);
-        std::memcpy(key.data() + 8, c.data(), c.size());
-        if (key != ctx->scrub_key) {  // the tables of another matrix: upload once
-            void* stage;
-            rc = get_stage(ctx, 256 + c.size(), &stage);
-            if (rc)
-                return rc;
-            std::memcpy(stage, rowtab, 256);
-            std::memcpy((char*)stage + 256, c.data(), c.size());
-            rc = upload(ctx, d, 256 + c.size());
-            if (rc)
-                return rc;
-            ctx->scrub_key = std::move(key);
-        }
+        rc = scrub_tables(ctx, k, e, c, rowtab);
+        if (rc)
+            return rc;
     }
     uint8_t* calc = d + kScrubTabBytes;
     for (size_t b0 = 0; b0 < blocks; b0 += slice) {
@@ -1846,6 +1856,59 @@ int scrub_two_pass(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_
         a.locate = locate ? 1 : 0;
         KTimer kt(ctx, "k_scrub_compare", nb);
         RS_HIP(ctx, launch_scrub_compare(a, ctx->stream));
+    }
+    return RSGPU_OK;
+}
+
+// The repair of at most kMaxGridBlocks blocks through the two-pass path, slice
+// by slice of the scratch: the encode, then COLUMNS: the correcting compare;
+// ONE_ROW: the compare that only folds, the finalise of the slice's reports,
+// and the gated correcting compare, while the slice's computed parity is
+// still in the scratch.  The caller finalises a COLUMNS call.
+int repair_two_pass(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks, uint8_t* d_src,
+                    uint8_t* d_parity, const unsigned char* coef, const std::vector<uint8_t>& c,
+                    const uint8_t* rowtab, int mode, RepairFold* fold)
+{
+    const size_t per_block = (size_t)e * pitch;
+    const size_t slice = std::max<size_t>(1, std::min(blocks, kScrubParityBytes / per_block));
+    int rc = ensure_scrub(ctx, kScrubTabBytes + slice * per_block);
+    if (rc)
+        return rc;
+    rc = scrub_tables(ctx, k, e, c, rowtab);
+    if (rc)
+        return rc;
+    uint8_t* d = (uint8_t*)ctx->d_scrub;
+    for (size_t b0 = 0; b0 < blocks; b0 += slice) {
+        const size_t nb = std::min(slice, blocks - b0);
+        rc = rsgpu_encode_blocks(ctx, k, e, len, pitch, nb, d_src + b0 * k * pitch, d + kScrubTabBytes, coef);
+        if (rc)
+            return rc;
+        RepairCmpArgs a{};
+        a.calc = d + kScrubTabBytes;
+        a.src = d_src + b0 * k * pitch;
+        a.par = d_parity + b0 * per_block;
+        a.pitch = (long long)pitch;
+        a.len = (long long)len;
+        a.blocks = (long long)nb;
+        a.k = k;
+        a.e = e;
+        a.rowtab = d;
+        a.coef = d + 256;
+        a.fold = fold + b0;
+        a.mode = mode == RSGPU_REPAIR_COLUMNS ? kRepairColumns : kRepairLocate;
+        {
+            KTimer kt(ctx, "k_repair_compare", nb);
+            RS_HIP(ctx, launch_repair_compare(a, ctx->stream));
+        }
+        if (mode == RSGPU_REPAIR_ONE_ROW) {
+            {
+                KTimer kt(ctx, "k_repair_finalise", nb);
+                RS_HIP(ctx, launch_repair_finalise(fold + b0, (long long)nb, mode, ctx->stream));
+            }
+            a.mode = kRepairGated;
+            KTimer kt(ctx, "k_repair_compare_gated", nb);
+            RS_HIP(ctx, launch_repair_compare(a, ctx->stream));
+        }
     }
     return RSGPU_OK;
 }
@@ -1918,6 +1981,72 @@ int rsgpu_scrub_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, s
     }
     KTimer kt(ctx, "k_scrub_finalise", blocks);
     RS_HIP(ctx, launch_scrub_finalise(d_report, (long long)blocks, locate ? 1 : 0, ctx->stream));
+    return RSGPU_OK;
+}
+
+int rsgpu_repair_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                        unsigned char* d_src, unsigned char* d_parity, const unsigned char* coef, int mode,
+                        rsgpu_repair_report* d_report)
+{
+    int rc = check_geom(ctx, k, e, len, pitch, blocks);
+    if (rc)
+        return rc;
+    if (!d_report || (uintptr_t)d_report % 8 != 0 ||
+        (mode != RSGPU_REPAIR_ONE_ROW && mode != RSGPU_REPAIR_COLUMNS))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_repair_blocks: bad report pointer or mode");
+    const bool work = e > 0 && len > 0;
+    if (work && (!d_src || !d_parity))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_repair_blocks: null rows");
+    std::vector<uint8_t> c;
+    uint8_t rowtab[256];
+    if (e > 0) {  // e == 0: no parity, nothing can be bad
+        if (e >= 2)
+            c = scrub_matrix(k, e, coef);
+        if (e < 2 || !scrub_locatable(k, e, c.data(), rowtab))
+            return fail(ctx, RSGPU_ERR_UNSUPPORTED,
+                        "rsgpu_repair_blocks: needs a locatable matrix (rsgpu_scrub_locatable)");
+        if (mode == RSGPU_REPAIR_COLUMNS && e < 3)
+            return fail(ctx, RSGPU_ERR_UNSUPPORTED, "rsgpu_repair_blocks: RSGPU_REPAIR_COLUMNS needs e >= 3");
+    }
+    RepairFold* fold = reinterpret_cast<RepairFold*>(d_report);
+    RS_HIP(ctx, hipMemsetAsync(d_report, 0, blocks * sizeof(rsgpu_repair_report), ctx->stream));
+    if (!work) {
+        KTimer kt(ctx, "k_repair_finalise", blocks);
+        RS_HIP(ctx, launch_repair_finalise(d_report, (long long)blocks, mode, ctx->stream));
+        return RSGPU_OK;
+    }
+    const bool fused = ctx->scrub_kernel != RSGPU_SCRUB_TWO_PASS && !coef && rs_bitsliced_available(k, e) &&
+                       len % 32 == 0 && len < (1ull << 32) && pitch % 16 == 0 && (uintptr_t)d_src % 16 == 0 &&
+                       (uintptr_t)d_parity % 16 == 0;
+    // block index in grid.y: larger batches as consecutive slices, each
+    // complete (located, finalised, corrected) before the next
+    for (size_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks) {
+        const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
+        uint8_t* src = d_src + b0 * k * pitch;
+        uint8_t* par = d_parity + b0 * e * pitch;
+        if (!fused) {
+            rc = repair_two_pass(ctx, k, e, len, pitch, nb, src, par, coef, c, rowtab, mode, fold + b0);
+            if (rc)
+                return rc;
+            if (mode == RSGPU_REPAIR_ONE_ROW)
+                continue;  // finalised slice by slice
+        } else {
+            KTimer kt(ctx, "k_rs_bs_repair", nb);
+            RS_HIP(ctx, launch_rs_bitsliced_repair(k, e, src, par, (long long)pitch, (long long)len, (long long)nb,
+                                                   fold + b0, mode == RSGPU_REPAIR_COLUMNS ? kRepairColumns
+                                                                                           : kRepairLocate,
+                                                   ctx->stream));
+        }
+        {
+            KTimer kt(ctx, "k_repair_finalise", nb);
+            RS_HIP(ctx, launch_repair_finalise(fold + b0, (long long)nb, mode, ctx->stream));
+        }
+        if (fused && mode == RSGPU_REPAIR_ONE_ROW) {
+            KTimer kt(ctx, "k_rs_bs_repair_gated", nb);
+            RS_HIP(ctx, launch_rs_bitsliced_repair(k, e, src, par, (long long)pitch, (long long)len, (long long)nb,
+                                                   fold + b0, kRepairGated, ctx->stream));
+        }
+    }
     return RSGPU_OK;
 }
 

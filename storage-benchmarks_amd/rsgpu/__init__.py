@@ -36,7 +36,8 @@ __all__ = [
     "gf_mul", "gf_inv", "gf_gen_rs_matrix", "gf_gen_cauchy1_matrix", "gf_invert_matrix",
     "gf_vect_mul_init", "ec_init_tables", "erasure_patterns", "EXPORTED_SYMBOLS",
     "LIB_PATH", "scrub_locatable", "SCRUB_REPORT_DTYPE", "SCRUB_LOCATE", "SCRUB_CLEAN",
-    "SCRUB_ONE_ROW", "SCRUB_DAMAGED",
+    "SCRUB_ONE_ROW", "SCRUB_DAMAGED", "REPAIR_REPORT_DTYPE", "REPAIR_MODES", "REPAIR_ONE_ROW",
+    "REPAIR_COLUMNS", "REPAIR_CLEAN", "REPAIR_REPAIRED", "REPAIR_PARTIAL", "REPAIR_DAMAGED",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -59,6 +60,13 @@ SCRUB_KERNELS = {"auto": 0, "fused": 1, "two_pass": 2}
 SCRUB_LOCATE = 1
 SCRUB_CLEAN, SCRUB_ONE_ROW, SCRUB_DAMAGED = 0, 1, 2
 SCRUB_REPORT_DTYPE = np.dtype([("bad_columns", "<u8"), ("status", "<i4"), ("row", "<i4")])
+# rsgpu_repair_blocks' modes, statuses and report (include/rsgpu.h
+# rsgpu_repair_report)
+REPAIR_ONE_ROW, REPAIR_COLUMNS = 0, 1
+REPAIR_MODES = {"one_row": REPAIR_ONE_ROW, "columns": REPAIR_COLUMNS}
+REPAIR_CLEAN, REPAIR_REPAIRED, REPAIR_PARTIAL, REPAIR_DAMAGED = 0, 1, 2, 3
+REPAIR_REPORT_DTYPE = np.dtype([("bad_columns", "<u8"), ("repaired_columns", "<u8"),
+                                ("status", "<i4"), ("row", "<i4")])
 
 vp = C.c_void_p
 sz = C.c_size_t
@@ -107,6 +115,7 @@ _SIGS = {
     "rsgpu_verify_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, vp]),
     "rsgpu_scrub_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp]),
     "rsgpu_scrub_locatable": (C.c_int, [C.c_int, C.c_int, vp]),
+    "rsgpu_repair_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp]),
     "rsgpu_set_scrub_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_host_alloc": (C.c_int, [vp, C.POINTER(vp), sz]),
     "rsgpu_host_free": (C.c_int, [vp, vp]),
@@ -425,6 +434,20 @@ class Context:
                                             _ptr(d_par), cptr, SCRUB_LOCATE if locate else 0,
                                             _ptr(d_report)), "rsgpu_scrub_blocks")
 
+    def repair_blocks(self, k, e, length, pitch, blocks, d_src, d_par, d_report, coef=None,
+                      mode: str = "one_row") -> None:
+        """Repair in place (include/rsgpu.h rsgpu_repair_blocks): d_src and
+        d_par are corrected on the device, mode one_row | columns; d_report
+        is device memory of blocks x 24 bytes, 8-byte aligned, read back as
+        REPAIR_REPORT_DTYPE.  Enqueued on the context's stream."""
+        cptr = None
+        if coef is not None:
+            coef = np.ascontiguousarray(coef, np.uint8)
+            cptr = coef.ctypes.data
+        self.check(lib().rsgpu_repair_blocks(self._h, k, e, length, pitch, blocks, _ptr(d_src),
+                                             _ptr(d_par), cptr, REPAIR_MODES[mode],
+                                             _ptr(d_report)), "rsgpu_repair_blocks")
+
     def fill_synthetic(self, d_rows, rows, length, pitch, seed, row0=0) -> None:
         self.check(lib().rsgpu_fill_synthetic(self._h, _ptr(d_rows), rows, length, pitch, seed,
                                               row0), "rsgpu_fill_synthetic")
@@ -496,6 +519,19 @@ class GpuEncoder:
                               locate=locate)
         self.ctx.synchronize()
         return rep.cpu().numpy().view(SCRUB_REPORT_DTYPE)[: self.B].copy()
+
+    def repair(self, mode: str = "one_row") -> np.ndarray:
+        """Scrubs this encoder's blocks and corrects their rows in place
+        (mode one_row | columns, include/rsgpu.h rsgpu_repair_blocks); the
+        per-block reports as a structured array (REPAIR_REPORT_DTYPE).
+        Synchronises (the reports are copied to the host)."""
+        import torch
+        rep = torch.empty(max(1, self.B) * REPAIR_REPORT_DTYPE.itemsize, dtype=torch.uint8,
+                          device=self.src.device)
+        self.ctx.repair_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, rep,
+                               mode=mode)
+        self.ctx.synchronize()
+        return rep.cpu().numpy().view(REPAIR_REPORT_DTYPE)[: self.B].copy()
 
     def block_size(self) -> int:
         return self.m_block_size
