@@ -315,4 +315,28 @@ hipError_t launch_row_ptrs(const uint8_t* base, long long pitch, int rows_per_bl
 hipError_t launch_update(const uint8_t* data, uint8_t* const* coding, const uint4* tabs4,
                          const uint32_t* ctab, int rows, long long len, hipStream_t st);
 
+// Partial-stripe update (rsgpu_update_blocks, rs_update.hip k_update_blocks):
+// per block the rows its list names are replaced (or taken as deltas) and the
+// e parity rows follow, parity[p] ^= XOR_i c[p][j_i] * delta_i.  blocks <=
+// 65535 per launch.
+struct UpdateArgs {
+    int k, e, u;
+    int delta;            // non-zero: upd rows are deltas, src is not touched
+    long long pitch, blocks;
+    const uint8_t* cols;  // [B][u] listed rows, ascending, then RSGPU_UPDATE_NONE
+    const uint8_t* upd;   // [B][u] rows
+    uint8_t* src;         // [B][k] rows (unused with delta)
+    uint8_t* par;         // [B][e] rows
+    const uint8_t* coef;  // device e x k matrix
+    const uint4* tab4;    // device [256]: perm_tables words 0-3 of every coefficient value
+    const uint32_t* tabc; // device [256]: perm_tables word 4
+    int* status;          // [B]: 0, or -2 for a malformed list (block untouched)
+};
+// rows of a list one walk over the parity serves (the in-register group)
+int update_group_rows();
+// bytes == false: columns [col0, col1) are 16-byte units of 16-byte aligned
+// rows; bytes == true: byte columns, any alignment.  An empty range only
+// validates the lists and writes the statuses.
+hipError_t launch_update_blocks(const UpdateArgs& a, bool bytes, long long col0, long long col1, hipStream_t st);
+
 }  // namespace rsgpu

@@ -611,6 +611,8 @@ int rsgpu_destroy(rsgpu_ctx* ctx)
         (void)hipFree(ctx->d_scratch);
     if (ctx->d_scrub)
         (void)hipFree(ctx->d_scrub);
+    if (ctx->d_update)
+        (void)hipFree(ctx->d_update);
     if (ctx->h_stage)
         (void)hipHostFree(ctx->h_stage);
     if (ctx->stage_done)
@@ -2045,6 +2047,125 @@ int rsgpu_repair_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
             KTimer kt(ctx, "k_rs_bs_repair_gated", nb);
             RS_HIP(ctx, launch_rs_bitsliced_repair(k, e, src, par, (long long)pitch, (long long)len, (long long)nb,
                                                    fold + b0, kRepairGated, ctx->stream));
+        }
+    }
+    return RSGPU_OK;
+}
+
+// ---- partial-stripe update -----------------------------------------------------
+
+// The update's device buffer: [tab4 256 x 16 B | tabc 256 x 4 B | matrix].
+constexpr size_t kUpdTab4Bytes = 256 * sizeof(uint4);
+constexpr size_t kUpdTabBytes = kUpdTab4Bytes + 256 * sizeof(uint32_t);
+constexpr size_t kUpdMatrixBytes = (size_t)RSGPU_MAX_SOURCES * RSGPU_MAX_SOURCES;
+
+// The tables (once per context) and the matrix (when it differs from the one
+// the buffer holds) go up on the stream, ahead of the kernel that reads them.
+static int update_tables(rsgpu_ctx* ctx, int k, int e, const unsigned char* coef)
+{
+    const bool fresh = ctx->d_update == nullptr;
+    if (fresh) {
+        RS_HIP(ctx, hipMalloc(&ctx->d_update, kUpdTabBytes + kUpdMatrixBytes));
+        ctx->update_key.clear();
+    }
+    std::vector<uint8_t> c;
+    std::vector<uint8_t> key;
+    if (e > 0) {
+        c = scrub_matrix(k, e, coef);
+        key.resize(8 + c.size());
+        std::memcpy(key.data(), &k, 4);
+        std::memcpy(key.data() + 4, &e, 4);
+        std::memcpy(key.data() + 8, c.data(), c.size());
+    }
+    const bool matrix = e > 0 && key != ctx->update_key;
+    if (!fresh && !matrix)
+        return RSGPU_OK;
+    const size_t first = fresh ? 0 : kUpdTabBytes;
+    const size_t last = matrix ? kUpdTabBytes + c.size() : kUpdTabBytes;
+    void* stage;
+    int rc = get_stage(ctx, kUpdTabBytes + kUpdMatrixBytes, &stage);
+    if (rc)
+        return rc;
+    if (fresh) {
+        uint4* t4 = (uint4*)stage;
+        uint32_t* tc = (uint32_t*)((char*)stage + kUpdTab4Bytes);
+        for (int v = 0; v < 256; ++v) {
+            uint32_t t[5];
+            perm_tables((uint8_t)v, t);
+            t4[v] = make_uint4(t[0], t[1], t[2], t[3]);
+            tc[v] = t[4];
+        }
+    }
+    if (matrix)
+        std::memcpy((char*)stage + kUpdTabBytes, c.data(), c.size());
+    RS_HIP(ctx, hipMemcpyAsync((char*)ctx->d_update + first, (char*)stage + first, last - first,
+                               hipMemcpyHostToDevice, ctx->stream));
+    RS_HIP(ctx, hipEventRecord(ctx->stage_done, ctx->stream));
+    ctx->stage_pending = true;
+    if (matrix)
+        ctx->update_key = std::move(key);
+    return RSGPU_OK;
+}
+
+static bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return an > 0 && bn > 0 && a0 < b0 + bn && b0 < a0 + an;
+}
+
+int rsgpu_update_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks, int u,
+                        const unsigned char* d_cols, const unsigned char* d_upd, unsigned char* d_src,
+                        unsigned char* d_parity, const unsigned char* coef, int flags, int* d_status)
+{
+    int rc = check_geom(ctx, k, e, len, pitch, blocks);
+    if (rc)
+        return rc;
+    if (u < 1 || u > k || (flags & ~RSGPU_UPDATE_DELTA) != 0 || !d_cols || !d_status)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_update_blocks: bad u, flags, list or status pointer");
+    const bool delta = (flags & RSGPU_UPDATE_DELTA) != 0;
+    const bool src_used = !delta, par_used = e > 0;
+    if (len > 0 && (((src_used || par_used) && !d_upd) || (src_used && !d_src) || (par_used && !d_parity)))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_update_blocks: null rows");
+    // rows i of a buffer of R rows per block end at ((blocks R - 1) pitch + len)
+    auto span = [&](size_t rows) { return len == 0 ? (size_t)0 : (blocks * rows - 1) * pitch + len; };
+    if ((src_used && ranges_overlap(d_upd, span((size_t)u), d_src, span((size_t)k))) ||
+        (par_used && ranges_overlap(d_upd, span((size_t)u), d_parity, span((size_t)e))))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_update_blocks: d_upd overlaps d_src or d_parity");
+    rc = update_tables(ctx, k, e, coef);
+    if (rc)
+        return rc;
+    const bool work = len > 0 && (src_used || par_used);
+    const bool vec = pitch % 16 == 0 && (uintptr_t)d_upd % 16 == 0 && (!src_used || (uintptr_t)d_src % 16 == 0) &&
+                     (!par_used || (uintptr_t)d_parity % 16 == 0);
+    const long long n16 = work && vec ? (long long)(len / 16) : 0;
+    // block index in grid.y: larger batches as consecutive slices
+    for (size_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks) {
+        const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
+        UpdateArgs a{};
+        a.k = k;
+        a.e = e;
+        a.u = u;
+        a.delta = delta ? 1 : 0;
+        a.pitch = (long long)pitch;
+        a.blocks = (long long)nb;
+        a.cols = d_cols + b0 * (size_t)u;
+        a.upd = d_upd ? d_upd + b0 * (size_t)u * pitch : nullptr;
+        a.src = src_used && d_src ? d_src + b0 * (size_t)k * pitch : nullptr;
+        a.par = par_used && d_parity ? d_parity + b0 * (size_t)e * pitch : nullptr;
+        a.tab4 = (const uint4*)ctx->d_update;
+        a.tabc = (const uint32_t*)((const char*)ctx->d_update + kUpdTab4Bytes);
+        a.coef = (const uint8_t*)ctx->d_update + kUpdTabBytes;
+        a.status = d_status + b0;
+        if (n16 > 0) {
+            KTimer kt(ctx, "k_update_blocks", nb);
+            RS_HIP(ctx, launch_update_blocks(a, false, 0, n16, ctx->stream));
+        }
+        // the bytes the vector kernel leaves: all of them, the len % 16 tail,
+        // or none (the launch then only writes the statuses)
+        const long long first = n16 * 16, end = work ? (long long)len : 0;
+        if (n16 == 0 || first < end) {
+            KTimer kt(ctx, n16 > 0 ? "k_update_blocks(tail)" : "k_update_blocks(bytes)", nb);
+            RS_HIP(ctx, launch_update_blocks(a, true, first, first < end ? end : first, ctx->stream));
         }
     }
     return RSGPU_OK;

@@ -80,6 +80,11 @@ struct rsgpu_ctx {
     void* d_scrub = nullptr;
     size_t scrub_bytes = 0;
     std::vector<uint8_t> scrub_key;
+    // partial-stripe update (rsgpu_update_blocks): one fixed-size device
+    // buffer [v_perm tables of the 256 coefficient values | e x k matrix];
+    // update_key = the (k, e, matrix) it holds
+    void* d_update = nullptr;
+    std::vector<uint8_t> update_key;
     // pinned host staging for small uploads, guarded by an event
     void* h_stage = nullptr;
     size_t stage_bytes = 0;

@@ -38,6 +38,7 @@ __all__ = [
     "LIB_PATH", "scrub_locatable", "SCRUB_REPORT_DTYPE", "SCRUB_LOCATE", "SCRUB_CLEAN",
     "SCRUB_ONE_ROW", "SCRUB_DAMAGED", "REPAIR_REPORT_DTYPE", "REPAIR_MODES", "REPAIR_ONE_ROW",
     "REPAIR_COLUMNS", "REPAIR_CLEAN", "REPAIR_REPAIRED", "REPAIR_PARTIAL", "REPAIR_DAMAGED",
+    "UPDATE_NONE", "UPDATE_DELTA",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -67,6 +68,9 @@ REPAIR_MODES = {"one_row": REPAIR_ONE_ROW, "columns": REPAIR_COLUMNS}
 REPAIR_CLEAN, REPAIR_REPAIRED, REPAIR_PARTIAL, REPAIR_DAMAGED = 0, 1, 2, 3
 REPAIR_REPORT_DTYPE = np.dtype([("bad_columns", "<u8"), ("repaired_columns", "<u8"),
                                 ("status", "<i4"), ("row", "<i4")])
+# rsgpu_update_blocks' list padding and flag (include/rsgpu.h)
+UPDATE_NONE = 255
+UPDATE_DELTA = 1
 
 vp = C.c_void_p
 sz = C.c_size_t
@@ -117,6 +121,8 @@ _SIGS = {
     "rsgpu_scrub_locatable": (C.c_int, [C.c_int, C.c_int, vp]),
     "rsgpu_repair_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp]),
     "rsgpu_set_scrub_kernel": (C.c_int, [vp, C.c_int]),
+    "rsgpu_update_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, C.c_int, vp, vp, vp, vp, vp,
+                                      C.c_int, vp]),
     "rsgpu_host_alloc": (C.c_int, [vp, C.POINTER(vp), sz]),
     "rsgpu_host_free": (C.c_int, [vp, vp]),
     "rsgpu_encode_blocks_host": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp]),
@@ -448,6 +454,23 @@ class Context:
                                              _ptr(d_par), cptr, REPAIR_MODES[mode],
                                              _ptr(d_report)), "rsgpu_repair_blocks")
 
+    def update_blocks(self, k, e, length, pitch, blocks, u, d_cols, d_upd, d_src, d_par, d_status,
+                      coef=None, delta: bool = False) -> None:
+        """Partial-stripe update (include/rsgpu.h rsgpu_update_blocks): the
+        rows block b's list d_cols[b] names (device, blocks x u bytes,
+        ascending, padded with UPDATE_NONE) are replaced by d_upd's rows and
+        the parity follows; with delta the rows of d_upd are new ^ old and
+        d_src may be None.  d_status is device memory of blocks int32.
+        Enqueued on the context's stream."""
+        cptr = None
+        if coef is not None:
+            coef = np.ascontiguousarray(coef, np.uint8)
+            cptr = coef.ctypes.data
+        self.check(lib().rsgpu_update_blocks(self._h, k, e, length, pitch, blocks, u, _ptr(d_cols),
+                                             _ptr(d_upd), _ptr(d_src), _ptr(d_par), cptr,
+                                             UPDATE_DELTA if delta else 0, _ptr(d_status)),
+                   "rsgpu_update_blocks")
+
     def fill_synthetic(self, d_rows, rows, length, pitch, seed, row0=0) -> None:
         self.check(lib().rsgpu_fill_synthetic(self._h, _ptr(d_rows), rows, length, pitch, seed,
                                               row0), "rsgpu_fill_synthetic")
@@ -532,6 +555,28 @@ class GpuEncoder:
                                mode=mode)
         self.ctx.synchronize()
         return rep.cpu().numpy().view(REPAIR_REPORT_DTYPE)[: self.B].copy()
+
+    def update(self, cols, rows, delta: bool = False) -> np.ndarray:
+        """Overwrites source rows of this encoder's blocks and brings the
+        parity along (include/rsgpu.h rsgpu_update_blocks): cols is a
+        (blocks, u) uint8 array of row indices per block, ascending and
+        padded with UPDATE_NONE; rows a device tensor of the blocks x u update
+        rows at this encoder's pitch (deltas, new ^ old, with delta=True).
+        Returns the per-block statuses (0, or -2 for a malformed list).
+        Synchronises (the statuses are copied to the host)."""
+        import torch
+        cols = np.ascontiguousarray(cols, np.uint8)
+        if cols.ndim != 2 or cols.shape[0] != self.B:
+            raise ValueError("cols must be a (blocks, u) array")
+        u = cols.shape[1]
+        if rows.numel() < self.B * u * self.pitch:
+            raise ValueError("rows must hold blocks x u rows at the encoder's pitch")
+        d_cols = torch.from_numpy(cols).to(self.src.device)
+        status = torch.empty(max(1, self.B), dtype=torch.int32, device=self.src.device)
+        self.ctx.update_blocks(self.k, self.e, self.L, self.pitch, self.B, u, d_cols, rows,
+                               None if delta else self.src, self.par, status, delta=delta)
+        self.ctx.synchronize()
+        return status.cpu().numpy()[: self.B].copy()
 
     def block_size(self) -> int:
         return self.m_block_size
