@@ -335,6 +335,86 @@ int rsgpu_scrub_locatable(int k, int e, const unsigned char *coef);
 #define RSGPU_SCRUB_TWO_PASS 2
 int rsgpu_set_scrub_kernel(rsgpu_ctx *ctx, int kernel);
 
+/* ---- degraded scrub: a block with known-lost rows ------------------------ */
+
+/* A block may have rows that are KNOWN to be lost (a failed device), and one
+ * of its surviving rows may be silently bad as well.  The decodes trust every
+ * survivor, and the scrub above needs all k + e rows: run after a rebuild it
+ * sees the error only in the parity rows the decoder did not use and names a
+ * healthy parity row.  This call answers, BEFORE anything is rebuilt, whether
+ * the survivors are consistent, and with >= 2 spare parity rows which one
+ * surviving row is not; the caller adds that row to the erasure list and
+ * decodes with the calls above.  Nothing is decoded and no row is written.
+ *
+ * Per byte column of a block with lost set L (n rows, n <= e):
+ *   consistent  some choice of bytes for the rows in L makes all e syndromes
+ *               (the scrub's s_p above) zero; BAD otherwise
+ *   explains    a surviving row r explains a bad column when XORing some
+ *               x != 0 into row r's byte makes the column consistent
+ * Both are properties of the surviving bytes alone: the bytes stored in the
+ * lost rows influence no field of any report.  The call may nevertheless READ
+ * the lost source rows (they are part of the layout; its first pass is the
+ * ordinary encode of all k rows); lost parity rows are never read.
+ *
+ *   d_lost  DEVICE [blocks][u] bytes, 1 <= u <= 8: block b's list of lost
+ *           row indices in [0, k + e), strictly ascending (k + p is parity
+ *           row p), then RSGPU_LOST_NONE to the end; n, the number of listed
+ *           rows, may differ from block to block
+ *   flags   0 or RSGPU_SCRUB_LOCATE
+ *
+ * The report (rsgpu_scrub_report, overwritten by every call): bad_columns is
+ * the number of bad columns, row is -1 except for ONE_ROW, and the status is
+ * the first that applies of
+ *   BAD_LIST    not strictly ascending, an index >= k + e, a row after a
+ *               NONE, or n > e; bad_columns 0; the compare reads nothing of
+ *               the block beyond the list (the encode pass reads its source
+ *               rows with the rest of the batch; they influence nothing)
+ *   UNCHECKED   n == e: no spare row, nothing can be checked
+ *   BAD_MATRIX  with D the lost data rows, no |D| surviving parity rows p
+ *               have c[p][D] invertible: the survivors do not determine D
+ *   CLEAN       no bad column
+ *   ONE_ROW     (RSGPU_SCRUB_LOCATE only) every bad column is explained by
+ *               EXACTLY one surviving row, the same in all of them: `row`
+ *   DAMAGED     anything else, a column that no row or more than one row
+ *               explains included.  With a spare of e - n == 1 no column is
+ *               explained by exactly one row: such a block is CLEAN or DAMAGED
+ * No matrix is refused as "not locatable": ambiguity is decided per column.
+ * With every list all-NONE the reports equal rsgpu_scrub_blocks' byte for
+ * byte for the gf_gen_rs_matrix and gf_gen_cauchy1_matrix codes (at most one
+ * row explains a column there).  As the scrub's, ONE_ROW names the most
+ * likely explanation, not a proof: e - n - 1 or more damaged survivors in one
+ * column can look like another single row.
+ *
+ * Layout, `coef` and accepted geometries as rsgpu_scrub_blocks (any len, any
+ * pitch >= len, any alignment, custom e x k matrix or NULL); d_report
+ * [blocks] is DEVICE memory, 8-byte aligned.  Enqueued on the context's
+ * stream, no synchronisation; more than 65535 blocks run as consecutive
+ * slices.  e == 0 or len == 0: every block with a well-formed list is CLEAN,
+ * a malformed list is still BAD_LIST.  Null pointers, a misaligned report, u
+ * outside [1, 8] or unknown flag bits: RSGPU_ERR_ARG, nothing is enqueued and
+ * the report is untouched.
+ *
+ * Cost: the encode of the k source rows into context-owned scratch (slices
+ * of at most 128 MiB of parity, as the TWO_PASS scrub), then
+ * k_degraded_compare, which reads the stored and the recomputed row of every
+ * surviving parity row once: 2 (e - |P|) rows per block, P the lost parity
+ * rows.  Measured at (64, 32), 1 MB rows, 1024 blocks on one MI355X
+ * (profiles/degraded): one lost row per block 36.4 ms, what
+ * the TWO_PASS scrub of complete blocks takes (36.2 ms; FUSED 22.3 ms, the
+ * encode alone 22.0 ms); 4 lost rows 38.8 ms, 8 lost rows 41.5 ms.  The
+ * compare is memory-bound for up to 2 lost data rows per block and bound by
+ * its arithmetic at 8 (0.79 of the device-to-device copy rate).  Not built: a
+ * form fused into the compiled encode, and host-resident blocks. */
+#define RSGPU_LOST_NONE 255         /* list padding */
+#define RSGPU_SCRUB_UNCHECKED 3     /* n == e: no spare row, nothing can be checked */
+#define RSGPU_SCRUB_BAD_MATRIX (-1) /* the lost data rows are not determined by the surviving parity */
+#define RSGPU_SCRUB_BAD_LIST (-2)   /* malformed list */
+int rsgpu_scrub_degraded_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch,
+                                size_t blocks, const unsigned char *d_src,
+                                const unsigned char *d_parity, const unsigned char *coef,
+                                int u, const unsigned char *d_lost, int flags,
+                                rsgpu_scrub_report *d_report);
+
 /* ---- repair in place of what the scrub locates ---------------------------- */
 
 /* "Bad", "explains" and "locatable" as for the scrub above.  A bad column is

@@ -1,0 +1,601 @@
+// rs_degraded.hip -- degraded scrub (rsgpu_scrub_degraded_blocks) for gfx950:
+// are the SURVIVING rows of a block consistent, when up to e of its k + e rows
+// are known to be lost?  Nothing is rebuilt and no row is written.
+//
+// With D the lost data rows, P the lost parity rows and s_p the raw syndromes
+// (stored ^ recomputed parity, the recomputed one over all k source rows as
+// they lie in memory), a byte column is consistent when some choice of the
+// lost bytes zeroes every syndrome.  The lost parity rows can always be
+// chosen, so only the surviving parity rows S count, and the lost data bytes
+// enter them through c[S][D]: the column is consistent when s_S lies in the
+// column space of c[S][D].  k_degraded_prepare picks |D| pivot rows Q of S
+// with c[Q][D] invertible and writes R = c[rest][D] (c[Q][D])^-1 for the
+// other rows of S; the reduced syndromes
+//   t_p = s_p ^ XOR_i R[p][i] * s_Q[i],   p in rest,
+// are then zero exactly for a consistent column, and the bytes stored in the
+// lost rows cancel out of them.  A surviving row r explains a bad column when
+// t is a non-zero multiple of r's own reduced column h_r (prepare writes
+// those too): c[rest][r] ^ R c[Q][r] for a data row, column i of R for the
+// pivot parity row Q[i], a unit vector for a rest parity row.
+//
+// k_degraded_compare is the hot kernel, built like k_update_blocks: a
+// workgroup owns one block and a strided set of columns, stages the v_perm
+// tables of its block's R in LDS, and a lane owns a 16-byte column (a byte in
+// the byte kernel): it loads the |Q| <= 8 pivot syndromes once, keeps them as
+// the selector dwords of the 3-3-2 split, and walks the rest rows once.  Rows
+// in P are never loaded: 2 (e - |P|) rows per block, each read once.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/rsgpu.h"
+#include "gf256.h"
+#include "rs_kernels.h"
+
+namespace rsgpu {
+
+namespace {
+
+__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
+{
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+}
+
+__device__ __forceinline__ uint32_t vperm(uint32_t hi, uint32_t lo, uint32_t sel)
+{
+    return __builtin_amdgcn_perm(hi, lo, sel);
+}
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) const u32x4 g_cu32x4;
+typedef __attribute__((address_space(1))) const uint8_t g_cu8;
+
+// A lane's column of one row: W dwords (4: 16 bytes of 16-byte aligned rows,
+// 1: one byte in the low bits).
+template <int W>
+struct Col {
+    uint32_t d[W];
+};
+
+template <int W>
+__device__ __forceinline__ Col<W> col_load(const uint8_t* row, long long c)
+{
+    Col<W> r;
+    if constexpr (W == 4) {
+        const u32x4 v = ((g_cu32x4*)row)[c];
+        r.d[0] = v.x; r.d[1] = v.y; r.d[2] = v.z; r.d[3] = v.w;
+    } else {
+        r.d[0] = ((g_cu8*)row)[c];
+    }
+    return r;
+}
+
+constexpr int kDegThreads = 256;
+constexpr int kRestAhead = 4;  // rest rows (stored and computed) loaded together
+
+// a^-1 = a^254
+__device__ uint8_t deg_inv(uint8_t a)
+{
+    uint8_t r = 1, s = a;
+    for (int bit = 1; bit < 8; ++bit) {  // 254 = 0b11111110
+        s = gf_mul_slow(s, s);
+        r = gf_mul_slow(r, s);
+    }
+    return r;
+}
+
+// ---------------------------------------------------------------------------
+// k_degraded_prepare: one wave per block.  Lane 0 validates the list, splits
+// it, chooses the pivot rows greedily (ascending surviving parity rows, each
+// kept when it raises the rank of c[Q][D]) and inverts c[Q][D]; the wave then
+// writes R and, with locate, the reduced column of every row.  A block that
+// never reaches the compare gets its final report here; the others get a
+// zeroed fold.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_degraded_prepare(DegradedArgs a)
+{
+    __shared__ uint8_t lost[256];    // per row of [0, k + e): 1 when listed
+    __shared__ uint8_t dl[8], ql[8]; // D (data rows), Q (parity indices)
+    __shared__ uint8_t restl[256];   // rest parity indices, ascending
+    __shared__ uint8_t basis[8][8];  // echelon form of the rows kept so far
+    __shared__ uint8_t bpiv[8];      // pivot column of each basis row
+    __shared__ uint8_t am[8][8], inv[8][8];
+    __shared__ uint8_t rl[256 * 8];  // R [nrest][8]
+    __shared__ int sh_state, sh_nd, sh_nrest;
+
+    const long long b = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int k = a.k, e = a.e, m = a.k + a.e;
+    uint8_t* tab = a.tab + (size_t)b * a.tab_stride;
+    DegradedHdr* hdr = reinterpret_cast<DegradedHdr*>(tab);
+    const uint8_t* list = a.lost + b * a.u;
+
+    for (int r = lane; r < 256; r += 64)
+        lost[r] = 0;
+    __syncthreads();
+
+    if (lane == 0) {
+        int n = 0, prev = -1, nd = 0;
+        bool ok = true, none = false;
+        for (int i = 0; i < a.u; ++i) {
+            const int j = list[i];
+            if (j == RSGPU_LOST_NONE) {
+                none = true;
+            } else {
+                ok = ok && !none && j < m && j > prev;
+                prev = j;
+                ++n;
+            }
+        }
+        ok = ok && n <= e;
+        int state = kDegRun;
+        if (!ok) {
+            state = RSGPU_SCRUB_BAD_LIST;
+        } else if (!a.work) {
+            state = kDegClean;
+        } else if (n == e) {
+            state = RSGPU_SCRUB_UNCHECKED;
+        } else {
+            for (int i = 0; i < n; ++i) {
+                const int j = list[i];
+                lost[j] = 1;
+                if (j < k)
+                    dl[nd++] = (uint8_t)j;
+            }
+            // greedy pivots: reduce each surviving parity row's c[p][D] by the
+            // basis; what is left non-zero raises the rank
+            int nq = 0;
+            for (int p = 0; p < e && nq < nd; ++p) {
+                if (lost[k + p])
+                    continue;
+                uint8_t v[8];
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    v[i] = i < nd ? a.coef[(size_t)p * k + dl[i < nd ? i : 0]] : 0;
+                for (int q = 0; q < nq; ++q) {
+                    uint8_t f = 0;
+#pragma unroll
+                    for (int i = 0; i < 8; ++i)
+                        f = i == bpiv[q] ? v[i] : f;
+                    if (f) {
+#pragma unroll
+                        for (int i = 0; i < 8; ++i)
+                            v[i] ^= gf_mul_slow(f, basis[q][i]);
+                    }
+                }
+                int piv = -1;
+#pragma unroll
+                for (int i = 7; i >= 0; --i)
+                    piv = v[i] ? i : piv;
+                if (piv < 0)
+                    continue;
+                uint8_t lead = 0;
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    lead = i == piv ? v[i] : lead;
+                const uint8_t li = deg_inv(lead);
+#pragma unroll
+                for (int i = 0; i < 8; ++i)
+                    basis[nq][i] = gf_mul_slow(li, v[i]);
+                bpiv[nq] = (uint8_t)piv;
+                ql[nq++] = (uint8_t)p;
+            }
+            if (nq < nd) {
+                state = RSGPU_SCRUB_BAD_MATRIX;
+            } else {
+                // (c[Q][D])^-1 by Gauss-Jordan; the matrix has full rank
+                for (int i = 0; i < nd; ++i)
+                    for (int j = 0; j < nd; ++j) {
+                        am[i][j] = a.coef[(size_t)ql[i] * k + dl[j]];
+                        inv[i][j] = i == j;
+                    }
+                for (int col = 0; col < nd; ++col) {
+                    int pr = col;
+                    while (pr < nd && am[pr][col] == 0)
+                        ++pr;
+                    if (pr >= nd)
+                        break;  // cannot happen for a full-rank matrix
+                    if (pr != col)
+                        for (int j = 0; j < nd; ++j) {
+                            const uint8_t x = am[pr][j], y = inv[pr][j];
+                            am[pr][j] = am[col][j];
+                            inv[pr][j] = inv[col][j];
+                            am[col][j] = x;
+                            inv[col][j] = y;
+                        }
+                    const uint8_t li = deg_inv(am[col][col]);
+                    for (int j = 0; j < nd; ++j) {
+                        am[col][j] = gf_mul_slow(li, am[col][j]);
+                        inv[col][j] = gf_mul_slow(li, inv[col][j]);
+                    }
+                    for (int r = 0; r < nd; ++r) {
+                        const uint8_t f = am[r][col];
+                        if (r == col || f == 0)
+                            continue;
+                        for (int j = 0; j < nd; ++j) {
+                            am[r][j] ^= gf_mul_slow(f, am[col][j]);
+                            inv[r][j] ^= gf_mul_slow(f, inv[col][j]);
+                        }
+                    }
+                }
+                // the rest: surviving parity rows that are no pivot
+                int nrest = 0, qi = 0;
+                for (int p = 0; p < e; ++p) {
+                    if (lost[k + p])
+                        continue;
+                    if (qi < nq && ql[qi] == p) {
+                        ++qi;
+                        continue;
+                    }
+                    restl[nrest++] = (uint8_t)p;
+                }
+                sh_nrest = nrest;
+            }
+        }
+        sh_state = state;
+        sh_nd = nd;
+        // the report: final for a block that stops here, a zeroed fold otherwise
+        rsgpu_scrub_report r;
+        r.bad_columns = 0;
+        r.status = state == kDegRun || state == kDegClean ? RSGPU_SCRUB_CLEAN : state;
+        r.row = state == kDegRun ? 0 : -1;
+        a.report[b] = r;
+        hdr->state = state;
+    }
+    __syncthreads();
+    if (sh_state != kDegRun)
+        return;
+    const int nd = sh_nd, nrest = sh_nrest;
+    if (lane == 0) {
+        hdr->nq = (uint8_t)nd;
+        hdr->nrest = (uint8_t)nrest;
+    }
+    if (lane < 8)
+        hdr->q[lane] = lane < nd ? ql[lane] : 0;
+    uint8_t* t_rest = tab + sizeof(DegradedHdr);
+    uint8_t* t_r = t_rest + a.rest_bytes;
+    uint8_t* t_h = t_r + (size_t)e * 8;
+    for (int pi = lane; pi < nrest; pi += 64)
+        t_rest[pi] = restl[pi];
+    // R[pi][i] = XOR_j c[rest_pi][D_j] * inv[j][i]
+    for (int idx = lane; idx < nrest * 8; idx += 64) {
+        const int pi = idx >> 3, i = idx & 7;
+        uint8_t x = 0;
+        if (i < nd)
+            for (int j = 0; j < nd; ++j)
+                x ^= gf_mul_slow(a.coef[(size_t)restl[pi] * k + dl[j]], inv[j][i]);
+        rl[idx] = x;
+        t_r[idx] = x;
+    }
+    if (!a.locate)
+        return;
+    __syncthreads();
+    // the reduced column of every row, [k + e][e] with nrest entries used
+    for (int idx = lane; idx < m * nrest; idx += 64) {
+        const int r = idx / nrest, pi = idx - r * nrest;
+        uint8_t h = 0;
+        if (!lost[r]) {
+            if (r < k) {
+                h = a.coef[(size_t)restl[pi] * k + r];
+                for (int i = 0; i < nd; ++i)
+                    h ^= gf_mul_slow(rl[pi * 8 + i], a.coef[(size_t)ql[i] * k + r]);
+            } else {
+                const int p = r - k;
+                if (restl[pi] == p)
+                    h = 1;
+                for (int i = 0; i < nd; ++i)
+                    if (ql[i] == p)
+                        h = rl[pi * 8 + i];
+            }
+        }
+        t_h[(size_t)r * e + pi] = h;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// The cold path: which surviving rows explain byte column ci of a block?
+// Returns the row when exactly one does, else -1.  t is recomputed from
+// memory, entry by entry; a candidate row r must have t = x h_r for one
+// x != 0, tested without a division as t_p h_r[p*] == t_p* h_r[p] for every p,
+// p* the first non-zero entry of t.  One other entry of t screens the rows
+// before the full walk.
+// ---------------------------------------------------------------------------
+struct DegBlock {
+    const uint8_t* calc;  // the block's recomputed parity rows
+    const uint8_t* par;   // the block's stored parity rows
+    const uint8_t* rest;  // [nrest]
+    const uint8_t* r;     // [nrest][8]
+    const uint8_t* h;     // [k + e][e]
+    long long pitch;
+    int nq, nrest, rows, e;
+    uint8_t q[8];
+};
+
+__device__ __forceinline__ uint8_t deg_t(const DegBlock& d, unsigned long long sq, int pi, long long ci)
+{
+    const size_t off = (size_t)d.rest[pi] * d.pitch + ci;
+    uint8_t t = d.calc[off] ^ d.par[off];
+    for (int i = 0; i < d.nq; ++i)
+        t ^= gf_mul_slow(d.r[pi * 8 + i], (uint8_t)(sq >> (8 * i)));
+    return t;
+}
+
+__device__ __noinline__ int deg_locate(const uint8_t* tab, const uint8_t* calcb, const uint8_t* parb,
+                                       long long pitch, int k, int e, int rest_bytes, long long ci)
+{
+    const DegradedHdr* hdr = reinterpret_cast<const DegradedHdr*>(tab);
+    DegBlock d;
+    d.calc = calcb;
+    d.par = parb;
+    d.rest = tab + sizeof(DegradedHdr);
+    d.r = d.rest + rest_bytes;
+    d.h = d.r + (size_t)e * 8;
+    d.pitch = pitch;
+    d.nq = hdr->nq;
+    d.nrest = hdr->nrest;
+    d.rows = k + e;
+    d.e = e;
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        d.q[i] = hdr->q[i];
+    unsigned long long sq = 0;
+    for (int i = 0; i < d.nq; ++i) {
+        const size_t off = (size_t)d.q[i] * d.pitch + ci;
+        sq |= (unsigned long long)(uint8_t)(d.calc[off] ^ d.par[off]) << (8 * i);
+    }
+    int ps = -1;
+    uint8_t ts = 0, t0 = 0, t2 = 0;
+    for (int pi = 0; pi < d.nrest; ++pi) {
+        const uint8_t t = deg_t(d, sq, pi, ci);
+        if (pi == 0)
+            t0 = t;
+        if (ps < 0 && t) {
+            ps = pi;
+            ts = t;
+        } else if (ps >= 0 && pi == ps + 1) {
+            t2 = t;
+        }
+    }
+    if (ps < 0)
+        return -1;  // not a bad column
+    // the screen: entry 0 (zero) when p* > 0, else entry 1 when there is one
+    const int p2 = ps > 0 ? 0 : d.nrest > 1 ? 1 : -1;
+    if (ps > 0)
+        t2 = t0;
+    int found = 0, row = -1;
+    for (int r = 0; r < d.rows && found < 2; ++r) {
+        const uint8_t* h = d.h + (size_t)r * d.e;
+        const uint8_t hs = h[ps];
+        if (!hs)
+            continue;
+        if (p2 >= 0 && gf_mul_slow(t2, hs) != gf_mul_slow(ts, h[p2]))
+            continue;
+        bool ok = true;
+        for (int pi = 0; pi < d.nrest && ok; ++pi)
+            ok = gf_mul_slow(deg_t(d, sq, pi, ci), hs) == gf_mul_slow(ts, h[pi]);
+        if (ok) {
+            ++found;
+            row = r;
+        }
+    }
+    return found == 1 ? row : -1;
+}
+
+// one atomic per wave and field, none for a wave without a bad column
+__device__ __forceinline__ void deg_fold_wave(DegradedFold* f, unsigned long long bad, unsigned hi1, unsigned lo1)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        bad += __shfl_down(bad, off, 64);
+        hi1 = max(hi1, (unsigned)__shfl_down((int)hi1, off, 64));
+        lo1 = max(lo1, (unsigned)__shfl_down((int)lo1, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0 && bad) {
+        atomicAdd(&f->bad, bad);
+        if (hi1) {
+            atomicMax(&f->hi1, hi1);
+            atomicMax(&f->lo1, lo1);
+        }
+    }
+}
+
+// G: pivot syndromes a lane holds; W: dwords per lane and row.  Columns
+// [col0, col1) in units of 16 bytes (W = 4) or bytes (W = 1).
+template <int G, int W>
+__global__ __launch_bounds__(kDegThreads) void k_degraded_compare(DegradedArgs a, long long col0, long long col1)
+{
+    extern __shared__ uint4 lt4[];  // [e][G] tables of bits 0-5, [e][G] dwords of bits 6-7, [e] rest rows
+    uint32_t* ltc = reinterpret_cast<uint32_t*>(lt4 + (size_t)a.e * G);
+    uint32_t* lrest = ltc + (size_t)a.e * G;
+    const long long b = blockIdx.y;
+    const uint8_t* tab = a.tab + (size_t)b * a.tab_stride;
+    const DegradedHdr* hdr = reinterpret_cast<const DegradedHdr*>(tab);
+    if (hdr->state != kDegRun)
+        return;  // the whole workgroup: the prepare has reported this block
+    const int nq = hdr->nq < G ? hdr->nq : G, nrest = hdr->nrest;
+    const uint8_t* t_rest = tab + sizeof(DegradedHdr);
+    const uint8_t* t_r = t_rest + a.rest_bytes;
+
+    for (int idx = threadIdx.x; idx < nrest * G; idx += kDegThreads) {
+        const int pi = idx / G, i = idx - pi * G;
+        if (i < nq) {
+            const uint8_t c = t_r[pi * 8 + i];
+            lt4[idx] = a.tab4[c];
+            ltc[idx] = a.tabc[c];
+        }
+    }
+    for (int pi = threadIdx.x; pi < nrest; pi += kDegThreads)
+        lrest[pi] = t_rest[pi];
+    __syncthreads();
+
+    const uint8_t* calcb = a.calc + b * a.e * a.pitch;
+    const uint8_t* parb = a.par + b * a.e * a.pitch;
+    const long long stride = (long long)gridDim.x * kDegThreads;
+    unsigned long long bad = 0;
+    unsigned hi1 = 0, lo1 = 0;
+
+    for (long long col = col0 + (long long)blockIdx.x * kDegThreads + threadIdx.x; col < col1; col += stride) {
+        // the pivot syndromes of this column as v_perm selectors
+        uint32_t s0[G][W], s1[G][W], s2[G][W];
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            if (i < nq) {
+                const long long off = (long long)hdr->q[i] * a.pitch;
+                const Col<W> x = col_load<W>(parb + off, col);
+                const Col<W> y = col_load<W>(calcb + off, col);
+#pragma unroll
+                for (int w = 0; w < W; ++w) {
+                    const uint32_t s = x.d[w] ^ y.d[w];
+                    s0[i][w] = s & 0x07070707u;
+                    s1[i][w] = (s >> 3) & 0x07070707u;
+                    s2[i][w] = (s >> 6) & 0x03030303u;
+                }
+            }
+        }
+        // one walk over the rest rows, 2 kRestAhead loads in flight
+        uint32_t any[W];
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+            any[w] = 0;
+        for (int p0 = 0; p0 < nrest; p0 += kRestAhead) {
+            Col<W> x[kRestAhead], y[kRestAhead];
+#pragma unroll
+            for (int q = 0; q < kRestAhead; ++q)
+                if (p0 + q < nrest) {
+                    const long long off = (long long)lrest[p0 + q] * a.pitch;
+                    x[q] = col_load<W>(parb + off, col);
+                    y[q] = col_load<W>(calcb + off, col);
+                }
+#pragma unroll
+            for (int q = 0; q < kRestAhead; ++q) {
+                if (p0 + q < nrest) {
+                    const uint4* t4 = lt4 + (size_t)(p0 + q) * G;
+                    const uint32_t* tc = ltc + (size_t)(p0 + q) * G;
+                    uint32_t t[W];
+#pragma unroll
+                    for (int w = 0; w < W; ++w)
+                        t[w] = x[q].d[w] ^ y[q].d[w];
+#pragma unroll
+                    for (int i = 0; i < G; ++i) {
+                        if (i < nq) {
+                            const uint4 tt = t4[i];
+                            const uint32_t c = tc[i];
+#pragma unroll
+                            for (int w = 0; w < W; ++w)
+                                t[w] ^= xor3(vperm(tt.y, tt.x, s0[i][w]), vperm(tt.w, tt.z, s1[i][w]),
+                                             vperm(c, c, s2[i][w]));
+                        }
+                    }
+#pragma unroll
+                    for (int w = 0; w < W; ++w)
+                        any[w] |= t[w];
+                }
+            }
+        }
+        uint32_t all = 0;
+#pragma unroll
+        for (int w = 0; w < W; ++w)
+            all |= any[w];
+        if (all == 0)
+            continue;
+        // the bad byte columns of this lane's column
+#pragma unroll
+        for (int w = 0; w < W; ++w) {
+            for (int j = 0; j < (W == 4 ? 4 : 1); ++j) {
+                if (((any[w] >> (8 * j)) & 0xFFu) == 0)
+                    continue;
+                ++bad;
+                if (!a.locate)
+                    continue;
+                const long long ci = W == 4 ? col * 16 + w * 4 + j : col;
+                const int row = deg_locate(tab, calcb, parb, a.pitch, a.k, a.e, (int)a.rest_bytes, ci);
+                hi1 = max(hi1, row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
+                lo1 = max(lo1, row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
+            }
+        }
+    }
+    deg_fold_wave(reinterpret_cast<DegradedFold*>(a.report) + b, bad, hi1, lo1);
+}
+
+// the fold of every block the compare ran on into its report; the prepare's
+// reports stay as they are
+__global__ __launch_bounds__(256) void k_degraded_finalise(DegradedArgs a)
+{
+    const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= a.blocks)
+        return;
+    const DegradedHdr* hdr = reinterpret_cast<const DegradedHdr*>(a.tab + (size_t)b * a.tab_stride);
+    if (hdr->state != kDegRun)
+        return;
+    const DegradedFold f = reinterpret_cast<const DegradedFold*>(a.report)[b];
+    rsgpu_scrub_report r;
+    r.bad_columns = f.bad;
+    const bool one = a.locate && f.hi1 >= 1 && f.hi1 < kScrubNoRow && f.hi1 - 1 == kScrubBias - f.lo1;
+    r.status = f.bad == 0 ? RSGPU_SCRUB_CLEAN : one ? RSGPU_SCRUB_ONE_ROW : RSGPU_SCRUB_DAMAGED;
+    r.row = (f.bad != 0 && one) ? (int)f.hi1 - 1 : -1;
+    a.report[b] = r;
+}
+
+template <int W>
+hipError_t launch_w(const DegradedArgs& a, long long col0, long long col1, hipStream_t st)
+{
+    // workgroups per block as the update's: enough columns each to amortise
+    // the staging, enough in all to fill the device when the batch is small
+    const long long ncols = col1 - col0;
+    long long gx = (ncols + kDegThreads - 1) / kDegThreads;
+    const long long want = a.blocks >= 1024 ? 8 : (8192 + a.blocks - 1) / a.blocks;
+    if (gx > want)
+        gx = want;
+    const dim3 grid((unsigned)gx, (unsigned)a.blocks), block(kDegThreads);
+    const int most = a.u < a.e ? a.u : a.e;  // pivot rows of any block: |D| <= n <= min(u, e)
+    const int g = most > 4 ? 8 : most > 2 ? 4 : most > 1 ? 2 : 1;
+    const size_t lds = (size_t)a.e * g * (sizeof(uint4) + sizeof(uint32_t)) + (size_t)a.e * sizeof(uint32_t);
+    switch (g) {
+    case 1: hipLaunchKernelGGL((k_degraded_compare<1, W>), grid, block, lds, st, a, col0, col1); break;
+    case 2: hipLaunchKernelGGL((k_degraded_compare<2, W>), grid, block, lds, st, a, col0, col1); break;
+    case 4: hipLaunchKernelGGL((k_degraded_compare<4, W>), grid, block, lds, st, a, col0, col1); break;
+    default: hipLaunchKernelGGL((k_degraded_compare<8, W>), grid, block, lds, st, a, col0, col1); break;
+    }
+    return hipGetLastError();
+}
+
+bool args_ok(const DegradedArgs& a)
+{
+    return a.blocks > 0 && a.blocks <= 65535 && a.k > 0 && a.e >= 0 && a.k + a.e <= RSGPU_MAX_SOURCES &&
+           a.u >= 1 && a.u <= 8 && a.lost && a.tab && a.report && a.tab_stride >= degraded_tab_stride(a.k, a.e);
+}
+
+}  // namespace
+
+size_t degraded_rest_bytes(int e) { return ((size_t)e + 15) / 16 * 16; }
+
+size_t degraded_tab_stride(int k, int e)
+{
+    const size_t n = sizeof(DegradedHdr) + degraded_rest_bytes(e) + (size_t)e * 8 + (size_t)(k + e) * e;
+    return (n + 15) / 16 * 16;
+}
+
+hipError_t launch_degraded_prepare(const DegradedArgs& a, hipStream_t st)
+{
+    if (!args_ok(a) || (a.work && !a.coef))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_degraded_prepare, dim3((unsigned)a.blocks), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_degraded_compare(const DegradedArgs& a, bool bytes, long long col0, long long col1,
+                                   hipStream_t st)
+{
+    if (!args_ok(a) || !a.work || !a.calc || !a.par || !a.tab4 || !a.tabc || col0 < 0 || col1 <= col0 ||
+        col1 * (bytes ? 1 : 16) > a.len)
+        return hipErrorInvalidValue;
+    return bytes ? launch_w<1>(a, col0, col1, st) : launch_w<4>(a, col0, col1, st);
+}
+
+hipError_t launch_degraded_finalise(const DegradedArgs& a, hipStream_t st)
+{
+    if (!args_ok(a))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_degraded_finalise, dim3((unsigned)((a.blocks + 255) / 256)), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace rsgpu

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+struct rsgpu_scrub_report;  // include/rsgpu.h
+
 namespace rsgpu {
 
 struct DotArgs {
@@ -338,5 +340,52 @@ int update_group_rows();
 // rows; bytes == true: byte columns, any alignment.  An empty range only
 // validates the lists and writes the statuses.
 hipError_t launch_update_blocks(const UpdateArgs& a, bool bytes, long long col0, long long col1, hipStream_t st);
+
+// Degraded scrub (rsgpu_scrub_degraded_blocks, rs_degraded.hip): blocks with
+// known-lost rows.  k_degraded_prepare writes one table per block,
+//   [DegradedHdr | rest: degraded_rest_bytes(e) | R: e x 8 | H: (k + e) x e]
+// at degraded_tab_stride(k, e): the pivot parity rows Q (one per lost data
+// row), the other surviving parity rows `rest`, R[pi][i] = the factor of pivot
+// syndrome i in the reduced syndrome of rest row pi, and (locate only) H[r] =
+// the reduced column of row r, zero for a lost row.  state != kDegRun: the
+// prepare has written the block's final report and the compare and the
+// finalise leave it alone.  The compare folds into the report's own 16 bytes
+// as the scrub does (DegradedFold is ScrubFold's layout, kScrubBias and
+// kScrubNoRow its constants).
+constexpr int kDegRun = 0;      // the compare runs; the report holds a zeroed fold
+constexpr int kDegClean = 100;  // e == 0 or len == 0 with a well-formed list: CLEAN
+// any other state is the block's status: UNCHECKED, BAD_MATRIX or BAD_LIST
+struct DegradedHdr {
+    int state;
+    uint8_t nq, nrest, pad[2];
+    uint8_t q[8];  // parity indices p < e of the pivot rows, ascending
+};
+struct DegradedFold {
+    unsigned long long bad;
+    unsigned hi1, lo1;
+};
+struct DegradedArgs {
+    int k, e, u;
+    int locate;
+    int work;  // 0: e == 0 or len == 0, only the lists are judged
+    long long pitch, len, blocks;
+    const uint8_t* lost;   // [B][u]
+    const uint8_t* coef;   // device e x k matrix
+    const uint8_t* calc;   // [B][e] rows: the parity of the sources as stored, recomputed
+    const uint8_t* par;    // [B][e] rows: the stored parity
+    uint8_t* tab;          // [B] tables at tab_stride
+    size_t tab_stride, rest_bytes;
+    const uint4* tab4;     // device [256]: perm_tables words 0-3 of every coefficient value
+    const uint32_t* tabc;  // device [256]: perm_tables word 4
+    ::rsgpu_scrub_report* report;  // [B]
+};
+size_t degraded_rest_bytes(int e);
+size_t degraded_tab_stride(int k, int e);
+hipError_t launch_degraded_prepare(const DegradedArgs& a, hipStream_t st);
+// bytes == false: columns [col0, col1) are 16-byte units of 16-byte aligned
+// rows; bytes == true: byte columns, any alignment
+hipError_t launch_degraded_compare(const DegradedArgs& a, bool bytes, long long col0, long long col1,
+                                   hipStream_t st);
+hipError_t launch_degraded_finalise(const DegradedArgs& a, hipStream_t st);
 
 }  // namespace rsgpu

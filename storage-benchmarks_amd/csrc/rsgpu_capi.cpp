@@ -613,6 +613,8 @@ int rsgpu_destroy(rsgpu_ctx* ctx)
         (void)hipFree(ctx->d_scrub);
     if (ctx->d_update)
         (void)hipFree(ctx->d_update);
+    if (ctx->d_degraded)
+        (void)hipFree(ctx->d_degraded);
     if (ctx->h_stage)
         (void)hipHostFree(ctx->h_stage);
     if (ctx->stage_done)
@@ -2167,6 +2169,119 @@ int rsgpu_update_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
             KTimer kt(ctx, n16 > 0 ? "k_update_blocks(tail)" : "k_update_blocks(bytes)", nb);
             RS_HIP(ctx, launch_update_blocks(a, true, first, first < end ? end : first, ctx->stream));
         }
+    }
+    return RSGPU_OK;
+}
+
+// ---- degraded scrub ------------------------------------------------------------
+
+// The per-block tables of one slice (rs_kernels.h DegradedArgs) are bounded as
+// the computed parity is: a slice holds no more blocks than fit kDegTabBytes.
+constexpr size_t kDegTabBytes = 64u << 20;
+
+static int ensure_degraded(rsgpu_ctx* ctx, size_t bytes)
+{
+    if (ctx->degraded_bytes >= bytes)
+        return RSGPU_OK;
+    if (ctx->d_degraded) {
+        // every kernel that reads the old buffer is on the context's stream
+        RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        RS_HIP(ctx, hipFree(ctx->d_degraded));
+        ctx->d_degraded = nullptr;
+        ctx->degraded_bytes = 0;
+    }
+    RS_HIP(ctx, hipMalloc(&ctx->d_degraded, bytes));
+    ctx->degraded_bytes = bytes;
+    return RSGPU_OK;
+}
+
+int rsgpu_scrub_degraded_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                                const unsigned char* d_src, const unsigned char* d_parity,
+                                const unsigned char* coef, int u, const unsigned char* d_lost, int flags,
+                                rsgpu_scrub_report* d_report)
+{
+    int rc = check_geom(ctx, k, e, len, pitch, blocks);
+    if (rc)
+        return rc;
+    if (!d_report || (uintptr_t)d_report % 8 != 0 || (flags & ~RSGPU_SCRUB_LOCATE) != 0 || u < 1 || u > 8 ||
+        !d_lost)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_scrub_degraded_blocks: bad report pointer, flags, u or list");
+    const bool work = e > 0 && len > 0;
+    if (work && (!d_src || !d_parity))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_scrub_degraded_blocks: null rows");
+    // Two nested slicings.  A group of blocks shares one prepare and one
+    // finalise: its tables fit kDegTabBytes, its blocks fit a grid.  Inside it
+    // a slice is what the scrub scratch holds of computed parity (the TWO_PASS
+    // rule): encode, then compare.
+    const size_t per_block = (size_t)e * pitch, stride = degraded_tab_stride(k, e);
+    const size_t group = std::max<size_t>(1, std::min({blocks, kMaxGridBlocks, kDegTabBytes / stride}));
+    const size_t slice = work ? std::max<size_t>(1, std::min(group, kScrubParityBytes / per_block)) : group;
+    rc = ensure_degraded(ctx, group * stride);
+    if (rc)
+        return rc;
+    if (work) {
+        rc = ensure_scrub(ctx, kScrubTabBytes + slice * per_block);
+        if (rc)
+            return rc;
+        // the v_perm tables of every coefficient value and the matrix, on the device
+        rc = update_tables(ctx, k, e, coef);
+        if (rc)
+            return rc;
+    }
+    uint8_t* calc = work ? (uint8_t*)ctx->d_scrub + kScrubTabBytes : nullptr;
+    const bool vec = pitch % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
+    const long long n16 = work && vec ? (long long)(len / 16) : 0;
+    for (size_t g0 = 0; g0 < blocks; g0 += group) {
+        const size_t ng = std::min(group, blocks - g0);
+        DegradedArgs a{};
+        a.k = k;
+        a.e = e;
+        a.u = u;
+        a.locate = (flags & RSGPU_SCRUB_LOCATE) ? 1 : 0;
+        a.work = work ? 1 : 0;
+        a.pitch = (long long)pitch;
+        a.len = (long long)len;
+        a.blocks = (long long)ng;
+        a.lost = d_lost + g0 * (size_t)u;
+        a.tab = (uint8_t*)ctx->d_degraded;
+        a.tab_stride = stride;
+        a.rest_bytes = degraded_rest_bytes(e);
+        a.report = d_report + g0;
+        if (work) {
+            a.coef = (const uint8_t*)ctx->d_update + kUpdTabBytes;
+            a.tab4 = (const uint4*)ctx->d_update;
+            a.tabc = (const uint32_t*)((const char*)ctx->d_update + kUpdTab4Bytes);
+        }
+        {
+            KTimer kt(ctx, "k_degraded_prepare", ng);
+            RS_HIP(ctx, launch_degraded_prepare(a, ctx->stream));
+        }
+        if (!work)
+            continue;  // the prepare has written every report
+        for (size_t s0 = 0; s0 < ng; s0 += slice) {
+            const size_t b0 = g0 + s0, nb = std::min(slice, ng - s0);
+            // the parity of the k source rows as they lie in memory, lost ones
+            // included: their contribution cancels in the reduced syndromes
+            rc = rsgpu_encode_blocks(ctx, k, e, len, pitch, nb, d_src + b0 * (size_t)k * pitch, calc, coef);
+            if (rc)
+                return rc;
+            DegradedArgs c = a;
+            c.blocks = (long long)nb;
+            c.tab = a.tab + s0 * stride;
+            c.report = a.report + s0;
+            c.calc = calc;
+            c.par = d_parity + b0 * per_block;
+            if (n16 > 0) {
+                KTimer kt(ctx, "k_degraded_compare", nb);
+                RS_HIP(ctx, launch_degraded_compare(c, false, 0, n16, ctx->stream));
+            }
+            if ((size_t)n16 * 16 < len) {
+                KTimer kt(ctx, n16 > 0 ? "k_degraded_compare(tail)" : "k_degraded_compare(bytes)", nb);
+                RS_HIP(ctx, launch_degraded_compare(c, true, n16 * 16, (long long)len, ctx->stream));
+            }
+        }
+        KTimer kt(ctx, "k_degraded_finalise", ng);
+        RS_HIP(ctx, launch_degraded_finalise(a, ctx->stream));
     }
     return RSGPU_OK;
 }

@@ -85,6 +85,10 @@ struct rsgpu_ctx {
     // update_key = the (k, e, matrix) it holds
     void* d_update = nullptr;
     std::vector<uint8_t> update_key;
+    // degraded scrub (rsgpu_scrub_degraded_blocks): grow-only device buffer
+    // of the per-block tables k_degraded_prepare writes for one slice
+    void* d_degraded = nullptr;
+    size_t degraded_bytes = 0;
     // pinned host staging for small uploads, guarded by an event
     void* h_stage = nullptr;
     size_t stage_bytes = 0;

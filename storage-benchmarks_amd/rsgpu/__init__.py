@@ -38,7 +38,8 @@ __all__ = [
     "LIB_PATH", "scrub_locatable", "SCRUB_REPORT_DTYPE", "SCRUB_LOCATE", "SCRUB_CLEAN",
     "SCRUB_ONE_ROW", "SCRUB_DAMAGED", "REPAIR_REPORT_DTYPE", "REPAIR_MODES", "REPAIR_ONE_ROW",
     "REPAIR_COLUMNS", "REPAIR_CLEAN", "REPAIR_REPAIRED", "REPAIR_PARTIAL", "REPAIR_DAMAGED",
-    "UPDATE_NONE", "UPDATE_DELTA",
+    "UPDATE_NONE", "UPDATE_DELTA", "LOST_NONE", "SCRUB_UNCHECKED", "SCRUB_BAD_MATRIX",
+    "SCRUB_BAD_LIST",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -71,6 +72,10 @@ REPAIR_REPORT_DTYPE = np.dtype([("bad_columns", "<u8"), ("repaired_columns", "<u
 # rsgpu_update_blocks' list padding and flag (include/rsgpu.h)
 UPDATE_NONE = 255
 UPDATE_DELTA = 1
+# rsgpu_scrub_degraded_blocks' list padding and additional statuses
+# (include/rsgpu.h); the report is SCRUB_REPORT_DTYPE
+LOST_NONE = 255
+SCRUB_UNCHECKED, SCRUB_BAD_MATRIX, SCRUB_BAD_LIST = 3, -1, -2
 
 vp = C.c_void_p
 sz = C.c_size_t
@@ -119,6 +124,8 @@ _SIGS = {
     "rsgpu_verify_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, vp]),
     "rsgpu_scrub_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp]),
     "rsgpu_scrub_locatable": (C.c_int, [C.c_int, C.c_int, vp]),
+    "rsgpu_scrub_degraded_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp,
+                                              C.c_int, vp]),
     "rsgpu_repair_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp]),
     "rsgpu_set_scrub_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_update_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, C.c_int, vp, vp, vp, vp, vp,
@@ -440,6 +447,24 @@ class Context:
                                             _ptr(d_par), cptr, SCRUB_LOCATE if locate else 0,
                                             _ptr(d_report)), "rsgpu_scrub_blocks")
 
+    def scrub_degraded_blocks(self, k, e, length, pitch, blocks, d_src, d_par, u, d_lost, d_report,
+                              coef=None, locate: bool = True) -> None:
+        """Degraded scrub (include/rsgpu.h rsgpu_scrub_degraded_blocks): are
+        the surviving rows of blocks with known-lost rows consistent, and
+        which one is not?  d_lost is device memory of blocks x u bytes
+        (1 <= u <= 8): per block the lost row indices in [0, k + e),
+        ascending, padded with LOST_NONE.  d_report as scrub_blocks'; the
+        statuses add SCRUB_UNCHECKED, SCRUB_BAD_MATRIX and SCRUB_BAD_LIST.
+        Rows are only read.  Enqueued on the context's stream."""
+        cptr = None
+        if coef is not None:
+            coef = np.ascontiguousarray(coef, np.uint8)
+            cptr = coef.ctypes.data
+        self.check(lib().rsgpu_scrub_degraded_blocks(self._h, k, e, length, pitch, blocks, _ptr(d_src),
+                                                     _ptr(d_par), cptr, u, _ptr(d_lost),
+                                                     SCRUB_LOCATE if locate else 0, _ptr(d_report)),
+                   "rsgpu_scrub_degraded_blocks")
+
     def repair_blocks(self, k, e, length, pitch, blocks, d_src, d_par, d_report, coef=None,
                       mode: str = "one_row") -> None:
         """Repair in place (include/rsgpu.h rsgpu_repair_blocks): d_src and
@@ -540,6 +565,25 @@ class GpuEncoder:
                           device=self.src.device)
         self.ctx.scrub_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, rep,
                               locate=locate)
+        self.ctx.synchronize()
+        return rep.cpu().numpy().view(SCRUB_REPORT_DTYPE)[: self.B].copy()
+
+    def scrub_degraded(self, lost, locate: bool = True) -> np.ndarray:
+        """Scrubs this encoder's blocks with known-lost rows (include/rsgpu.h
+        rsgpu_scrub_degraded_blocks): lost is a (blocks, u) uint8 array,
+        1 <= u <= 8, of row indices in [0, k + e) per block, ascending and
+        padded with LOST_NONE.  The per-block reports as a structured array
+        (SCRUB_REPORT_DTYPE).  Synchronises (the reports are copied to the
+        host)."""
+        import torch
+        lost = np.ascontiguousarray(lost, np.uint8)
+        if lost.ndim != 2 or lost.shape[0] != self.B:
+            raise ValueError("lost must be a (blocks, u) array")
+        d_lost = torch.from_numpy(lost).to(self.src.device)
+        rep = torch.empty(max(1, self.B) * SCRUB_REPORT_DTYPE.itemsize, dtype=torch.uint8,
+                          device=self.src.device)
+        self.ctx.scrub_degraded_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,
+                                       lost.shape[1], d_lost, rep, locate=locate)
         self.ctx.synchronize()
         return rep.cpu().numpy().view(SCRUB_REPORT_DTYPE)[: self.B].copy()
 
