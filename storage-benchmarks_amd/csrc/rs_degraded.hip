@@ -30,44 +30,11 @@
 #include "../../include/rsgpu.h"
 #include "gf256.h"
 #include "rs_kernels.h"
+#include "rs_lane.h"
 
 namespace rsgpu {
 
 namespace {
-
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
-{
-    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
-
-__device__ __forceinline__ uint32_t vperm(uint32_t hi, uint32_t lo, uint32_t sel)
-{
-    return __builtin_amdgcn_perm(hi, lo, sel);
-}
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const u32x4 g_cu32x4;
-typedef __attribute__((address_space(1))) const uint8_t g_cu8;
-
-// A lane's column of one row: W dwords (4: 16 bytes of 16-byte aligned rows,
-// 1: one byte in the low bits).
-template <int W>
-struct Col {
-    uint32_t d[W];
-};
-
-template <int W>
-__device__ __forceinline__ Col<W> col_load(const uint8_t* row, long long c)
-{
-    Col<W> r;
-    if constexpr (W == 4) {
-        const u32x4 v = ((g_cu32x4*)row)[c];
-        r.d[0] = v.x; r.d[1] = v.y; r.d[2] = v.z; r.d[3] = v.w;
-    } else {
-        r.d[0] = ((g_cu8*)row)[c];
-    }
-    return r;
-}
 
 constexpr int kDegThreads = 256;
 constexpr int kRestAhead = 4;  // rest rows (stored and computed) loaded together
@@ -380,23 +347,6 @@ __device__ __noinline__ int deg_locate(const uint8_t* tab, const uint8_t* calcb,
     return found == 1 ? row : -1;
 }
 
-// one atomic per wave and field, none for a wave without a bad column
-__device__ __forceinline__ void deg_fold_wave(DegradedFold* f, unsigned long long bad, unsigned hi1, unsigned lo1)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        bad += __shfl_down(bad, off, 64);
-        hi1 = max(hi1, (unsigned)__shfl_down((int)hi1, off, 64));
-        lo1 = max(lo1, (unsigned)__shfl_down((int)lo1, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0 && bad) {
-        atomicAdd(&f->bad, bad);
-        if (hi1) {
-            atomicMax(&f->hi1, hi1);
-            atomicMax(&f->lo1, lo1);
-        }
-    }
-}
-
 // G: pivot syndromes a lane holds; W: dwords per lane and row.  Columns
 // [col0, col1) in units of 16 bytes (W = 4) or bytes (W = 1).
 template <int G, int W>
@@ -512,7 +462,7 @@ __global__ __launch_bounds__(kDegThreads) void k_degraded_compare(DegradedArgs a
             }
         }
     }
-    deg_fold_wave(reinterpret_cast<DegradedFold*>(a.report) + b, bad, hi1, lo1);
+    scrub_fold_wave(reinterpret_cast<ScrubFold*>(a.report) + b, bad, hi1, lo1);
 }
 
 // the fold of every block the compare ran on into its report; the prepare's
@@ -525,26 +475,13 @@ __global__ __launch_bounds__(256) void k_degraded_finalise(DegradedArgs a)
     const DegradedHdr* hdr = reinterpret_cast<const DegradedHdr*>(a.tab + (size_t)b * a.tab_stride);
     if (hdr->state != kDegRun)
         return;
-    const DegradedFold f = reinterpret_cast<const DegradedFold*>(a.report)[b];
-    rsgpu_scrub_report r;
-    r.bad_columns = f.bad;
-    const bool one = a.locate && f.hi1 >= 1 && f.hi1 < kScrubNoRow && f.hi1 - 1 == kScrubBias - f.lo1;
-    r.status = f.bad == 0 ? RSGPU_SCRUB_CLEAN : one ? RSGPU_SCRUB_ONE_ROW : RSGPU_SCRUB_DAMAGED;
-    r.row = (f.bad != 0 && one) ? (int)f.hi1 - 1 : -1;
-    a.report[b] = r;
+    a.report[b] = scrub_verdict(reinterpret_cast<const ScrubFold*>(a.report)[b], a.locate);
 }
 
 template <int W>
 hipError_t launch_w(const DegradedArgs& a, long long col0, long long col1, hipStream_t st)
 {
-    // workgroups per block as the update's: enough columns each to amortise
-    // the staging, enough in all to fill the device when the batch is small
-    const long long ncols = col1 - col0;
-    long long gx = (ncols + kDegThreads - 1) / kDegThreads;
-    const long long want = a.blocks >= 1024 ? 8 : (8192 + a.blocks - 1) / a.blocks;
-    if (gx > want)
-        gx = want;
-    const dim3 grid((unsigned)gx, (unsigned)a.blocks), block(kDegThreads);
+    const dim3 grid(columns_grid_x(col1 - col0, a.blocks, kDegThreads), (unsigned)a.blocks), block(kDegThreads);
     const int most = a.u < a.e ? a.u : a.e;  // pivot rows of any block: |D| <= n <= min(u, e)
     const int g = most > 4 ? 8 : most > 2 ? 4 : most > 1 ? 2 : 1;
     const size_t lds = (size_t)a.e * g * (sizeof(uint4) + sizeof(uint32_t)) + (size_t)a.e * sizeof(uint32_t);
@@ -559,8 +496,9 @@ hipError_t launch_w(const DegradedArgs& a, long long col0, long long col1, hipSt
 
 bool args_ok(const DegradedArgs& a)
 {
-    return a.blocks > 0 && a.blocks <= 65535 && a.k > 0 && a.e >= 0 && a.k + a.e <= RSGPU_MAX_SOURCES &&
-           a.u >= 1 && a.u <= 8 && a.lost && a.tab && a.report && a.tab_stride >= degraded_tab_stride(a.k, a.e);
+    return a.blocks > 0 && a.blocks <= (long long)kMaxGridBlocks && a.k > 0 && a.e >= 0 &&
+           a.k + a.e <= RSGPU_MAX_SOURCES && a.u >= 1 && a.u <= 8 && a.lost && a.tab && a.report &&
+           a.tab_stride >= degraded_tab_stride(a.k, a.e);
 }
 
 }  // namespace

@@ -7,6 +7,10 @@ struct rsgpu_scrub_report;  // include/rsgpu.h
 
 namespace rsgpu {
 
+// Most kernels put the block index in grid.y (or z), whose limit is 65535:
+// the block-batched entry points run larger batches as consecutive slices.
+constexpr size_t kMaxGridBlocks = 65535;
+
 struct DotArgs {
     const uint8_t* const* srcs;   // device [blocks][k] row pointers
     uint8_t* const* dsts;         // device [blocks][rows] row pointers
@@ -350,8 +354,8 @@ hipError_t launch_update_blocks(const UpdateArgs& a, bool bytes, long long col0,
 // the reduced column of row r, zero for a lost row.  state != kDegRun: the
 // prepare has written the block's final report and the compare and the
 // finalise leave it alone.  The compare folds into the report's own 16 bytes
-// as the scrub does (DegradedFold is ScrubFold's layout, kScrubBias and
-// kScrubNoRow its constants).
+// as the scrub does (a ScrubFold, with its constants kScrubBias and
+// kScrubNoRow).
 constexpr int kDegRun = 0;      // the compare runs; the report holds a zeroed fold
 constexpr int kDegClean = 100;  // e == 0 or len == 0 with a well-formed list: CLEAN
 // any other state is the block's status: UNCHECKED, BAD_MATRIX or BAD_LIST
@@ -359,10 +363,6 @@ struct DegradedHdr {
     int state;
     uint8_t nq, nrest, pad[2];
     uint8_t q[8];  // parity indices p < e of the pivot rows, ascending
-};
-struct DegradedFold {
-    unsigned long long bad;
-    unsigned hi1, lo1;
 };
 struct DegradedArgs {
     int k, e, u;

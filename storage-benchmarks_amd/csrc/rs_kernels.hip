@@ -45,6 +45,7 @@
 #include "gf256.h"
 #include "rs_jit.h"
 #include "rs_kernels.h"
+#include "rs_lane.h"
 #include "rs_synth.h"
 
 namespace rsgpu {
@@ -56,22 +57,6 @@ static_assert(sizeof(RepairFold) == sizeof(rsgpu_repair_report) && sizeof(Repair
                   kRepairGate == RSGPU_REPAIR_REPAIRED,
               "a block's fold lives in its report, and the report's status is the gate");
 
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
-{
-    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
-
-__device__ __forceinline__ uint32_t vperm(uint32_t hi, uint32_t lo, uint32_t sel)
-{
-    return __builtin_amdgcn_perm(hi, lo, sel);
-}
-
-// Row pointers fetched from memory are generic (flat) pointers; loads through
-// them would be flat_load (out-of-order vs LDS, forcing vmcnt(0)+lgkmcnt(0)
-// waits).  All rows live in global memory, so address-space-cast them.
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const u32x4 g_cu32x4;
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
 __device__ __forceinline__ uint4 gload16(const uint8_t* p, long long w)
 {
     const u32x4 v = ((g_cu32x4*)p)[w];
@@ -704,23 +689,6 @@ __device__ __forceinline__ uint8_t scrub_div(uint8_t a, uint8_t b)
     return a ? kGfTables.exp[kGfTables.log[a] + 255 - kGfTables.log[b]] : 0;
 }
 
-// one atomic per wave and field, none for a wave without a bad column
-__device__ __forceinline__ void scrub_fold_wave(ScrubFold* f, unsigned long long bad, unsigned hi1, unsigned lo1)
-{
-    for (int off = 32; off > 0; off >>= 1) {
-        bad += __shfl_down(bad, off, 64);
-        hi1 = max(hi1, (unsigned)__shfl_down((int)hi1, off, 64));
-        lo1 = max(lo1, (unsigned)__shfl_down((int)lo1, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0 && bad) {
-        atomicAdd(&f->bad, bad);
-        if (hi1) {
-            atomicMax(&f->hi1, hi1);
-            atomicMax(&f->lo1, lo1);
-        }
-    }
-}
-
 // byte column i of a block: counted when bad and, with locate, its row folded.
 // The repair (A::kRepair; wsrc, wpar: the block's writable rows) corrects the
 // column's byte in the row that explains it, src[r][i] ^= x or parity[p0][i]
@@ -877,13 +845,7 @@ __global__ __launch_bounds__(256) void k_scrub_finalise(void* report, long long 
     const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= blocks)
         return;
-    const ScrubFold f = static_cast<const ScrubFold*>(report)[b];
-    rsgpu_scrub_report r;
-    r.bad_columns = f.bad;
-    const bool one = locate && f.hi1 >= 1 && f.hi1 < kScrubNoRow && f.hi1 - 1 == kScrubBias - f.lo1;
-    r.status = f.bad == 0 ? RSGPU_SCRUB_CLEAN : one ? RSGPU_SCRUB_ONE_ROW : RSGPU_SCRUB_DAMAGED;
-    r.row = (f.bad != 0 && one) ? (int)f.hi1 - 1 : -1;
-    static_cast<rsgpu_scrub_report*>(report)[b] = r;
+    static_cast<rsgpu_scrub_report*>(report)[b] = scrub_verdict(static_cast<const ScrubFold*>(report)[b], locate);
 }
 
 // The repair's fold into its report (rs_kernels.h RepairFold).  ONE_ROW: the
@@ -896,7 +858,7 @@ __global__ __launch_bounds__(256) void k_repair_finalise(void* report, long long
     if (b >= blocks)
         return;
     const RepairFold f = static_cast<const RepairFold*>(report)[b];
-    const bool one = f.hi1 >= 1 && f.hi1 < kScrubNoRow && f.hi1 - 1 == kScrubBias - f.lo1;
+    const bool one = fold_one_row(f);
     rsgpu_repair_report r;
     r.bad_columns = f.bad;
     if (mode == RSGPU_REPAIR_ONE_ROW) {
@@ -919,7 +881,8 @@ __global__ __launch_bounds__(256) void k_repair_finalise(void* report, long long
 
 hipError_t launch_repair_compare(const RepairCmpArgs& a, hipStream_t st)
 {
-    if (a.blocks <= 0 || a.blocks > 65535 || a.len <= 0 || a.e <= 0 || !a.src || !a.par || !a.calc || !a.fold)
+    if (a.blocks <= 0 || a.blocks > (long long)kMaxGridBlocks || a.len <= 0 || a.e <= 0 || !a.src || !a.par ||
+        !a.calc || !a.fold)
         return hipErrorInvalidValue;
     const long long gx = std::min<long long>((a.len + 255) / 256, 1024);
     hipLaunchKernelGGL(k_repair_compare, dim3((unsigned)gx, (unsigned)a.blocks), dim3(256), 0, st, a);
@@ -935,7 +898,7 @@ hipError_t launch_repair_finalise(void* report, long long blocks, int mode, hipS
 
 hipError_t launch_scrub_compare(const ScrubCmpArgs& a, hipStream_t st)
 {
-    if (a.blocks <= 0 || a.blocks > 65535 || a.len <= 0 || a.e <= 0)
+    if (a.blocks <= 0 || a.blocks > (long long)kMaxGridBlocks || a.len <= 0 || a.e <= 0)
         return hipErrorInvalidValue;
     const long long gx = std::min<long long>((a.len + 255) / 256, 1024);
     hipLaunchKernelGGL(k_scrub_compare, dim3((unsigned)gx, (unsigned)a.blocks), dim3(256), 0, st, a);

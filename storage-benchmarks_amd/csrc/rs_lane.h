@@ -1,0 +1,114 @@
+// rs_lane.h -- what the kernels of the scrub family share (rs_kernels.hip's
+// scrub and repair, rs_update.hip, rs_degraded.hip): the lane's building
+// blocks (v_perm multiply, three-way XOR, a column of one row), the fold of a
+// wave's bad columns into a block's report, the verdict on a finished fold,
+// and the grid rule of the column kernels.  Internal to librsgpu's .hip files.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+
+#include "../../include/rsgpu.h"
+#include "rs_kernels.h"
+
+namespace rsgpu {
+
+__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
+{
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+}
+
+__device__ __forceinline__ uint32_t vperm(uint32_t hi, uint32_t lo, uint32_t sel)
+{
+    return __builtin_amdgcn_perm(hi, lo, sel);
+}
+
+// Row pointers fetched from memory are generic (flat) pointers; loads through
+// them would be flat_load (out-of-order vs LDS, forcing vmcnt(0)+lgkmcnt(0)
+// waits).  All rows live in global memory, so address-space-cast them.
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) const u32x4 g_cu32x4;
+typedef __attribute__((address_space(1))) u32x4 g_u32x4;
+typedef __attribute__((address_space(1))) const uint8_t g_cu8;
+typedef __attribute__((address_space(1))) uint8_t g_u8;
+
+// A lane's column of one row: W dwords.  W = 4 is the 16-byte vector path
+// (16-byte aligned rows), W = 1 the byte path (one byte in the low bits).
+template <int W>
+struct Col {
+    uint32_t d[W];
+};
+
+template <int W>
+__device__ __forceinline__ Col<W> col_load(const uint8_t* row, long long c)
+{
+    Col<W> r;
+    if constexpr (W == 4) {
+        const u32x4 v = ((g_cu32x4*)row)[c];
+        r.d[0] = v.x; r.d[1] = v.y; r.d[2] = v.z; r.d[3] = v.w;
+    } else {
+        r.d[0] = ((g_cu8*)row)[c];
+    }
+    return r;
+}
+
+template <int W>
+__device__ __forceinline__ void col_store(uint8_t* row, long long c, const Col<W>& v)
+{
+    if constexpr (W == 4) {
+        u32x4 t;
+        t.x = v.d[0]; t.y = v.d[1]; t.z = v.d[2]; t.w = v.d[3];
+        ((g_u32x4*)row)[c] = t;
+    } else {
+        ((g_u8*)row)[c] = (uint8_t)v.d[0];
+    }
+}
+
+// A wave's bad columns into its block's fold (rs_kernels.h ScrubFold): one
+// atomic per wave and field, none for a wave without a bad column.
+__device__ __forceinline__ void scrub_fold_wave(ScrubFold* f, unsigned long long bad, unsigned hi1, unsigned lo1)
+{
+    for (int off = 32; off > 0; off >>= 1) {
+        bad += __shfl_down(bad, off, 64);
+        hi1 = max(hi1, (unsigned)__shfl_down((int)hi1, off, 64));
+        lo1 = max(lo1, (unsigned)__shfl_down((int)lo1, off, 64));
+    }
+    if ((threadIdx.x & 63) == 0 && bad) {
+        atomicAdd(&f->bad, bad);
+        if (hi1) {
+            atomicMax(&f->hi1, hi1);
+            atomicMax(&f->lo1, lo1);
+        }
+    }
+}
+
+// the two maxima of a fold (ScrubFold, RepairFold) name the same row: every
+// column that counted is explained by it
+template <class F>
+__device__ __forceinline__ bool fold_one_row(const F& f)
+{
+    return f.hi1 >= 1 && f.hi1 < kScrubNoRow && f.hi1 - 1 == kScrubBias - f.lo1;
+}
+
+// a block's finished fold as its report
+__device__ __forceinline__ rsgpu_scrub_report scrub_verdict(const ScrubFold& f, int locate)
+{
+    rsgpu_scrub_report r;
+    r.bad_columns = f.bad;
+    const bool one = locate && fold_one_row(f);
+    r.status = f.bad == 0 ? RSGPU_SCRUB_CLEAN : one ? RSGPU_SCRUB_ONE_ROW : RSGPU_SCRUB_DAMAGED;
+    r.row = (f.bad != 0 && one) ? (int)f.hi1 - 1 : -1;
+    return r;
+}
+
+// Workgroups per block of a kernel whose lanes own columns: enough columns
+// each to amortise the staging of the block's tables, enough in all to fill
+// the device when the batch is small.
+inline unsigned columns_grid_x(long long ncols, long long blocks, int threads)
+{
+    const long long want = blocks >= 1024 ? 8 : (8192 + blocks - 1) / blocks;
+    return (unsigned)std::max(1LL, std::min((ncols + threads - 1) / threads, want));
+}
+
+}  // namespace rsgpu

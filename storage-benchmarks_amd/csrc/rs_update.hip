@@ -27,58 +27,11 @@
 
 #include "../../include/rsgpu.h"
 #include "rs_kernels.h"
+#include "rs_lane.h"
 
 namespace rsgpu {
 
 namespace {
-
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
-{
-    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
-
-__device__ __forceinline__ uint32_t vperm(uint32_t hi, uint32_t lo, uint32_t sel)
-{
-    return __builtin_amdgcn_perm(hi, lo, sel);
-}
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) const u32x4 g_cu32x4;
-typedef __attribute__((address_space(1))) u32x4 g_u32x4;
-typedef __attribute__((address_space(1))) const uint8_t g_cu8;
-typedef __attribute__((address_space(1))) uint8_t g_u8;
-
-// A lane's column of one row: W dwords.  W = 4 is the 16-byte vector path
-// (16-byte aligned rows), W = 1 the byte path (one byte in the low bits).
-template <int W>
-struct Col {
-    uint32_t d[W];
-};
-
-template <int W>
-__device__ __forceinline__ Col<W> col_load(const uint8_t* row, long long c)
-{
-    Col<W> r;
-    if constexpr (W == 4) {
-        const u32x4 v = ((g_cu32x4*)row)[c];
-        r.d[0] = v.x; r.d[1] = v.y; r.d[2] = v.z; r.d[3] = v.w;
-    } else {
-        r.d[0] = ((g_cu8*)row)[c];
-    }
-    return r;
-}
-
-template <int W>
-__device__ __forceinline__ void col_store(uint8_t* row, long long c, const Col<W>& v)
-{
-    if constexpr (W == 4) {
-        u32x4 t;
-        t.x = v.d[0]; t.y = v.d[1]; t.z = v.d[2]; t.w = v.d[3];
-        ((g_u32x4*)row)[c] = t;
-    } else {
-        ((g_u8*)row)[c] = (uint8_t)v.d[0];
-    }
-}
 
 constexpr int kUpdThreads = 256;
 constexpr int kParityAhead = 4;  // parity rows loaded before the first is stored
@@ -188,16 +141,7 @@ __global__ __launch_bounds__(kUpdThreads) void k_update_blocks(UpdateArgs a, lon
 template <int W>
 hipError_t launch_w(const UpdateArgs& a, long long col0, long long col1, hipStream_t st)
 {
-    // workgroups per block: enough columns each to amortise the staging of the
-    // tables, enough in all to fill the device when the batch is small
-    const long long ncols = col1 - col0;
-    long long gx = (ncols + kUpdThreads - 1) / kUpdThreads;
-    const long long want = a.blocks >= 1024 ? 8 : (8192 + a.blocks - 1) / a.blocks;
-    if (gx > want)
-        gx = want;
-    if (gx < 1)
-        gx = 1;
-    const dim3 grid((unsigned)gx, (unsigned)a.blocks), block(kUpdThreads);
+    const dim3 grid(columns_grid_x(col1 - col0, a.blocks, kUpdThreads), (unsigned)a.blocks), block(kUpdThreads);
     const int g = a.u > 4 ? 8 : a.u > 2 ? 4 : a.u;
     const size_t lds = (size_t)a.e * g * (sizeof(uint4) + sizeof(uint32_t));
     switch (g) {

@@ -1,6 +1,7 @@
 // rsgpu_capi.cpp -- C ABI of librsgpu (include/rsgpu.h): host GF helpers with
 // ISA-L semantics, context/stream management, and the launch sequences of the
-// batched encode / decode hot path.
+// batched encode / decode hot path.  Scrub, repair, update and degraded scrub
+// are rsgpu_scrub.cpp; the helpers both files use, rsgpu_internal.h.
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
@@ -15,14 +16,13 @@
 #include "../../include/rsgpu.h"
 #include "gf256.h"
 #include "rsgpu_ctx.h"
+#include "rsgpu_internal.h"
 #include "jit_prog.h"
 #include "rs_jit.h"
 #include "rs_kernels.h"
 #include "rs_synth.h"
 
-namespace {
-
-using namespace rsgpu;
+namespace rsgpu {
 
 const GfTables& host_gf()
 {
@@ -34,34 +34,38 @@ const GfTables& host_gf()
     return t;
 }
 
-inline uint8_t hmul(uint8_t a, uint8_t b)
+uint8_t hmul(uint8_t a, uint8_t b)
 {
     const GfTables& t = host_gf();
     return (a && b) ? t.exp[t.log[a] + t.log[b]] : 0;
 }
 
-// Grow the scratch buffer.  Every kernel that may still read the old buffer
-// was enqueued on the context stream, or on an earlier stream the current
-// one waits on (rsgpu_set_stream), so synchronising the current stream
-// retires them all before the free.
-int ensure_scratch(rsgpu_ctx* ctx, size_t bytes)
+int check_geom(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks)
 {
-    if (ctx->scratch_bytes >= bytes)
-        return RSGPU_OK;
-    if (ctx->d_scratch) {
-        RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        RS_HIP(ctx, hipFree(ctx->d_scratch));
-        ctx->d_scratch = nullptr;
-        ctx->scratch_bytes = 0;
-    }
-    size_t want = bytes < (1u << 20) ? (1u << 20) : bytes;
-    RS_HIP(ctx, hipMalloc(&ctx->d_scratch, want));
-    ctx->scratch_bytes = want;
+    if (!ctx)
+        return RSGPU_ERR_ARG;
+    if (k <= 0 || e < 0 || k + e > RSGPU_MAX_SOURCES || pitch < len || blocks == 0)
+        return fail(ctx, RSGPU_ERR_ARG, "bad geometry (k, e, len, pitch, blocks)");
     return RSGPU_OK;
 }
 
-// Returns a pinned staging pointer of >= bytes, after the previous upload
-// from it has completed.
+int ensure_device(rsgpu_ctx* ctx, rsgpu_ctx::DevBuf& b, size_t bytes, size_t floor)
+{
+    if (b.bytes >= bytes)
+        return RSGPU_OK;
+    if (b.p) {
+        RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        RS_HIP(ctx, hipFree(b.p));
+        b.p = nullptr;
+        b.bytes = 0;
+    }
+    b.key.clear();
+    const size_t want = std::max(bytes, floor);
+    RS_HIP(ctx, hipMalloc(&b.p, want));
+    b.bytes = want;
+    return RSGPU_OK;
+}
+
 int get_stage(rsgpu_ctx* ctx, size_t bytes, void** out)
 {
     if (ctx->stage_pending) {
@@ -79,15 +83,14 @@ int get_stage(rsgpu_ctx* ctx, size_t bytes, void** out)
     return RSGPU_OK;
 }
 
-int upload(rsgpu_ctx* ctx, void* d_dst, size_t bytes)
+int upload(rsgpu_ctx* ctx, void* d_dst, size_t bytes, size_t dst_off, size_t stage_off)
 {
-    RS_HIP(ctx, hipMemcpyAsync(d_dst, ctx->h_stage, bytes, hipMemcpyHostToDevice, ctx->stream));
+    RS_HIP(ctx, hipMemcpyAsync((char*)d_dst + dst_off, (char*)ctx->h_stage + stage_off, bytes,
+                               hipMemcpyHostToDevice, ctx->stream));
     RS_HIP(ctx, hipEventRecord(ctx->stage_done, ctx->stream));
     ctx->stage_pending = true;
     return RSGPU_OK;
 }
-
-inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 hipEvent_t pool_event(rsgpu_ctx* ctx)
 {
@@ -100,6 +103,16 @@ hipEvent_t pool_event(rsgpu_ctx* ctx)
     (void)hipEventCreate(&e);
     return e;
 }
+
+}  // namespace rsgpu
+
+namespace {
+
+using namespace rsgpu;
+
+int ensure_scratch(rsgpu_ctx* ctx, size_t bytes) { return ensure_device(ctx, ctx->scratch, bytes, 1u << 20); }
+
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // Cross-stream ordering events (timing disabled), recycled round-robin: an
 // event may be re-recorded once the stream that waits on it has been handed
@@ -116,31 +129,6 @@ hipEvent_t sync_event(rsgpu_ctx* ctx)
     ctx->sync_next = (ctx->sync_next + 1) % ctx->sync_evs.size();
     return e;
 }
-
-// Brackets one kernel launch with events when timing is enabled.
-struct KTimer {
-    rsgpu_ctx* ctx;
-    hipStream_t s;
-    rsgpu_ctx::Rec rec{};
-    KTimer(rsgpu_ctx* c, const char* name, size_t blocks) : KTimer(c, name, blocks, c->stream) {}
-    KTimer(rsgpu_ctx* c, const char* name, size_t blocks, hipStream_t st) : ctx(c), s(st)
-    {
-        if (!ctx->timing)
-            return;
-        rec.name = name;
-        rec.blocks = blocks;
-        rec.a = pool_event(ctx);
-        rec.b = pool_event(ctx);
-        (void)hipEventRecord(rec.a, s);
-    }
-    ~KTimer()
-    {
-        if (!ctx->timing)
-            return;
-        (void)hipEventRecord(rec.b, s);
-        ctx->recs.push_back(rec);
-    }
-};
 
 // Locate the handler table of k_rs_tc once per context: the query kernel
 // reports the table's first and end addresses; the layout must be exactly
@@ -512,14 +500,14 @@ int dot_from_host_coef(rsgpu_ctx* ctx, const uint8_t* coef, int k, int rows, lon
         if (pre && pre_bytes <= sizeof(PutArgs::w) && pre_bytes % 8 == 0) {
             // a few row pointers (isa_arithmetic's per-row calls): through the
             // kernel arguments, no staging round trip
-            RS_HIP(ctx, launch_put_words(ctx->d_scratch, pre, pre_bytes, ctx->stream));
+            RS_HIP(ctx, launch_put_words(ctx->scratch.p, pre, pre_bytes, ctx->stream));
         } else if (pre) {  // the row pointers the caller staged with the table upload
             void* stage;
             int rc = get_stage(ctx, pre_bytes, &stage);
             if (rc)
                 return rc;
             std::memcpy(stage, pre, pre_bytes);
-            rc = upload(ctx, ctx->d_scratch, pre_bytes);
+            rc = upload(ctx, ctx->scratch.p, pre_bytes);
             if (rc)
                 return rc;
         }
@@ -537,8 +525,8 @@ int dot_from_host_coef(rsgpu_ctx* ctx, const uint8_t* coef, int k, int rows, lon
     if (pre)
         std::memcpy(stage, pre, pre_bytes);
     char* tab = (char*)stage + skip;
-    char* d = (char*)ctx->d_scratch + tab_off;
-    char* d_up = pre ? (char*)ctx->d_scratch : d;
+    char* d = (char*)ctx->scratch.p + tab_off;
+    char* d_up = pre ? (char*)ctx->scratch.p : d;
     if (tcp) {
         tc_fill_addr(ctx, coef, k, rows, (unsigned long long*)tab);
         rc = upload(ctx, d_up, skip + bytes);
@@ -607,14 +595,9 @@ int rsgpu_destroy(rsgpu_ctx* ctx)
         return RSGPU_ERR_ARG;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->d_scratch)
-        (void)hipFree(ctx->d_scratch);
-    if (ctx->d_scrub)
-        (void)hipFree(ctx->d_scrub);
-    if (ctx->d_update)
-        (void)hipFree(ctx->d_update);
-    if (ctx->d_degraded)
-        (void)hipFree(ctx->d_degraded);
+    for (void* p : {ctx->scratch.p, ctx->scrub.p, ctx->d_update, ctx->degraded.p})
+        if (p)
+            (void)hipFree(p);
     if (ctx->h_stage)
         (void)hipHostFree(ctx->h_stage);
     if (ctx->stage_done)
@@ -873,7 +856,7 @@ int rsgpu_ec_encode_data(rsgpu_ctx* ctx, int len, int k, int rows, const unsigne
         hp[j] = data[j];
     for (int r = 0; r < rows; ++r)
         hp[k + r] = coding[r];
-    char* d = (char*)ctx->d_scratch;
+    char* d = (char*)ctx->scratch.p;
     return dot_from_host_coef(ctx, coef.data(), k, rows, len, 1, (const uint8_t* const*)d,
                               (uint8_t* const*)(d + sizeof(void*) * k), ptr_bytes, aligned,
                               "k_rs_tc(ec_encode_data)", "k_rs_jit(ec_encode_data)", hp.data(),
@@ -910,10 +893,10 @@ int rsgpu_ec_encode_data_update(rsgpu_ctx* ctx, int len, int k, int rows, int ve
         t4[r] = make_uint4(t[0], t[1], t[2], t[3]);
         tc[r] = t[4];
     }
-    rc = upload(ctx, ctx->d_scratch, ptr_bytes + tab_bytes);
+    rc = upload(ctx, ctx->scratch.p, ptr_bytes + tab_bytes);
     if (rc)
         return rc;
-    char* d = (char*)ctx->d_scratch;
+    char* d = (char*)ctx->scratch.p;
     RS_HIP(ctx, launch_update(data, (uint8_t* const*)d, (const uint4*)(d + ptr_bytes),
                               (const uint32_t*)(d + ptr_bytes + (size_t)rows * sizeof(uint4)),
                               rows, len, ctx->stream));
@@ -948,19 +931,6 @@ int rsgpu_gf_vect_mul(rsgpu_ctx* ctx, int len, const unsigned char* gftbl, void*
 }
 
 // ---- device, batched -----------------------------------------------------------
-
-// Most kernels put the block index in grid.y (or z), whose limit is 65535:
-// the block-batched entry points run larger batches as consecutive slices.
-constexpr size_t kMaxGridBlocks = 65535;
-
-static int check_geom(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks)
-{
-    if (!ctx)
-        return RSGPU_ERR_ARG;
-    if (k <= 0 || e < 0 || k + e > RSGPU_MAX_SOURCES || pitch < len || blocks == 0)
-        return fail(ctx, RSGPU_ERR_ARG, "bad geometry (k, e, len, pitch, blocks)");
-    return RSGPU_OK;
-}
 
 int rsgpu_encode_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                         const unsigned char* d_src, unsigned char* d_parity,
@@ -1025,7 +995,7 @@ int rsgpu_encode_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
     rc = ensure_scratch(ctx, src_ptr_bytes + dst_ptr_bytes + dot_table_bytes(k, e));
     if (rc)
         return rc;
-    char* d = (char*)ctx->d_scratch;
+    char* d = (char*)ctx->scratch.p;
     RS_HIP(ctx, launch_row_ptrs(d_src, (long long)pitch, k, (long long)blocks,
                                 (const uint8_t**)d, ctx->stream));
     RS_HIP(ctx, launch_row_ptrs(d_parity, (long long)pitch, e, (long long)blocks,
@@ -1697,10 +1667,10 @@ int rsgpu_decode_general(rsgpu_ctx* ctx, int k, int m, size_t len, size_t pitch,
         if (rc)
             return rc;
         std::memcpy(stage, encode_matrix, bytes);
-        rc = upload(ctx, ctx->d_scratch, bytes);
+        rc = upload(ctx, ctx->scratch.p, bytes);
         if (rc)
             return rc;
-        d_enc = (const uint8_t*)ctx->d_scratch;
+        d_enc = (const uint8_t*)ctx->scratch.p;
     }
     rc = general_prepare(ctx, plan, k, m, nerrs, false, pitch, blocks, d_enc, d_src, d_parity, d_err,
                          d_out, d_workspace, d_status);
@@ -1732,557 +1702,6 @@ int rsgpu_verify_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
     }
     RS_HIP(ctx, launch_compare_rows(d_src, (long long)pitch, k, d_out, (long long)pitch, e, d_err,
                                     (long long)len, (long long)blocks, d_mismatch, ctx->stream));
-    return RSGPU_OK;
-}
-
-}  // extern "C"
-
-namespace {
-
-// ---- parity scrub ------------------------------------------------------------
-
-// the e x k parity matrix of a scrub: `coef`, or the gf_gen_rs_matrix rows
-std::vector<uint8_t> scrub_matrix(int k, int e, const unsigned char* coef)
-{
-    std::vector<uint8_t> c((size_t)e * k);
-    if (coef) {
-        std::memcpy(c.data(), coef, c.size());
-    } else {
-        std::vector<uint8_t> a((size_t)(k + e) * k);
-        rsgpu_gf_gen_rs_matrix(a.data(), k + e, k);
-        std::memcpy(c.data(), a.data() + (size_t)k * k, c.size());
-    }
-    return c;
-}
-
-// rsgpu.h's rule: e >= 2, no zero in rows 0 and 1, the ratios c[1][j] / c[0][j]
-// pairwise distinct.  tab (256 bytes, optional): ratio -> j, 255 for none.
-bool scrub_locatable(int k, int e, const uint8_t* c, uint8_t* tab)
-{
-    uint8_t t[256];
-    std::memset(t, 255, sizeof t);
-    bool ok = e >= 2 && k <= 255;
-    for (int j = 0; ok && j < k; ++j) {
-        const uint8_t c0 = c[j], c1 = c[(size_t)k + j];
-        if (!c0 || !c1) {
-            ok = false;
-            break;
-        }
-        const uint8_t ratio = hmul(c1, rsgpu_gf_inv(c0));
-        ok = t[ratio] == 255;
-        t[ratio] = (uint8_t)j;
-    }
-    if (ok && tab)
-        std::memcpy(tab, t, sizeof t);
-    return ok;
-}
-
-// Two-pass scratch: [rowtab 256 B | matrix e x k | pad to kScrubTabBytes |
-// computed parity of a slice].  The parity part is bounded: a slice holds as
-// many blocks as fit kScrubParityBytes (4 blocks of C3's 32 x 1 MB parity;
-// enough workgroups per launch to fill the device), one block when a single
-// block's parity is larger.
-constexpr size_t kScrubTabBytes = 16384;  // 256 + e k <= 256 + 125 * 125
-constexpr size_t kScrubParityBytes = 128u << 20;
-
-int ensure_scrub(rsgpu_ctx* ctx, size_t bytes)
-{
-    if (ctx->scrub_bytes >= bytes)
-        return RSGPU_OK;
-    if (ctx->d_scrub) {
-        // every kernel that reads the old buffer is on the context's stream
-        RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        RS_HIP(ctx, hipFree(ctx->d_scrub));
-        ctx->d_scrub = nullptr;
-        ctx->scrub_bytes = 0;
-    }
-    ctx->scrub_key.clear();
-    RS_HIP(ctx, hipMalloc(&ctx->d_scrub, bytes));
-    ctx->scrub_bytes = bytes;
-    return RSGPU_OK;
-}
-
-// the ratio -> row table and the matrix at the head of the scrub buffer
-int scrub_tables(rsgpu_ctx* ctx, int k, int e, const std::vector<uint8_t>& c, const uint8_t* rowtab)
-{
-    std::vector<uint8_t> key(8 + c.size());
-    std::memcpy(key.data(), &k, 4);
-    std::memcpy(key.data() + 4, &e, 4);
-    std::memcpy(key.data() + 8, c.data(), c.size());
-    if (key == ctx->scrub_key)
-        return RSGPU_OK;
-    // the tables of another matrix: upload once
-    void* stage;
-    int rc = get_stage(ctx, 256 + c.size(), &stage);
-    if (rc)
-        return rc;
-    std::memcpy(stage, rowtab, 256);
-    std::memcpy((char*)stage + 256, c.data(), c.size());
-    rc = upload(ctx, ctx->d_scrub, 256 + c.size());
-    if (rc)
-        return rc;
-    ctx->scrub_key = std::move(key);
-    return RSGPU_OK;
-}
-
-int scrub_two_pass(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks, const uint8_t* d_src,
-                   const uint8_t* d_parity, const unsigned char* coef, const std::vector<uint8_t>& c,
-                   const uint8_t* rowtab, bool locate, ScrubFold* fold)
-{
-    const size_t per_block = (size_t)e * pitch;
-    const size_t slice = std::max<size_t>(1, std::min(blocks, kScrubParityBytes / per_block));
-    int rc = ensure_scrub(ctx, kScrubTabBytes + slice * per_block);
-    if (rc)
-        return rc;
-    uint8_t* d = (uint8_t*)ctx->d_scrub;
-    if (locate) {
-        rc = scrub_tables(ctx, k, e, c, rowtab);
-        if (rc)
-            return rc;
-    }
-    uint8_t* calc = d + kScrubTabBytes;
-    for (size_t b0 = 0; b0 < blocks; b0 += slice) {
-        const size_t nb = std::min(slice, blocks - b0);
-        rc = rsgpu_encode_blocks(ctx, k, e, len, pitch, nb, d_src + b0 * k * pitch, calc, coef);
-        if (rc)
-            return rc;
-        ScrubCmpArgs a{};
-        a.calc = calc;
-        a.par = d_parity + b0 * per_block;
-        a.pitch = (long long)pitch;
-        a.len = (long long)len;
-        a.blocks = (long long)nb;
-        a.k = k;
-        a.e = e;
-        a.rowtab = d;
-        a.coef = d + 256;
-        a.fold = fold + b0;
-        a.locate = locate ? 1 : 0;
-        KTimer kt(ctx, "k_scrub_compare", nb);
-        RS_HIP(ctx, launch_scrub_compare(a, ctx->stream));
-    }
-    return RSGPU_OK;
-}
-
-// The repair of at most kMaxGridBlocks blocks through the two-pass path, slice
-// by slice of the scratch: the encode, then COLUMNS: the correcting compare;
-// ONE_ROW: the compare that only folds, the finalise of the slice's reports,
-// and the gated correcting compare, while the slice's computed parity is
-// still in the scratch.  The caller finalises a COLUMNS call.
-int repair_two_pass(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks, uint8_t* d_src,
-                    uint8_t* d_parity, const unsigned char* coef, const std::vector<uint8_t>& c,
-                    const uint8_t* rowtab, int mode, RepairFold* fold)
-{
-    const size_t per_block = (size_t)e * pitch;
-    const size_t slice = std::max<size_t>(1, std::min(blocks, kScrubParityBytes / per_block));
-    int rc = ensure_scrub(ctx, kScrubTabBytes + slice * per_block);
-    if (rc)
-        return rc;
-    rc = scrub_tables(ctx, k, e, c, rowtab);
-    if (rc)
-        return rc;
-    uint8_t* d = (uint8_t*)ctx->d_scrub;
-    for (size_t b0 = 0; b0 < blocks; b0 += slice) {
-        const size_t nb = std::min(slice, blocks - b0);
-        rc = rsgpu_encode_blocks(ctx, k, e, len, pitch, nb, d_src + b0 * k * pitch, d + kScrubTabBytes, coef);
-        if (rc)
-            return rc;
-        RepairCmpArgs a{};
-        a.calc = d + kScrubTabBytes;
-        a.src = d_src + b0 * k * pitch;
-        a.par = d_parity + b0 * per_block;
-        a.pitch = (long long)pitch;
-        a.len = (long long)len;
-        a.blocks = (long long)nb;
-        a.k = k;
-        a.e = e;
-        a.rowtab = d;
-        a.coef = d + 256;
-        a.fold = fold + b0;
-        a.mode = mode == RSGPU_REPAIR_COLUMNS ? kRepairColumns : kRepairLocate;
-        {
-            KTimer kt(ctx, "k_repair_compare", nb);
-            RS_HIP(ctx, launch_repair_compare(a, ctx->stream));
-        }
-        if (mode == RSGPU_REPAIR_ONE_ROW) {
-            {
-                KTimer kt(ctx, "k_repair_finalise", nb);
-                RS_HIP(ctx, launch_repair_finalise(fold + b0, (long long)nb, mode, ctx->stream));
-            }
-            a.mode = kRepairGated;
-            KTimer kt(ctx, "k_repair_compare_gated", nb);
-            RS_HIP(ctx, launch_repair_compare(a, ctx->stream));
-        }
-    }
-    return RSGPU_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int rsgpu_scrub_locatable(int k, int e, const unsigned char* coef)
-{
-    if (k <= 0 || e < 0 || k + e > RSGPU_MAX_SOURCES)
-        return 0;
-    if (e < 2)
-        return 0;
-    const std::vector<uint8_t> c = scrub_matrix(k, e, coef);
-    return scrub_locatable(k, e, c.data(), nullptr) ? 1 : 0;
-}
-
-int rsgpu_set_scrub_kernel(rsgpu_ctx* ctx, int kernel)
-{
-    if (!ctx || kernel < RSGPU_SCRUB_AUTO || kernel > RSGPU_SCRUB_TWO_PASS)
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_scrub_kernel: unknown kernel");
-    ctx->scrub_kernel = kernel;
-    return RSGPU_OK;
-}
-
-int rsgpu_scrub_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
-                       const unsigned char* d_src, const unsigned char* d_parity,
-                       const unsigned char* coef, int flags, rsgpu_scrub_report* d_report)
-{
-    int rc = check_geom(ctx, k, e, len, pitch, blocks);
-    if (rc)
-        return rc;
-    if (!d_report || (uintptr_t)d_report % 8 != 0 || (flags & ~RSGPU_SCRUB_LOCATE) != 0)
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_scrub_blocks: bad report pointer or flags");
-    const bool locate = (flags & RSGPU_SCRUB_LOCATE) != 0;
-    const bool work = e > 0 && len > 0;
-    if (work && (!d_src || !d_parity))
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_scrub_blocks: null rows");
-    std::vector<uint8_t> c;
-    uint8_t rowtab[256];
-    if (locate) {
-        if (e >= 2)
-            c = scrub_matrix(k, e, coef);
-        if (e < 2 || !scrub_locatable(k, e, c.data(), rowtab))
-            return fail(ctx, RSGPU_ERR_UNSUPPORTED,
-                        "rsgpu_scrub_blocks: RSGPU_SCRUB_LOCATE needs a locatable matrix (rsgpu_scrub_locatable)");
-    }
-    ScrubFold* fold = reinterpret_cast<ScrubFold*>(d_report);
-    RS_HIP(ctx, hipMemsetAsync(d_report, 0, blocks * sizeof(rsgpu_scrub_report), ctx->stream));
-    if (work) {
-        const bool fused = ctx->scrub_kernel != RSGPU_SCRUB_TWO_PASS && !coef && rs_bitsliced_available(k, e) &&
-                           len % 32 == 0 && len < (1ull << 32) && pitch % 16 == 0 &&
-                           (uintptr_t)d_src % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
-        // block index in grid.y: larger batches as consecutive slices
-        for (size_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks) {
-            const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
-            const uint8_t* src = d_src + b0 * k * pitch;
-            const uint8_t* par = d_parity + b0 * e * pitch;
-            if (fused) {
-                KTimer kt(ctx, "k_rs_bs_scrub", nb);
-                RS_HIP(ctx, launch_rs_bitsliced_scrub(k, e, src, par, (long long)pitch, (long long)len,
-                                                      (long long)nb, fold + b0, locate ? 1 : 0, ctx->stream));
-            } else {
-                rc = scrub_two_pass(ctx, k, e, len, pitch, nb, src, par, coef, c, rowtab, locate, fold + b0);
-                if (rc)
-                    return rc;
-            }
-        }
-    }
-    KTimer kt(ctx, "k_scrub_finalise", blocks);
-    RS_HIP(ctx, launch_scrub_finalise(d_report, (long long)blocks, locate ? 1 : 0, ctx->stream));
-    return RSGPU_OK;
-}
-
-int rsgpu_repair_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
-                        unsigned char* d_src, unsigned char* d_parity, const unsigned char* coef, int mode,
-                        rsgpu_repair_report* d_report)
-{
-    int rc = check_geom(ctx, k, e, len, pitch, blocks);
-    if (rc)
-        return rc;
-    if (!d_report || (uintptr_t)d_report % 8 != 0 ||
-        (mode != RSGPU_REPAIR_ONE_ROW && mode != RSGPU_REPAIR_COLUMNS))
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_repair_blocks: bad report pointer or mode");
-    const bool work = e > 0 && len > 0;
-    if (work && (!d_src || !d_parity))
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_repair_blocks: null rows");
-    std::vector<uint8_t> c;
-    uint8_t rowtab[256];
-    if (e > 0) {  // e == 0: no parity, nothing can be bad
-        if (e >= 2)
-            c = scrub_matrix(k, e, coef);
-        if (e < 2 || !scrub_locatable(k, e, c.data(), rowtab))
-            return fail(ctx, RSGPU_ERR_UNSUPPORTED,
-                        "rsgpu_repair_blocks: needs a locatable matrix (rsgpu_scrub_locatable)");
-        if (mode == RSGPU_REPAIR_COLUMNS && e < 3)
-            return fail(ctx, RSGPU_ERR_UNSUPPORTED, "rsgpu_repair_blocks: RSGPU_REPAIR_COLUMNS needs e >= 3");
-    }
-    RepairFold* fold = reinterpret_cast<RepairFold*>(d_report);
-    RS_HIP(ctx, hipMemsetAsync(d_report, 0, blocks * sizeof(rsgpu_repair_report), ctx->stream));
-    if (!work) {
-        KTimer kt(ctx, "k_repair_finalise", blocks);
-        RS_HIP(ctx, launch_repair_finalise(d_report, (long long)blocks, mode, ctx->stream));
-        return RSGPU_OK;
-    }
-    const bool fused = ctx->scrub_kernel != RSGPU_SCRUB_TWO_PASS && !coef && rs_bitsliced_available(k, e) &&
-                       len % 32 == 0 && len < (1ull << 32) && pitch % 16 == 0 && (uintptr_t)d_src % 16 == 0 &&
-                       (uintptr_t)d_parity % 16 == 0;
-    // block index in grid.y: larger batches as consecutive slices, each
-    // complete (located, finalised, corrected) before the next
-    for (size_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks) {
-        const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
-        uint8_t* src = d_src + b0 * k * pitch;
-        uint8_t* par = d_parity + b0 * e * pitch;
-        if (!fused) {
-            rc = repair_two_pass(ctx, k, e, len, pitch, nb, src, par, coef, c, rowtab, mode, fold + b0);
-            if (rc)
-                return rc;
-            if (mode == RSGPU_REPAIR_ONE_ROW)
-                continue;  // finalised slice by slice
-        } else {
-            KTimer kt(ctx, "k_rs_bs_repair", nb);
-            RS_HIP(ctx, launch_rs_bitsliced_repair(k, e, src, par, (long long)pitch, (long long)len, (long long)nb,
-                                                   fold + b0, mode == RSGPU_REPAIR_COLUMNS ? kRepairColumns
-                                                                                           : kRepairLocate,
-                                                   ctx->stream));
-        }
-        {
-            KTimer kt(ctx, "k_repair_finalise", nb);
-            RS_HIP(ctx, launch_repair_finalise(fold + b0, (long long)nb, mode, ctx->stream));
-        }
-        if (fused && mode == RSGPU_REPAIR_ONE_ROW) {
-            KTimer kt(ctx, "k_rs_bs_repair_gated", nb);
-            RS_HIP(ctx, launch_rs_bitsliced_repair(k, e, src, par, (long long)pitch, (long long)len, (long long)nb,
-                                                   fold + b0, kRepairGated, ctx->stream));
-        }
-    }
-    return RSGPU_OK;
-}
-
-// ---- partial-stripe update -----------------------------------------------------
-
-// The update's device buffer: [tab4 256 x 16 B | tabc 256 x 4 B | matrix].
-constexpr size_t kUpdTab4Bytes = 256 * sizeof(uint4);
-constexpr size_t kUpdTabBytes = kUpdTab4Bytes + 256 * sizeof(uint32_t);
-constexpr size_t kUpdMatrixBytes = (size_t)RSGPU_MAX_SOURCES * RSGPU_MAX_SOURCES;
-
-// The tables (once per context) and the matrix (when it differs from the one
-// the buffer holds) go up on the stream, ahead of the kernel that reads them.
-static int update_tables(rsgpu_ctx* ctx, int k, int e, const unsigned char* coef)
-{
-    const bool fresh = ctx->d_update == nullptr;
-    if (fresh) {
-        RS_HIP(ctx, hipMalloc(&ctx->d_update, kUpdTabBytes + kUpdMatrixBytes));
-        ctx->update_key.clear();
-    }
-    std::vector<uint8_t> c;
-    std::vector<uint8_t> key;
-    if (e > 0) {
-        c = scrub_matrix(k, e, coef);
-        key.resize(8 + c.size());
-        std::memcpy(key.data(), &k, 4);
-        std::memcpy(key.data() + 4, &e, 4);
-        std::memcpy(key.data() + 8, c.data(), c.size());
-    }
-    const bool matrix = e > 0 && key != ctx->update_key;
-    if (!fresh && !matrix)
-        return RSGPU_OK;
-    const size_t first = fresh ? 0 : kUpdTabBytes;
-    const size_t last = matrix ? kUpdTabBytes + c.size() : kUpdTabBytes;
-    void* stage;
-    int rc = get_stage(ctx, kUpdTabBytes + kUpdMatrixBytes, &stage);
-    if (rc)
-        return rc;
-    if (fresh) {
-        uint4* t4 = (uint4*)stage;
-        uint32_t* tc = (uint32_t*)((char*)stage + kUpdTab4Bytes);
-        for (int v = 0; v < 256; ++v) {
-            uint32_t t[5];
-            perm_tables((uint8_t)v, t);
-            t4[v] = make_uint4(t[0], t[1], t[2], t[3]);
-            tc[v] = t[4];
-        }
-    }
-    if (matrix)
-        std::memcpy((char*)stage + kUpdTabBytes, c.data(), c.size());
-    RS_HIP(ctx, hipMemcpyAsync((char*)ctx->d_update + first, (char*)stage + first, last - first,
-                               hipMemcpyHostToDevice, ctx->stream));
-    RS_HIP(ctx, hipEventRecord(ctx->stage_done, ctx->stream));
-    ctx->stage_pending = true;
-    if (matrix)
-        ctx->update_key = std::move(key);
-    return RSGPU_OK;
-}
-
-static bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn)
-{
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return an > 0 && bn > 0 && a0 < b0 + bn && b0 < a0 + an;
-}
-
-int rsgpu_update_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks, int u,
-                        const unsigned char* d_cols, const unsigned char* d_upd, unsigned char* d_src,
-                        unsigned char* d_parity, const unsigned char* coef, int flags, int* d_status)
-{
-    int rc = check_geom(ctx, k, e, len, pitch, blocks);
-    if (rc)
-        return rc;
-    if (u < 1 || u > k || (flags & ~RSGPU_UPDATE_DELTA) != 0 || !d_cols || !d_status)
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_update_blocks: bad u, flags, list or status pointer");
-    const bool delta = (flags & RSGPU_UPDATE_DELTA) != 0;
-    const bool src_used = !delta, par_used = e > 0;
-    if (len > 0 && (((src_used || par_used) && !d_upd) || (src_used && !d_src) || (par_used && !d_parity)))
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_update_blocks: null rows");
-    // rows i of a buffer of R rows per block end at ((blocks R - 1) pitch + len)
-    auto span = [&](size_t rows) { return len == 0 ? (size_t)0 : (blocks * rows - 1) * pitch + len; };
-    if ((src_used && ranges_overlap(d_upd, span((size_t)u), d_src, span((size_t)k))) ||
-        (par_used && ranges_overlap(d_upd, span((size_t)u), d_parity, span((size_t)e))))
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_update_blocks: d_upd overlaps d_src or d_parity");
-    rc = update_tables(ctx, k, e, coef);
-    if (rc)
-        return rc;
-    const bool work = len > 0 && (src_used || par_used);
-    const bool vec = pitch % 16 == 0 && (uintptr_t)d_upd % 16 == 0 && (!src_used || (uintptr_t)d_src % 16 == 0) &&
-                     (!par_used || (uintptr_t)d_parity % 16 == 0);
-    const long long n16 = work && vec ? (long long)(len / 16) : 0;
-    // block index in grid.y: larger batches as consecutive slices
-    for (size_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks) {
-        const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
-        UpdateArgs a{};
-        a.k = k;
-        a.e = e;
-        a.u = u;
-        a.delta = delta ? 1 : 0;
-        a.pitch = (long long)pitch;
-        a.blocks = (long long)nb;
-        a.cols = d_cols + b0 * (size_t)u;
-        a.upd = d_upd ? d_upd + b0 * (size_t)u * pitch : nullptr;
-        a.src = src_used && d_src ? d_src + b0 * (size_t)k * pitch : nullptr;
-        a.par = par_used && d_parity ? d_parity + b0 * (size_t)e * pitch : nullptr;
-        a.tab4 = (const uint4*)ctx->d_update;
-        a.tabc = (const uint32_t*)((const char*)ctx->d_update + kUpdTab4Bytes);
-        a.coef = (const uint8_t*)ctx->d_update + kUpdTabBytes;
-        a.status = d_status + b0;
-        if (n16 > 0) {
-            KTimer kt(ctx, "k_update_blocks", nb);
-            RS_HIP(ctx, launch_update_blocks(a, false, 0, n16, ctx->stream));
-        }
-        // the bytes the vector kernel leaves: all of them, the len % 16 tail,
-        // or none (the launch then only writes the statuses)
-        const long long first = n16 * 16, end = work ? (long long)len : 0;
-        if (n16 == 0 || first < end) {
-            KTimer kt(ctx, n16 > 0 ? "k_update_blocks(tail)" : "k_update_blocks(bytes)", nb);
-            RS_HIP(ctx, launch_update_blocks(a, true, first, first < end ? end : first, ctx->stream));
-        }
-    }
-    return RSGPU_OK;
-}
-
-// ---- degraded scrub ------------------------------------------------------------
-
-// The per-block tables of one slice (rs_kernels.h DegradedArgs) are bounded as
-// the computed parity is: a slice holds no more blocks than fit kDegTabBytes.
-constexpr size_t kDegTabBytes = 64u << 20;
-
-static int ensure_degraded(rsgpu_ctx* ctx, size_t bytes)
-{
-    if (ctx->degraded_bytes >= bytes)
-        return RSGPU_OK;
-    if (ctx->d_degraded) {
-        // every kernel that reads the old buffer is on the context's stream
-        RS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        RS_HIP(ctx, hipFree(ctx->d_degraded));
-        ctx->d_degraded = nullptr;
-        ctx->degraded_bytes = 0;
-    }
-    RS_HIP(ctx, hipMalloc(&ctx->d_degraded, bytes));
-    ctx->degraded_bytes = bytes;
-    return RSGPU_OK;
-}
-
-int rsgpu_scrub_degraded_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
-                                const unsigned char* d_src, const unsigned char* d_parity,
-                                const unsigned char* coef, int u, const unsigned char* d_lost, int flags,
-                                rsgpu_scrub_report* d_report)
-{
-    int rc = check_geom(ctx, k, e, len, pitch, blocks);
-    if (rc)
-        return rc;
-    if (!d_report || (uintptr_t)d_report % 8 != 0 || (flags & ~RSGPU_SCRUB_LOCATE) != 0 || u < 1 || u > 8 ||
-        !d_lost)
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_scrub_degraded_blocks: bad report pointer, flags, u or list");
-    const bool work = e > 0 && len > 0;
-    if (work && (!d_src || !d_parity))
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_scrub_degraded_blocks: null rows");
-    // Two nested slicings.  A group of blocks shares one prepare and one
-    // finalise: its tables fit kDegTabBytes, its blocks fit a grid.  Inside it
-    // a slice is what the scrub scratch holds of computed parity (the TWO_PASS
-    // rule): encode, then compare.
-    const size_t per_block = (size_t)e * pitch, stride = degraded_tab_stride(k, e);
-    const size_t group = std::max<size_t>(1, std::min({blocks, kMaxGridBlocks, kDegTabBytes / stride}));
-    const size_t slice = work ? std::max<size_t>(1, std::min(group, kScrubParityBytes / per_block)) : group;
-    rc = ensure_degraded(ctx, group * stride);
-    if (rc)
-        return rc;
-    if (work) {
-        rc = ensure_scrub(ctx, kScrubTabBytes + slice * per_block);
-        if (rc)
-            return rc;
-        // the v_perm tables of every coefficient value and the matrix, on the device
-        rc = update_tables(ctx, k, e, coef);
-        if (rc)
-            return rc;
-    }
-    uint8_t* calc = work ? (uint8_t*)ctx->d_scrub + kScrubTabBytes : nullptr;
-    const bool vec = pitch % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
-    const long long n16 = work && vec ? (long long)(len / 16) : 0;
-    for (size_t g0 = 0; g0 < blocks; g0 += group) {
-        const size_t ng = std::min(group, blocks - g0);
-        DegradedArgs a{};
-        a.k = k;
-        a.e = e;
-        a.u = u;
-        a.locate = (flags & RSGPU_SCRUB_LOCATE) ? 1 : 0;
-        a.work = work ? 1 : 0;
-        a.pitch = (long long)pitch;
-        a.len = (long long)len;
-        a.blocks = (long long)ng;
-        a.lost = d_lost + g0 * (size_t)u;
-        a.tab = (uint8_t*)ctx->d_degraded;
-        a.tab_stride = stride;
-        a.rest_bytes = degraded_rest_bytes(e);
-        a.report = d_report + g0;
-        if (work) {
-            a.coef = (const uint8_t*)ctx->d_update + kUpdTabBytes;
-            a.tab4 = (const uint4*)ctx->d_update;
-            a.tabc = (const uint32_t*)((const char*)ctx->d_update + kUpdTab4Bytes);
-        }
-        {
-            KTimer kt(ctx, "k_degraded_prepare", ng);
-            RS_HIP(ctx, launch_degraded_prepare(a, ctx->stream));
-        }
-        if (!work)
-            continue;  // the prepare has written every report
-        for (size_t s0 = 0; s0 < ng; s0 += slice) {
-            const size_t b0 = g0 + s0, nb = std::min(slice, ng - s0);
-            // the parity of the k source rows as they lie in memory, lost ones
-            // included: their contribution cancels in the reduced syndromes
-            rc = rsgpu_encode_blocks(ctx, k, e, len, pitch, nb, d_src + b0 * (size_t)k * pitch, calc, coef);
-            if (rc)
-                return rc;
-            DegradedArgs c = a;
-            c.blocks = (long long)nb;
-            c.tab = a.tab + s0 * stride;
-            c.report = a.report + s0;
-            c.calc = calc;
-            c.par = d_parity + b0 * per_block;
-            if (n16 > 0) {
-                KTimer kt(ctx, "k_degraded_compare", nb);
-                RS_HIP(ctx, launch_degraded_compare(c, false, 0, n16, ctx->stream));
-            }
-            if ((size_t)n16 * 16 < len) {
-                KTimer kt(ctx, n16 > 0 ? "k_degraded_compare(tail)" : "k_degraded_compare(bytes)", nb);
-                RS_HIP(ctx, launch_degraded_compare(c, true, n16 * 16, (long long)len, ctx->stream));
-            }
-        }
-        KTimer kt(ctx, "k_degraded_finalise", ng);
-        RS_HIP(ctx, launch_degraded_finalise(a, ctx->stream));
-    }
     return RSGPU_OK;
 }
 

@@ -69,26 +69,29 @@ struct rsgpu_ctx {
     void* d_code_stage = nullptr;
     size_t code_stage_bytes = 0;
     std::string err;
-    // grow-only device scratch for pointer tables / coefficient tables
-    void* d_scratch = nullptr;
-    size_t scratch_bytes = 0;
+    // A grow-only device buffer (rsgpu_internal.h ensure_device).  key: what
+    // its head holds, for the owners that cache tables there; cleared when
+    // the buffer is reallocated.
+    struct DevBuf {
+        void* p = nullptr;
+        size_t bytes = 0;
+        std::vector<uint8_t> key;
+    };
+    // pointer tables / coefficient tables of the encode and decode paths
+    DevBuf scratch;
     // parity scrub (rsgpu_scrub_blocks): the kernel choice, and the two-pass
-    // path's grow-only device buffer [ratio -> row table | e x k matrix |
-    // computed parity of a slice]; scrub_key = the (k, e, matrix) whose
-    // tables the buffer holds
+    // path's buffer [ratio -> row table | e x k matrix | computed parity of a
+    // slice]; key = the (k, e, matrix) whose tables it holds
     int scrub_kernel = RSGPU_SCRUB_AUTO;
-    void* d_scrub = nullptr;
-    size_t scrub_bytes = 0;
-    std::vector<uint8_t> scrub_key;
+    DevBuf scrub;
     // partial-stripe update (rsgpu_update_blocks): one fixed-size device
     // buffer [v_perm tables of the 256 coefficient values | e x k matrix];
     // update_key = the (k, e, matrix) it holds
     void* d_update = nullptr;
     std::vector<uint8_t> update_key;
-    // degraded scrub (rsgpu_scrub_degraded_blocks): grow-only device buffer
-    // of the per-block tables k_degraded_prepare writes for one slice
-    void* d_degraded = nullptr;
-    size_t degraded_bytes = 0;
+    // degraded scrub (rsgpu_scrub_degraded_blocks): the per-block tables
+    // k_degraded_prepare writes for one slice
+    DevBuf degraded;
     // pinned host staging for small uploads, guarded by an event
     void* h_stage = nullptr;
     size_t stage_bytes = 0;

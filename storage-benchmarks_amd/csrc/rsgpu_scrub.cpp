@@ -1,0 +1,536 @@
+// rsgpu_scrub.cpp -- the scrub family of the C ABI (include/rsgpu.h): parity
+// scrub, repair in place, partial-stripe update and degraded scrub.  Argument
+// checks and launch sequences; the kernels are rs_kernels.hip (two-pass
+// compare, finalise), rs_bitsliced.hip (fused), rs_update.hip, rs_degraded.hip.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "../../include/rsgpu.h"
+#include "gf256.h"
+#include "rs_kernels.h"
+#include "rsgpu_ctx.h"
+#include "rsgpu_internal.h"
+
+namespace {
+
+using namespace rsgpu;
+
+// the e x k parity matrix of a call: `coef`, or the gf_gen_rs_matrix rows
+std::vector<uint8_t> scrub_matrix(int k, int e, const unsigned char* coef)
+{
+    std::vector<uint8_t> c((size_t)e * k);
+    if (coef) {
+        std::memcpy(c.data(), coef, c.size());
+    } else {
+        std::vector<uint8_t> a((size_t)(k + e) * k);
+        rsgpu_gf_gen_rs_matrix(a.data(), k + e, k);
+        std::memcpy(c.data(), a.data() + (size_t)k * k, c.size());
+    }
+    return c;
+}
+
+// (k, e, matrix): what the device copy of a matrix's tables is kept under
+std::vector<uint8_t> matrix_key(int k, int e, const std::vector<uint8_t>& c)
+{
+    std::vector<uint8_t> key(8 + c.size());
+    std::memcpy(key.data(), &k, 4);
+    std::memcpy(key.data() + 4, &e, 4);
+    std::memcpy(key.data() + 8, c.data(), c.size());
+    return key;
+}
+
+// rsgpu.h's rule: e >= 2, no zero in rows 0 and 1, the ratios c[1][j] / c[0][j]
+// pairwise distinct.  tab (256 bytes, optional): ratio -> j, 255 for none.
+bool scrub_locatable(int k, int e, const uint8_t* c, uint8_t* tab)
+{
+    uint8_t t[256];
+    std::memset(t, 255, sizeof t);
+    bool ok = e >= 2 && k <= 255;
+    for (int j = 0; ok && j < k; ++j) {
+        const uint8_t c0 = c[j], c1 = c[(size_t)k + j];
+        if (!c0 || !c1) {
+            ok = false;
+            break;
+        }
+        const uint8_t ratio = hmul(c1, rsgpu_gf_inv(c0));
+        ok = t[ratio] == 255;
+        t[ratio] = (uint8_t)j;
+    }
+    if (ok && tab)
+        std::memcpy(tab, t, sizeof t);
+    return ok;
+}
+
+// the matrix of a call that names rows, and its ratio -> row table
+struct Locator {
+    std::vector<uint8_t> c;
+    uint8_t rowtab[256];
+};
+
+// ... or RSGPU_ERR_UNSUPPORTED with `msg` when the matrix is not locatable
+int locator(rsgpu_ctx* ctx, int k, int e, const unsigned char* coef, const char* msg, Locator& loc)
+{
+    if (e >= 2)
+        loc.c = scrub_matrix(k, e, coef);
+    if (e < 2 || !scrub_locatable(k, e, loc.c.data(), loc.rowtab))
+        return fail(ctx, RSGPU_ERR_UNSUPPORTED, msg);
+    return RSGPU_OK;
+}
+
+// the fused kernels of the compiled codes (k_rs_bs_scrub, k_rs_bs_repair) serve
+bool fused_eligible(const rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, const void* d_src,
+                    const void* d_parity, const unsigned char* coef)
+{
+    return ctx->scrub_kernel != RSGPU_SCRUB_TWO_PASS && !coef && rs_bitsliced_available(k, e) && len % 32 == 0 &&
+           len < (1ull << 32) && pitch % 16 == 0 && (uintptr_t)d_src % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
+}
+
+// Two-pass scratch (ctx->scrub): [rowtab 256 B | matrix e x k | pad to
+// kScrubTabBytes | computed parity of a slice].  The parity part is bounded: a
+// slice holds as many blocks as fit kScrubParityBytes (4 blocks of C3's 32 x
+// 1 MB parity; enough workgroups per launch to fill the device), one block
+// when a single block's parity is larger.
+constexpr size_t kScrubTabBytes = 16384;  // 256 + e k <= 256 + 125 * 125
+constexpr size_t kScrubParityBytes = 128u << 20;
+
+size_t parity_slice(size_t blocks, size_t per_block)
+{
+    return std::max<size_t>(1, std::min(blocks, kScrubParityBytes / per_block));
+}
+
+int grow_parity_scratch(rsgpu_ctx* ctx, size_t blocks, size_t per_block)
+{
+    return ensure_device(ctx, ctx->scrub, kScrubTabBytes + parity_slice(blocks, per_block) * per_block);
+}
+
+// The two-pass walk over blocks [first, first + count) of d_src: the scratch
+// grown, the tables of `loc` (when given) at its head, uploaded when it holds
+// another matrix's; then slice by slice the encode into the scratch and
+// compare(b0, nb, calc) on blocks [b0, b0 + nb) while their computed parity
+// `calc` is still there.
+template <class Compare>
+int two_pass(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t first, size_t count,
+             const uint8_t* d_src, const unsigned char* coef, const Locator* loc, Compare&& compare)
+{
+    const size_t per_block = (size_t)e * pitch, slice = parity_slice(count, per_block);
+    int rc = grow_parity_scratch(ctx, count, per_block);
+    std::vector<uint8_t> key;
+    if (!rc && loc && (key = matrix_key(k, e, loc->c)) != ctx->scrub.key) {
+        void* stage;
+        rc = get_stage(ctx, 256 + loc->c.size(), &stage);
+        if (rc)
+            return rc;
+        std::memcpy(stage, loc->rowtab, 256);
+        std::memcpy((char*)stage + 256, loc->c.data(), loc->c.size());
+        rc = upload(ctx, ctx->scrub.p, 256 + loc->c.size());
+        if (!rc)
+            ctx->scrub.key = std::move(key);
+    }
+    uint8_t* calc = (uint8_t*)ctx->scrub.p + kScrubTabBytes;
+    for (size_t b0 = first; !rc && b0 < first + count; b0 += slice) {
+        const size_t nb = std::min(slice, first + count - b0);
+        rc = rsgpu_encode_blocks(ctx, k, e, len, pitch, nb, d_src + b0 * k * pitch, calc, coef);
+        if (!rc)
+            rc = compare(b0, nb, calc);
+    }
+    return rc;
+}
+
+// what ScrubCmpArgs and RepairCmpArgs share, for nb blocks of a slice
+template <class A, class Fold>
+A cmp_args(const rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t nb, const uint8_t* calc,
+           decltype(A::par) par, Fold* fold)
+{
+    A a{};
+    a.calc = calc;
+    a.par = par;
+    a.pitch = (long long)pitch;
+    a.len = (long long)len;
+    a.blocks = (long long)nb;
+    a.k = k;
+    a.e = e;
+    a.rowtab = (const uint8_t*)ctx->scrub.p;
+    a.coef = a.rowtab + 256;
+    a.fold = fold;
+    return a;
+}
+
+// The launches of a kernel that comes as a vector and a byte variant, on nb
+// blocks: 16-byte columns [0, n16), then the bytes they leave up to `end` --
+// all of them, the tail, or none; with no vector launch the byte launch runs
+// even over an empty range (the update then only writes the statuses).
+// names: the records of {vector, byte tail, bytes alone}.
+template <class Launch>
+int launch_head_and_tail(rsgpu_ctx* ctx, const char* const (&names)[3], size_t nb, long long n16, long long end,
+                         Launch&& launch)
+{
+    if (n16 > 0) {
+        KTimer kt(ctx, names[0], nb);
+        RS_HIP(ctx, launch(false, 0, n16));
+    }
+    const long long first = n16 * 16;
+    if (n16 == 0 || first < end) {
+        KTimer kt(ctx, names[n16 > 0 ? 1 : 2], nb);
+        RS_HIP(ctx, launch(true, first, std::max(first, end)));
+    }
+    return RSGPU_OK;
+}
+
+constexpr const char* kUpdateNames[3] = {"k_update_blocks", "k_update_blocks(tail)", "k_update_blocks(bytes)"};
+constexpr const char* kDegradedNames[3] = {"k_degraded_compare", "k_degraded_compare(tail)",
+                                           "k_degraded_compare(bytes)"};
+
+// The update's device buffer: [tab4 256 x 16 B | tabc 256 x 4 B | matrix].
+constexpr size_t kUpdTab4Bytes = 256 * sizeof(uint4);
+constexpr size_t kUpdTabBytes = kUpdTab4Bytes + 256 * sizeof(uint32_t);
+constexpr size_t kUpdMatrixBytes = (size_t)RSGPU_MAX_SOURCES * RSGPU_MAX_SOURCES;
+
+// The tables (once per context) and the matrix (when it differs from the one
+// the buffer holds) go up on the stream, ahead of the kernel that reads them.
+int update_tables(rsgpu_ctx* ctx, int k, int e, const unsigned char* coef)
+{
+    const bool fresh = ctx->d_update == nullptr;
+    if (fresh) {
+        RS_HIP(ctx, hipMalloc(&ctx->d_update, kUpdTabBytes + kUpdMatrixBytes));
+        ctx->update_key.clear();
+    }
+    std::vector<uint8_t> c, key;
+    if (e > 0) {
+        c = scrub_matrix(k, e, coef);
+        key = matrix_key(k, e, c);
+    }
+    const bool matrix = e > 0 && key != ctx->update_key;
+    if (!fresh && !matrix)
+        return RSGPU_OK;
+    const size_t first = fresh ? 0 : kUpdTabBytes;
+    const size_t last = matrix ? kUpdTabBytes + c.size() : kUpdTabBytes;
+    void* stage;
+    int rc = get_stage(ctx, kUpdTabBytes + kUpdMatrixBytes, &stage);
+    if (rc)
+        return rc;
+    if (fresh) {
+        uint4* t4 = (uint4*)stage;
+        uint32_t* tc = (uint32_t*)((char*)stage + kUpdTab4Bytes);
+        for (int v = 0; v < 256; ++v) {
+            uint32_t t[5];
+            perm_tables((uint8_t)v, t);
+            t4[v] = make_uint4(t[0], t[1], t[2], t[3]);
+            tc[v] = t[4];
+        }
+    }
+    if (matrix)
+        std::memcpy((char*)stage + kUpdTabBytes, c.data(), c.size());
+    rc = upload(ctx, ctx->d_update, last - first, first, first);
+    if (rc)
+        return rc;
+    if (matrix)
+        ctx->update_key = std::move(key);
+    return RSGPU_OK;
+}
+
+bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return an > 0 && bn > 0 && a0 < b0 + bn && b0 < a0 + an;
+}
+
+// The per-block tables of one slice (rs_kernels.h DegradedArgs) are bounded as
+// the computed parity is: a slice holds no more blocks than fit kDegTabBytes.
+constexpr size_t kDegTabBytes = 64u << 20;
+
+}  // namespace
+
+extern "C" {
+
+int rsgpu_scrub_locatable(int k, int e, const unsigned char* coef)
+{
+    if (k <= 0 || e < 2 || k + e > RSGPU_MAX_SOURCES)
+        return 0;
+    const std::vector<uint8_t> c = scrub_matrix(k, e, coef);
+    return scrub_locatable(k, e, c.data(), nullptr) ? 1 : 0;
+}
+
+int rsgpu_set_scrub_kernel(rsgpu_ctx* ctx, int kernel)
+{
+    if (!ctx || kernel < RSGPU_SCRUB_AUTO || kernel > RSGPU_SCRUB_TWO_PASS)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_scrub_kernel: unknown kernel");
+    ctx->scrub_kernel = kernel;
+    return RSGPU_OK;
+}
+
+int rsgpu_scrub_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                       const unsigned char* d_src, const unsigned char* d_parity,
+                       const unsigned char* coef, int flags, rsgpu_scrub_report* d_report)
+{
+    int rc = check_geom(ctx, k, e, len, pitch, blocks);
+    if (rc)
+        return rc;
+    if (!d_report || (uintptr_t)d_report % 8 != 0 || (flags & ~RSGPU_SCRUB_LOCATE) != 0)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_scrub_blocks: bad report pointer or flags");
+    const bool locate = (flags & RSGPU_SCRUB_LOCATE) != 0;
+    const bool work = e > 0 && len > 0;
+    if (work && (!d_src || !d_parity))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_scrub_blocks: null rows");
+    Locator loc;
+    if (locate) {
+        rc = locator(ctx, k, e, coef,
+                     "rsgpu_scrub_blocks: RSGPU_SCRUB_LOCATE needs a locatable matrix (rsgpu_scrub_locatable)", loc);
+        if (rc)
+            return rc;
+    }
+    ScrubFold* fold = reinterpret_cast<ScrubFold*>(d_report);
+    RS_HIP(ctx, hipMemsetAsync(d_report, 0, blocks * sizeof(rsgpu_scrub_report), ctx->stream));
+    auto compare = [&](size_t b0, size_t nb, const uint8_t* calc) -> int {
+        ScrubCmpArgs a =
+            cmp_args<ScrubCmpArgs>(ctx, k, e, len, pitch, nb, calc, d_parity + b0 * e * pitch, fold + b0);
+        a.locate = locate ? 1 : 0;
+        KTimer kt(ctx, "k_scrub_compare", nb);
+        RS_HIP(ctx, launch_scrub_compare(a, ctx->stream));
+        return RSGPU_OK;
+    };
+    const bool fused = fused_eligible(ctx, k, e, len, pitch, d_src, d_parity, coef);
+    // block index in grid.y: larger batches as consecutive slices
+    for (size_t b0 = 0; work && b0 < blocks; b0 += kMaxGridBlocks) {
+        const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
+        if (!fused) {
+            rc = two_pass(ctx, k, e, len, pitch, b0, nb, d_src, coef, locate ? &loc : nullptr, compare);
+            if (rc)
+                return rc;
+            continue;
+        }
+        KTimer kt(ctx, "k_rs_bs_scrub", nb);
+        RS_HIP(ctx, launch_rs_bitsliced_scrub(k, e, d_src + b0 * k * pitch, d_parity + b0 * e * pitch,
+                                              (long long)pitch, (long long)len, (long long)nb, fold + b0,
+                                              locate ? 1 : 0, ctx->stream));
+    }
+    KTimer kt(ctx, "k_scrub_finalise", blocks);
+    RS_HIP(ctx, launch_scrub_finalise(d_report, (long long)blocks, locate ? 1 : 0, ctx->stream));
+    return RSGPU_OK;
+}
+
+int rsgpu_repair_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                        unsigned char* d_src, unsigned char* d_parity, const unsigned char* coef, int mode,
+                        rsgpu_repair_report* d_report)
+{
+    int rc = check_geom(ctx, k, e, len, pitch, blocks);
+    if (rc)
+        return rc;
+    if (!d_report || (uintptr_t)d_report % 8 != 0 ||
+        (mode != RSGPU_REPAIR_ONE_ROW && mode != RSGPU_REPAIR_COLUMNS))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_repair_blocks: bad report pointer or mode");
+    const bool work = e > 0 && len > 0;
+    if (work && (!d_src || !d_parity))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_repair_blocks: null rows");
+    Locator loc;
+    if (e > 0) {  // e == 0: no parity, nothing can be bad
+        rc = locator(ctx, k, e, coef, "rsgpu_repair_blocks: needs a locatable matrix (rsgpu_scrub_locatable)", loc);
+        if (rc)
+            return rc;
+        if (mode == RSGPU_REPAIR_COLUMNS && e < 3)
+            return fail(ctx, RSGPU_ERR_UNSUPPORTED, "rsgpu_repair_blocks: RSGPU_REPAIR_COLUMNS needs e >= 3");
+    }
+    RepairFold* fold = reinterpret_cast<RepairFold*>(d_report);
+    RS_HIP(ctx, hipMemsetAsync(d_report, 0, blocks * sizeof(rsgpu_repair_report), ctx->stream));
+    auto finalise = [&](size_t b0, size_t nb) -> int {
+        KTimer kt(ctx, "k_repair_finalise", nb);
+        RS_HIP(ctx, launch_repair_finalise(fold + b0, (long long)nb, mode, ctx->stream));
+        return RSGPU_OK;
+    };
+    if (!work)
+        return finalise(0, blocks);
+    const bool fused = fused_eligible(ctx, k, e, len, pitch, d_src, d_parity, coef);
+    const int first_mode = mode == RSGPU_REPAIR_COLUMNS ? kRepairColumns : kRepairLocate;
+    // A slice of the scratch.  COLUMNS: the correcting compare; ONE_ROW: the
+    // compare that only folds, the finalise of the slice's reports, and the
+    // gated correcting compare, while the slice's computed parity is still in
+    // the scratch.
+    auto compare = [&](size_t b0, size_t nb, const uint8_t* calc) -> int {
+        RepairCmpArgs a =
+            cmp_args<RepairCmpArgs>(ctx, k, e, len, pitch, nb, calc, d_parity + b0 * e * pitch, fold + b0);
+        a.src = d_src + b0 * k * pitch;
+        a.mode = first_mode;
+        {
+            KTimer kt(ctx, "k_repair_compare", nb);
+            RS_HIP(ctx, launch_repair_compare(a, ctx->stream));
+        }
+        if (mode != RSGPU_REPAIR_ONE_ROW)
+            return RSGPU_OK;
+        const int frc = finalise(b0, nb);
+        if (frc)
+            return frc;
+        a.mode = kRepairGated;
+        KTimer kt(ctx, "k_repair_compare_gated", nb);
+        RS_HIP(ctx, launch_repair_compare(a, ctx->stream));
+        return RSGPU_OK;
+    };
+    // block index in grid.y: larger batches as consecutive slices, each
+    // complete (located, finalised, corrected) before the next
+    for (size_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks) {
+        const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
+        uint8_t* src = d_src + b0 * k * pitch;
+        uint8_t* par = d_parity + b0 * e * pitch;
+        if (!fused) {
+            rc = two_pass(ctx, k, e, len, pitch, b0, nb, d_src, coef, &loc, compare);
+            if (rc)
+                return rc;
+            if (mode == RSGPU_REPAIR_ONE_ROW)
+                continue;  // finalised slice by slice
+        } else {
+            KTimer kt(ctx, "k_rs_bs_repair", nb);
+            RS_HIP(ctx, launch_rs_bitsliced_repair(k, e, src, par, (long long)pitch, (long long)len, (long long)nb,
+                                                   fold + b0, first_mode, ctx->stream));
+        }
+        rc = finalise(b0, nb);
+        if (rc)
+            return rc;
+        if (fused && mode == RSGPU_REPAIR_ONE_ROW) {
+            KTimer kt(ctx, "k_rs_bs_repair_gated", nb);
+            RS_HIP(ctx, launch_rs_bitsliced_repair(k, e, src, par, (long long)pitch, (long long)len, (long long)nb,
+                                                   fold + b0, kRepairGated, ctx->stream));
+        }
+    }
+    return RSGPU_OK;
+}
+
+int rsgpu_update_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks, int u,
+                        const unsigned char* d_cols, const unsigned char* d_upd, unsigned char* d_src,
+                        unsigned char* d_parity, const unsigned char* coef, int flags, int* d_status)
+{
+    int rc = check_geom(ctx, k, e, len, pitch, blocks);
+    if (rc)
+        return rc;
+    if (u < 1 || u > k || (flags & ~RSGPU_UPDATE_DELTA) != 0 || !d_cols || !d_status)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_update_blocks: bad u, flags, list or status pointer");
+    const bool delta = (flags & RSGPU_UPDATE_DELTA) != 0;
+    const bool src_used = !delta, par_used = e > 0;
+    if (len > 0 && (((src_used || par_used) && !d_upd) || (src_used && !d_src) || (par_used && !d_parity)))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_update_blocks: null rows");
+    // rows i of a buffer of R rows per block end at ((blocks R - 1) pitch + len)
+    auto span = [&](size_t rows) { return len == 0 ? (size_t)0 : (blocks * rows - 1) * pitch + len; };
+    if ((src_used && ranges_overlap(d_upd, span((size_t)u), d_src, span((size_t)k))) ||
+        (par_used && ranges_overlap(d_upd, span((size_t)u), d_parity, span((size_t)e))))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_update_blocks: d_upd overlaps d_src or d_parity");
+    rc = update_tables(ctx, k, e, coef);
+    if (rc)
+        return rc;
+    const bool work = len > 0 && (src_used || par_used);
+    const bool vec = pitch % 16 == 0 && (uintptr_t)d_upd % 16 == 0 && (!src_used || (uintptr_t)d_src % 16 == 0) &&
+                     (!par_used || (uintptr_t)d_parity % 16 == 0);
+    const long long n16 = work && vec ? (long long)(len / 16) : 0;
+    // block index in grid.y: larger batches as consecutive slices
+    for (size_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks) {
+        const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
+        UpdateArgs a{};
+        a.k = k;
+        a.e = e;
+        a.u = u;
+        a.delta = delta ? 1 : 0;
+        a.pitch = (long long)pitch;
+        a.blocks = (long long)nb;
+        a.cols = d_cols + b0 * (size_t)u;
+        a.upd = d_upd ? d_upd + b0 * (size_t)u * pitch : nullptr;
+        a.src = src_used && d_src ? d_src + b0 * (size_t)k * pitch : nullptr;
+        a.par = par_used && d_parity ? d_parity + b0 * (size_t)e * pitch : nullptr;
+        a.tab4 = (const uint4*)ctx->d_update;
+        a.tabc = (const uint32_t*)((const char*)ctx->d_update + kUpdTab4Bytes);
+        a.coef = (const uint8_t*)ctx->d_update + kUpdTabBytes;
+        a.status = d_status + b0;
+        auto launch = [&](bool bytes, long long c0, long long c1) {
+            return launch_update_blocks(a, bytes, c0, c1, ctx->stream);
+        };
+        rc = launch_head_and_tail(ctx, kUpdateNames, nb, n16, work ? (long long)len : 0, launch);
+        if (rc)
+            return rc;
+    }
+    return RSGPU_OK;
+}
+
+int rsgpu_scrub_degraded_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                                const unsigned char* d_src, const unsigned char* d_parity,
+                                const unsigned char* coef, int u, const unsigned char* d_lost, int flags,
+                                rsgpu_scrub_report* d_report)
+{
+    int rc = check_geom(ctx, k, e, len, pitch, blocks);
+    if (rc)
+        return rc;
+    if (!d_report || (uintptr_t)d_report % 8 != 0 || (flags & ~RSGPU_SCRUB_LOCATE) != 0 || u < 1 || u > 8 ||
+        !d_lost)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_scrub_degraded_blocks: bad report pointer, flags, u or list");
+    const bool work = e > 0 && len > 0;
+    if (work && (!d_src || !d_parity))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_scrub_degraded_blocks: null rows");
+    // Two nested slicings.  A group of blocks shares one prepare and one
+    // finalise: its tables fit kDegTabBytes, its blocks fit a grid.  Inside it
+    // a slice is what the scrub scratch holds of computed parity (the TWO_PASS
+    // rule): encode, then compare.
+    const size_t per_block = (size_t)e * pitch, stride = degraded_tab_stride(k, e);
+    const size_t group = std::max<size_t>(1, std::min({blocks, kMaxGridBlocks, kDegTabBytes / stride}));
+    rc = ensure_device(ctx, ctx->degraded, group * stride);
+    if (rc)
+        return rc;
+    if (work) {
+        // the scratch of the largest group now, so that no walk below grows it
+        rc = grow_parity_scratch(ctx, group, per_block);
+        if (rc)
+            return rc;
+        // the v_perm tables of every coefficient value and the matrix, on the device
+        rc = update_tables(ctx, k, e, coef);
+        if (rc)
+            return rc;
+    }
+    const bool vec = pitch % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
+    const long long n16 = work && vec ? (long long)(len / 16) : 0;
+    for (size_t g0 = 0; g0 < blocks; g0 += group) {
+        const size_t ng = std::min(group, blocks - g0);
+        DegradedArgs a{};
+        a.k = k;
+        a.e = e;
+        a.u = u;
+        a.locate = (flags & RSGPU_SCRUB_LOCATE) ? 1 : 0;
+        a.work = work ? 1 : 0;
+        a.pitch = (long long)pitch;
+        a.len = (long long)len;
+        a.blocks = (long long)ng;
+        a.lost = d_lost + g0 * (size_t)u;
+        a.tab = (uint8_t*)ctx->degraded.p;
+        a.tab_stride = stride;
+        a.rest_bytes = degraded_rest_bytes(e);
+        a.report = d_report + g0;
+        if (work) {
+            a.coef = (const uint8_t*)ctx->d_update + kUpdTabBytes;
+            a.tab4 = (const uint4*)ctx->d_update;
+            a.tabc = (const uint32_t*)((const char*)ctx->d_update + kUpdTab4Bytes);
+        }
+        {
+            KTimer kt(ctx, "k_degraded_prepare", ng);
+            RS_HIP(ctx, launch_degraded_prepare(a, ctx->stream));
+        }
+        if (!work)
+            continue;  // the prepare has written every report
+        // the parity of the k source rows as they lie in memory, lost ones
+        // included: their contribution cancels in the reduced syndromes
+        auto compare = [&](size_t b0, size_t nb, const uint8_t* calc) {
+            DegradedArgs c = a;
+            c.blocks = (long long)nb;
+            c.tab = a.tab + (b0 - g0) * stride;
+            c.report = d_report + b0;
+            c.calc = calc;
+            c.par = d_parity + b0 * per_block;
+            auto launch = [&](bool bytes, long long c0, long long c1) {
+                return launch_degraded_compare(c, bytes, c0, c1, ctx->stream);
+            };
+            return launch_head_and_tail(ctx, kDegradedNames, nb, n16, (long long)len, launch);
+        };
+        rc = two_pass(ctx, k, e, len, pitch, g0, ng, d_src, coef, nullptr, compare);
+        if (rc)
+            return rc;
+        KTimer kt(ctx, "k_degraded_finalise", ng);
+        RS_HIP(ctx, launch_degraded_finalise(a, ctx->stream));
+    }
+    return RSGPU_OK;
+}
+
+}  // extern "C"

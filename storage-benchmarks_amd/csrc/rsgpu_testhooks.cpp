@@ -24,8 +24,6 @@ using namespace rsgpu;
 
 namespace {
 
-constexpr size_t kMaxGridBlocks = 65535;
-
 // One pass's code in the two- / four-wave layout (rs_jit.h Wide<R, CS>):
 // rows row_base .. row_base + rows - 1 of the e x k matrix coef, from
 // Wide::code_word: wave w, chunk ch at (w nch + ch) chunk_stride from o64;

@@ -299,6 +299,44 @@ def test_more_blocks_than_a_grid_holds(ctx, kernel, mode):
     assert blk.scrub_is_clean(kernel)
 
 
+@pytest.mark.parametrize("mode", MODES)
+def test_slices(ctx, mode):
+    """(2, 8) with 1 MiB rows through the two-pass path: 8 MiB of parity per
+    block, so the 128 MiB scratch holds 16 blocks and 17 blocks run as two
+    slices; one damaged row in the last block of the first slice, another in
+    the only block of the second.  The model runs on the damaged columns and a
+    few others (the full rows are consistent by construction: encode_blocks,
+    tested on its own); the rows come back as they were before the damage."""
+    k, e, L, B = 2, 8, 1 << 20, 17
+    assert rsgpu.scrub_locatable(k, e)
+    blk = Blocks(ctx, k, e, L, B, pitch=L)
+    for b, row, col, x in [(15, 1, 0, 0x10), (15, 1, L - 1, 0xEE), (16, k + 3, 12345, 0x02), (16, k + 3, 777, 0x03)]:
+        blk.xor(b, row, col, x)
+    assert not blk.equals(blk.pristine)
+    cols = torch.tensor([0, 1, 777, 12345, L - 2, L - 1], device=blk.src.device)
+    hs = blk.src.view(B, k, L)[:, :, cols].cpu().numpy()
+    hp = blk.par.view(B, e, L)[:, :, cols].cpu().numpy()
+    fixed = [rm.repair(blk.c, hs[b], hp[b], mode) for b in range(B)]
+    want = [f[2] for f in fixed]
+    assert want == [CLEAN] * 15 + [(2, 2, rm.REPAIRED, 1), (2, 2, rm.REPAIRED, k + 3)]
+    # the model's rows are the undamaged ones
+    ps = blk.pristine[0].view(B, k, L)[:, :, cols].cpu().numpy()
+    pp = blk.pristine[1].view(B, e, L)[:, :, cols].cpu().numpy()
+    assert all((f[0] == ps[b]).all() and (f[1] == pp[b]).all() for b, f in enumerate(fixed))
+    ctx.timing_enable(True)
+    try:
+        run(blk, "two_pass", mode, want, blk.pristine)
+        slices = [(n, nb) for n, _, nb in ctx.timing_read() if n.startswith("k_repair_compare")]
+    finally:
+        ctx.timing_enable(False)
+    if mode == "one_row":
+        assert slices == [("k_repair_compare", 16), ("k_repair_compare_gated", 16),
+                          ("k_repair_compare", 1), ("k_repair_compare_gated", 1)]
+    else:
+        assert slices == [("k_repair_compare", 16), ("k_repair_compare", 1)]
+    assert blk.scrub_is_clean("two_pass")
+
+
 @pytest.mark.parametrize("kernel", KERNELS)
 def test_refusals(ctx, kernel):
     """RSGPU_ERR_UNSUPPORTED: nothing runs, the report keeps its poison and

@@ -278,6 +278,35 @@ def test_more_blocks_than_a_grid_holds(ctx, kernel):
     assert tuple(int(v) for v in rep[65537]) == (1, sm.ONE_ROW, 6)
 
 
+def test_slices(ctx):
+    """(2, 8) with 1 MiB rows through the two-pass path: 8 MiB of parity per
+    block, so the 128 MiB scratch holds 16 blocks and 17 blocks run as two
+    slices; one damaged row in the last block of the first slice, another in
+    the only block of the second.  The model runs on the damaged columns and a
+    few others (the full rows are consistent by construction: encode_blocks,
+    tested on its own)."""
+    k, e, L, B = 2, 8, 1 << 20, 17
+    assert rsgpu.scrub_locatable(k, e)
+    blk = Blocks(ctx, k, e, L, B, pitch=L)
+    for b, row, col, x in [(15, 1, 0, 0x10), (15, 1, L - 1, 0xEE), (16, k + 3, 12345, 0x02), (16, k + 3, 777, 0x03)]:
+        blk.xor(b, row, col, x)
+    cols = torch.tensor([0, 1, 777, 12345, L - 2, L - 1], device=blk.src.device)
+    hs = blk.src.view(B, k, L)[:, :, cols].cpu().numpy()
+    hp = blk.par.view(B, e, L)[:, :, cols].cpu().numpy()
+    for locate in (True, False):
+        want = [sm.scrub(blk.c, hs[b], hp[b], locate) for b in range(B)]
+        assert want[:15] == [CLEAN] * 15
+        assert want[15:] == ([(2, sm.ONE_ROW, 1), (2, sm.ONE_ROW, k + 3)] if locate else [(2, sm.DAMAGED, -1)] * 2)
+        ctx.timing_enable(True)
+        try:
+            rep = blk.scrub("two_pass", locate=locate)
+            slices = [nb for n, _, nb in ctx.timing_read() if n == "k_scrub_compare"]
+        finally:
+            ctx.timing_enable(False)
+        same(rep, want)
+        assert slices == [16, 1]
+
+
 def test_path_check(ctx):
     blk = Blocks(ctx, 64, 32, 4096, 2)
     seen = {}
