@@ -344,7 +344,8 @@ int rsgpu_set_scrub_kernel(rsgpu_ctx *ctx, int kernel);
  * healthy parity row.  This call answers, BEFORE anything is rebuilt, whether
  * the survivors are consistent, and with >= 2 spare parity rows which one
  * surviving row is not; the caller adds that row to the erasure list and
- * decodes with the calls above.  Nothing is decoded and no row is written.
+ * decodes with the calls above, or lets rsgpu_rebuild_blocks below do both on
+ * the device.  Nothing is decoded and no row is written.
  *
  * Per byte column of a block with lost set L (n rows, n <= e):
  *   consistent  some choice of bytes for the rows in L makes all e syndromes
@@ -414,6 +415,99 @@ int rsgpu_scrub_degraded_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t
                                 const unsigned char *d_parity, const unsigned char *coef,
                                 int u, const unsigned char *d_lost, int flags,
                                 rsgpu_scrub_report *d_report);
+
+/* ---- rebuild in place of known-lost rows, optionally checked -------------- */
+
+/* The step after the degraded scrub: the rows a block's list names are
+ * rebuilt where they belong, lost parity rows included, batched and on the
+ * stream.  Lists may hold a different number of rows in every block, which
+ * rsgpu_decode_general (one nerrs for the batch, a separate d_out) does not
+ * take.  With RSGPU_REBUILD_CHECK the degraded scrub runs first and its
+ * verdict decides per block, on the device and with no host decision in
+ * between, what is written: a silently bad survivor is rebuilt with the lost
+ * rows instead of being sealed into them.
+ *
+ * Layout, `coef` and d_lost exactly as rsgpu_scrub_degraded_blocks: [blocks][u]
+ * bytes, rows in [0, k + e) strictly ascending, then RSGPU_LOST_NONE; n may
+ * differ from block to block.  Any len, any pitch >= len, any alignment.  u is
+ * in [1, 8] without RSGPU_REBUILD_CHECK and in [1, 7] with it: the located row
+ * may join the list, and a lane holds at most 8 output rows.  d_report
+ * [blocks] is the 16-byte rsgpu_scrub_report, DEVICE memory, 8-byte aligned,
+ * overwritten by every call.
+ *
+ * Rebuilt, for a block with list L and D the lost data rows of L: the pivot
+ * rows Q are the surviving parity rows, walked in ascending order, that each
+ * raise the rank of c[Q][D]; the lost data bytes are the unique solution that
+ * zeroes the syndromes of the rows in Q; every lost parity row is the encode
+ * of the completed data.  With consistent survivors the result is the
+ * original block and does not depend on Q.  With inconsistent survivors it is
+ * defined by the greedy Q, for the gf_gen_rs_matrix and gf_gen_cauchy1_matrix
+ * codes the first |D| surviving parity rows, and then equals byte for byte
+ * what rsgpu_decode_general (ISA-L's gf_gen_decode_matrix path) recovers for
+ * the same list.
+ *
+ * Status per block, the first that applies:
+ *   BAD_LIST    a malformed list or n > e, as in the degraded scrub; nothing
+ *               of the block is read or written by the rebuild
+ *   BAD_MATRIX  the surviving parity rows do not determine D, judged on the
+ *               list as it will be rebuilt and also when n == e (where the
+ *               degraded scrub says UNCHECKED without looking at the matrix);
+ *               nothing is written
+ *   without RSGPU_REBUILD_CHECK: CLEAN, bad_columns 0, row -1, every listed
+ *               row rebuilt (n == 0 writes nothing)
+ *   with RSGPU_REBUILD_CHECK: the report is what rsgpu_scrub_degraded_blocks
+ *               with RSGPU_SCRUB_LOCATE reports for the block as it was before
+ *               the call, and
+ *     CLEAN      the listed rows are rebuilt
+ *     UNCHECKED  (n == e) the listed rows are rebuilt on trust; the status
+ *                tells the caller so
+ *     ONE_ROW    `row` joins the list and L + {row} is rebuilt: all len bytes
+ *                of that row are rewritten, in its consistent columns with the
+ *                value they had
+ *     DAMAGED    nothing is written
+ * A located row can always join the list: a row that explains a column has a
+ * non-zero reduced column, so the surviving parity rows still determine the
+ * extended D.  As the scrub's, ONE_ROW is the most likely explanation, not a
+ * proof: with e - n - 1 or more damaged survivors in one column the checked
+ * rebuild can write a consistent but wrong block.
+ *
+ * e == 0 or len == 0: every well-formed list is CLEAN and nothing is written;
+ * a malformed list is still BAD_LIST.  Null pointers, a misaligned report, u
+ * out of range for the mode or unknown flag bits: RSGPU_ERR_ARG, nothing is
+ * enqueued and the report is untouched.  Enqueued on the context's stream, no
+ * synchronisation; more than 65535 blocks run as consecutive slices.  Listed
+ * rows are never read without RSGPU_REBUILD_CHECK; with it only the scrub's
+ * encode pass reads the lost source rows, and they influence nothing.  Never
+ * written: surviving rows (other than a located row), bytes in [len, pitch),
+ * and the lists.
+ *
+ * Cost: k_rebuild_prepare (one wave per block: the pivots, the inverse and
+ * the block's k x 8 matrix of factors), then k_rebuild_blocks, ONE walk over k
+ * surviving rows per block -- the surviving data rows and the |D| pivot parity
+ * rows -- that writes the listed rows: (k + n) rows of traffic per block, no
+ * encode into scratch.  RSGPU_REBUILD_CHECK adds the degraded scrub in front
+ * (its cost above).  The vector path needs pitch % 16 == 0 and 16-byte
+ * aligned d_src and d_parity; other layouts run a byte kernel.  Measured at
+ * (64, 32), 1 MB rows, 1024 blocks on one MI355X (profiles/rebuild, DESIGN.md
+ * 3.8; the device-to-device copy of the same bytes ran at 5.04 TB/s): one lost
+ * row per block 11.8 ms, two 12.8 ms, four 14.5 ms -- the bytes at the copy's
+ * rate within 5 % -- and eight 22.8 ms, 1.56 of its bytes: with 8 outputs per
+ * lane the kernel is bound by its arithmetic (172 instructions per 16-byte
+ * column and source).  rsgpu_decode_general with the same uniform lists took
+ * 11.9 / 12.2 / 13.2 / 15.5 ms: equal at one row, 5 % and 9 % faster at two
+ * and four, 1.48 x faster at eight.  A caller whose blocks ALL have many (7,
+ * 8) lost rows and whose survivors are trusted is better served by
+ * rsgpu_decode_general plus a copy of the rows back; this call is for lists
+ * that differ from block to block, for rows that should come back in place,
+ * and for the check.  Checked, with clean survivors: 46.8 ms (n = 1), 51.2 ms
+ * (n = 4), 58.5 ms (n = 7), the degraded scrub alone being 34.9 / 36.5 / 38.0
+ * ms.  Not built: host-resident blocks, a bit-sliced or generated-code form
+ * for many lost rows per block, and more than one located row per block. */
+#define RSGPU_REBUILD_CHECK 1 /* flags: scrub the survivors first, let the verdict decide */
+int rsgpu_rebuild_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                         unsigned char *d_src, unsigned char *d_parity,
+                         const unsigned char *coef, int u, const unsigned char *d_lost,
+                         int flags, rsgpu_scrub_report *d_report);
 
 /* ---- repair in place of what the scrub locates ---------------------------- */
 

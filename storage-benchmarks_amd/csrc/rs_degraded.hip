@@ -31,6 +31,7 @@
 #include "gf256.h"
 #include "rs_kernels.h"
 #include "rs_lane.h"
+#include "rs_pivots.h"
 
 namespace rsgpu {
 
@@ -38,17 +39,6 @@ namespace {
 
 constexpr int kDegThreads = 256;
 constexpr int kRestAhead = 4;  // rest rows (stored and computed) loaded together
-
-// a^-1 = a^254
-__device__ uint8_t deg_inv(uint8_t a)
-{
-    uint8_t r = 1, s = a;
-    for (int bit = 1; bit < 8; ++bit) {  // 254 = 0b11111110
-        s = gf_mul_slow(s, s);
-        r = gf_mul_slow(r, s);
-    }
-    return r;
-}
 
 // ---------------------------------------------------------------------------
 // k_degraded_prepare: one wave per block.  Lane 0 validates the list, splits
@@ -60,14 +50,13 @@ __device__ uint8_t deg_inv(uint8_t a)
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_degraded_prepare(DegradedArgs a)
 {
-    __shared__ uint8_t lost[256];    // per row of [0, k + e): 1 when listed
-    __shared__ uint8_t dl[8], ql[8]; // D (data rows), Q (parity indices)
-    __shared__ uint8_t restl[256];   // rest parity indices, ascending
-    __shared__ uint8_t basis[8][8];  // echelon form of the rows kept so far
-    __shared__ uint8_t bpiv[8];      // pivot column of each basis row
-    __shared__ uint8_t am[8][8], inv[8][8];
-    __shared__ uint8_t rl[256 * 8];  // R [nrest][8]
+    __shared__ PivotWork w;         // the lost rows, D, Q and (c[Q][D])^-1 (rs_pivots.h)
+    __shared__ uint8_t restl[256];  // rest parity indices, ascending
+    __shared__ uint8_t rl[256 * 8]; // R [nrest][8]
     __shared__ int sh_state, sh_nd, sh_nrest;
+    uint8_t (&lost)[256] = w.lost;
+    uint8_t (&dl)[8] = w.dl, (&ql)[8] = w.ql;
+    uint8_t (&inv)[8][8] = w.inv;
 
     const long long b = blockIdx.x;
     const int lane = threadIdx.x;
@@ -81,115 +70,26 @@ __global__ __launch_bounds__(64) void k_degraded_prepare(DegradedArgs a)
     __syncthreads();
 
     if (lane == 0) {
-        int n = 0, prev = -1, nd = 0;
-        bool ok = true, none = false;
-        for (int i = 0; i < a.u; ++i) {
-            const int j = list[i];
-            if (j == RSGPU_LOST_NONE) {
-                none = true;
-            } else {
-                ok = ok && !none && j < m && j > prev;
-                prev = j;
-                ++n;
-            }
-        }
-        ok = ok && n <= e;
+        const int n = lost_list_rows(list, a.u, m, e);
+        int nd = 0;
         int state = kDegRun;
-        if (!ok) {
+        if (n < 0) {
             state = RSGPU_SCRUB_BAD_LIST;
         } else if (!a.work) {
             state = kDegClean;
         } else if (n == e) {
             state = RSGPU_SCRUB_UNCHECKED;
         } else {
-            for (int i = 0; i < n; ++i) {
-                const int j = list[i];
-                lost[j] = 1;
-                if (j < k)
-                    dl[nd++] = (uint8_t)j;
-            }
-            // greedy pivots: reduce each surviving parity row's c[p][D] by the
-            // basis; what is left non-zero raises the rank
-            int nq = 0;
-            for (int p = 0; p < e && nq < nd; ++p) {
-                if (lost[k + p])
-                    continue;
-                uint8_t v[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    v[i] = i < nd ? a.coef[(size_t)p * k + dl[i < nd ? i : 0]] : 0;
-                for (int q = 0; q < nq; ++q) {
-                    uint8_t f = 0;
-#pragma unroll
-                    for (int i = 0; i < 8; ++i)
-                        f = i == bpiv[q] ? v[i] : f;
-                    if (f) {
-#pragma unroll
-                        for (int i = 0; i < 8; ++i)
-                            v[i] ^= gf_mul_slow(f, basis[q][i]);
-                    }
-                }
-                int piv = -1;
-#pragma unroll
-                for (int i = 7; i >= 0; --i)
-                    piv = v[i] ? i : piv;
-                if (piv < 0)
-                    continue;
-                uint8_t lead = 0;
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    lead = i == piv ? v[i] : lead;
-                const uint8_t li = deg_inv(lead);
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-                    basis[nq][i] = gf_mul_slow(li, v[i]);
-                bpiv[nq] = (uint8_t)piv;
-                ql[nq++] = (uint8_t)p;
-            }
-            if (nq < nd) {
+            nd = lost_pivots(w, list, n, a.coef, k, e);
+            if (nd < 0) {
                 state = RSGPU_SCRUB_BAD_MATRIX;
             } else {
-                // (c[Q][D])^-1 by Gauss-Jordan; the matrix has full rank
-                for (int i = 0; i < nd; ++i)
-                    for (int j = 0; j < nd; ++j) {
-                        am[i][j] = a.coef[(size_t)ql[i] * k + dl[j]];
-                        inv[i][j] = i == j;
-                    }
-                for (int col = 0; col < nd; ++col) {
-                    int pr = col;
-                    while (pr < nd && am[pr][col] == 0)
-                        ++pr;
-                    if (pr >= nd)
-                        break;  // cannot happen for a full-rank matrix
-                    if (pr != col)
-                        for (int j = 0; j < nd; ++j) {
-                            const uint8_t x = am[pr][j], y = inv[pr][j];
-                            am[pr][j] = am[col][j];
-                            inv[pr][j] = inv[col][j];
-                            am[col][j] = x;
-                            inv[col][j] = y;
-                        }
-                    const uint8_t li = deg_inv(am[col][col]);
-                    for (int j = 0; j < nd; ++j) {
-                        am[col][j] = gf_mul_slow(li, am[col][j]);
-                        inv[col][j] = gf_mul_slow(li, inv[col][j]);
-                    }
-                    for (int r = 0; r < nd; ++r) {
-                        const uint8_t f = am[r][col];
-                        if (r == col || f == 0)
-                            continue;
-                        for (int j = 0; j < nd; ++j) {
-                            am[r][j] ^= gf_mul_slow(f, am[col][j]);
-                            inv[r][j] ^= gf_mul_slow(f, inv[col][j]);
-                        }
-                    }
-                }
                 // the rest: surviving parity rows that are no pivot
                 int nrest = 0, qi = 0;
                 for (int p = 0; p < e; ++p) {
                     if (lost[k + p])
                         continue;
-                    if (qi < nq && ql[qi] == p) {
+                    if (qi < nd && ql[qi] == p) {
                         ++qi;
                         continue;
                     }

@@ -388,4 +388,43 @@ hipError_t launch_degraded_compare(const DegradedArgs& a, bool bytes, long long 
                                    hipStream_t st);
 hipError_t launch_degraded_finalise(const DegradedArgs& a, hipStream_t st);
 
+// Rebuild in place (rsgpu_rebuild_blocks, rs_rebuild.hip): the listed rows of
+// a block, and with `check` the one row its degraded report names, written
+// back as fixed linear combinations of k surviving rows: the surviving data
+// rows and the |D| pivot parity rows.  k_rebuild_prepare writes one table per
+// block,
+//   [RebuildHdr | sources: rebuild_src_bytes(k) | M: k x 8]
+// at rebuild_tab_stride(k): the k source rows (indices in [0, k + e)), the
+// rows to write, and M[s][o] = the factor of source s in output o.  state !=
+// kRebRun: nothing of the block is written, and its report is final.
+constexpr int kRebRun = 0;
+constexpr int kRebStop = 1;
+struct RebuildHdr {
+    int state;
+    uint8_t nout, pad[3];
+    uint8_t out[8];  // rows in [0, k + e) to write, ascending
+};
+struct RebuildArgs {
+    int k, e, u;
+    int check;  // non-zero: report holds the degraded scrub's verdict (with locate) of every block
+    int work;   // 0: e == 0 or len == 0, only the lists are judged
+    long long pitch, len, blocks;
+    const uint8_t* lost;   // [B][u]
+    const uint8_t* coef;   // device e x k matrix
+    uint8_t* src;          // [B][k] rows
+    uint8_t* par;          // [B][e] rows
+    uint8_t* tab;          // [B] tables at tab_stride
+    size_t tab_stride, src_bytes;
+    int g;                 // outputs a lane holds: 1, 2, 4 or 8, >= any block's
+    const uint4* tab4;     // device [256]: perm_tables words 0-3 of every coefficient value
+    const uint32_t* tabc;  // device [256]: perm_tables word 4
+    ::rsgpu_scrub_report* report;  // [B]
+};
+size_t rebuild_src_bytes(int k);
+size_t rebuild_tab_stride(int k);
+hipError_t launch_rebuild_prepare(const RebuildArgs& a, hipStream_t st);
+// bytes == false: columns [col0, col1) are 16-byte units of 16-byte aligned
+// rows; bytes == true: byte columns, any alignment
+hipError_t launch_rebuild_blocks(const RebuildArgs& a, bool bytes, long long col0, long long col1, hipStream_t st);
+
 }  // namespace rsgpu

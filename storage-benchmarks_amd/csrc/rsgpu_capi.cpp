@@ -1,7 +1,7 @@
 // rsgpu_capi.cpp -- C ABI of librsgpu (include/rsgpu.h): host GF helpers with
 // ISA-L semantics, context/stream management, and the launch sequences of the
-// batched encode / decode hot path.  Scrub, repair, update and degraded scrub
-// are rsgpu_scrub.cpp; the helpers both files use, rsgpu_internal.h.
+// batched encode / decode hot path.  Scrub, repair, update, degraded scrub and
+// rebuild are rsgpu_scrub.cpp; the helpers both files use, rsgpu_internal.h.
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
@@ -595,7 +595,7 @@ int rsgpu_destroy(rsgpu_ctx* ctx)
         return RSGPU_ERR_ARG;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (void* p : {ctx->scratch.p, ctx->scrub.p, ctx->d_update, ctx->degraded.p})
+    for (void* p : {ctx->scratch.p, ctx->scrub.p, ctx->d_update, ctx->degraded.p, ctx->rebuild.p})
         if (p)
             (void)hipFree(p);
     if (ctx->h_stage)

@@ -92,6 +92,9 @@ struct rsgpu_ctx {
     // degraded scrub (rsgpu_scrub_degraded_blocks): the per-block tables
     // k_degraded_prepare writes for one slice
     DevBuf degraded;
+    // rebuild in place (rsgpu_rebuild_blocks): the per-block tables
+    // k_rebuild_prepare writes for one group of blocks
+    DevBuf rebuild;
     // pinned host staging for small uploads, guarded by an event
     void* h_stage = nullptr;
     size_t stage_bytes = 0;

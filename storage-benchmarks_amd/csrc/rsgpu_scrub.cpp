@@ -1,7 +1,8 @@
 // rsgpu_scrub.cpp -- the scrub family of the C ABI (include/rsgpu.h): parity
-// scrub, repair in place, partial-stripe update and degraded scrub.  Argument
-// checks and launch sequences; the kernels are rs_kernels.hip (two-pass
-// compare, finalise), rs_bitsliced.hip (fused), rs_update.hip, rs_degraded.hip.
+// scrub, repair in place, partial-stripe update, degraded scrub and rebuild in
+// place.  Argument checks and launch sequences; the kernels are rs_kernels.hip
+// (two-pass compare, finalise), rs_bitsliced.hip (fused), rs_update.hip,
+// rs_degraded.hip, rs_rebuild.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -182,6 +183,7 @@ int launch_head_and_tail(rsgpu_ctx* ctx, const char* const (&names)[3], size_t n
 constexpr const char* kUpdateNames[3] = {"k_update_blocks", "k_update_blocks(tail)", "k_update_blocks(bytes)"};
 constexpr const char* kDegradedNames[3] = {"k_degraded_compare", "k_degraded_compare(tail)",
                                            "k_degraded_compare(bytes)"};
+constexpr const char* kRebuildNames[3] = {"k_rebuild_blocks", "k_rebuild_blocks(tail)", "k_rebuild_blocks(bytes)"};
 
 // The update's device buffer: [tab4 256 x 16 B | tabc 256 x 4 B | matrix].
 constexpr size_t kUpdTab4Bytes = 256 * sizeof(uint4);
@@ -529,6 +531,85 @@ int rsgpu_scrub_degraded_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t
             return rc;
         KTimer kt(ctx, "k_degraded_finalise", ng);
         RS_HIP(ctx, launch_degraded_finalise(a, ctx->stream));
+    }
+    return RSGPU_OK;
+}
+
+int rsgpu_rebuild_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                         unsigned char* d_src, unsigned char* d_parity, const unsigned char* coef, int u,
+                         const unsigned char* d_lost, int flags, rsgpu_scrub_report* d_report)
+{
+    int rc = check_geom(ctx, k, e, len, pitch, blocks);
+    if (rc)
+        return rc;
+    const bool check = (flags & RSGPU_REBUILD_CHECK) != 0;
+    // with the check the located row may join the list, and a lane holds 8 rows
+    if (!d_report || (uintptr_t)d_report % 8 != 0 || (flags & ~RSGPU_REBUILD_CHECK) != 0 || u < 1 ||
+        u > (check ? 7 : 8) || !d_lost)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_rebuild_blocks: bad report pointer, flags, u or list");
+    const bool work = e > 0 && len > 0;
+    if (work && (!d_src || !d_parity))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_rebuild_blocks: null rows");
+    // the verdict on every block as it is now; the prepare below acts on it.
+    // With nothing to check the prepare alone judges the lists.
+    if (check && work) {
+        rc = rsgpu_scrub_degraded_blocks(ctx, k, e, len, pitch, blocks, d_src, d_parity, coef, u, d_lost,
+                                         RSGPU_SCRUB_LOCATE, d_report);
+        if (rc)
+            return rc;
+    }
+    // a group of blocks shares one prepare: its tables fit kDegTabBytes, its
+    // blocks fit a grid
+    const size_t stride = rebuild_tab_stride(k);
+    const size_t group = std::max<size_t>(1, std::min({blocks, kMaxGridBlocks, kDegTabBytes / stride}));
+    rc = ensure_device(ctx, ctx->rebuild, group * stride);
+    if (rc)
+        return rc;
+    if (work) {
+        // the v_perm tables of every coefficient value and the matrix, on the device
+        rc = update_tables(ctx, k, e, coef);
+        if (rc)
+            return rc;
+    }
+    const bool vec = pitch % 16 == 0 && (uintptr_t)d_src % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
+    const long long n16 = work && vec ? (long long)(len / 16) : 0;
+    const int most = std::min(u + (check ? 1 : 0), e);  // rows of any block's list as it is rebuilt
+    for (size_t g0 = 0; g0 < blocks; g0 += group) {
+        const size_t ng = std::min(group, blocks - g0);
+        RebuildArgs a{};
+        a.k = k;
+        a.e = e;
+        a.u = u;
+        a.check = check && work ? 1 : 0;
+        a.work = work ? 1 : 0;
+        a.pitch = (long long)pitch;
+        a.len = (long long)len;
+        a.blocks = (long long)ng;
+        a.lost = d_lost + g0 * (size_t)u;
+        a.tab = (uint8_t*)ctx->rebuild.p;
+        a.tab_stride = stride;
+        a.src_bytes = rebuild_src_bytes(k);
+        a.g = most > 4 ? 8 : most > 2 ? 4 : most > 1 ? 2 : 1;
+        a.report = d_report + g0;
+        if (work) {
+            a.src = d_src + g0 * (size_t)k * pitch;
+            a.par = d_parity + g0 * (size_t)e * pitch;
+            a.coef = (const uint8_t*)ctx->d_update + kUpdTabBytes;
+            a.tab4 = (const uint4*)ctx->d_update;
+            a.tabc = (const uint32_t*)((const char*)ctx->d_update + kUpdTab4Bytes);
+        }
+        {
+            KTimer kt(ctx, "k_rebuild_prepare", ng);
+            RS_HIP(ctx, launch_rebuild_prepare(a, ctx->stream));
+        }
+        if (!work)
+            continue;  // the prepare has written every report
+        auto launch = [&](bool bytes, long long c0, long long c1) {
+            return launch_rebuild_blocks(a, bytes, c0, c1, ctx->stream);
+        };
+        rc = launch_head_and_tail(ctx, kRebuildNames, ng, n16, (long long)len, launch);
+        if (rc)
+            return rc;
     }
     return RSGPU_OK;
 }

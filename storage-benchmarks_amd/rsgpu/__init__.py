@@ -39,7 +39,7 @@ __all__ = [
     "SCRUB_ONE_ROW", "SCRUB_DAMAGED", "REPAIR_REPORT_DTYPE", "REPAIR_MODES", "REPAIR_ONE_ROW",
     "REPAIR_COLUMNS", "REPAIR_CLEAN", "REPAIR_REPAIRED", "REPAIR_PARTIAL", "REPAIR_DAMAGED",
     "UPDATE_NONE", "UPDATE_DELTA", "LOST_NONE", "SCRUB_UNCHECKED", "SCRUB_BAD_MATRIX",
-    "SCRUB_BAD_LIST",
+    "SCRUB_BAD_LIST", "REBUILD_CHECK",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -76,6 +76,9 @@ UPDATE_DELTA = 1
 # (include/rsgpu.h); the report is SCRUB_REPORT_DTYPE
 LOST_NONE = 255
 SCRUB_UNCHECKED, SCRUB_BAD_MATRIX, SCRUB_BAD_LIST = 3, -1, -2
+# rsgpu_rebuild_blocks' flag (include/rsgpu.h); lists and reports as the
+# degraded scrub's
+REBUILD_CHECK = 1
 
 vp = C.c_void_p
 sz = C.c_size_t
@@ -126,6 +129,8 @@ _SIGS = {
     "rsgpu_scrub_locatable": (C.c_int, [C.c_int, C.c_int, vp]),
     "rsgpu_scrub_degraded_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp,
                                               C.c_int, vp]),
+    "rsgpu_rebuild_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp, C.c_int,
+                                       vp]),
     "rsgpu_repair_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp]),
     "rsgpu_set_scrub_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_update_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, C.c_int, vp, vp, vp, vp, vp,
@@ -465,6 +470,24 @@ class Context:
                                                      SCRUB_LOCATE if locate else 0, _ptr(d_report)),
                    "rsgpu_scrub_degraded_blocks")
 
+    def rebuild_blocks(self, k, e, length, pitch, blocks, d_src, d_par, u, d_lost, d_report,
+                       coef=None, check: bool = True) -> None:
+        """Rebuild in place (include/rsgpu.h rsgpu_rebuild_blocks): the rows
+        d_lost names (as scrub_degraded_blocks') are written back into d_src
+        and d_par.  With check (1 <= u <= 7) the degraded scrub runs first and
+        decides per block: a located row is rebuilt too, a DAMAGED block is
+        left alone; without it (1 <= u <= 8) every survivor is trusted.
+        d_report as scrub_degraded_blocks'.  Enqueued on the context's
+        stream."""
+        cptr = None
+        if coef is not None:
+            coef = np.ascontiguousarray(coef, np.uint8)
+            cptr = coef.ctypes.data
+        self.check(lib().rsgpu_rebuild_blocks(self._h, k, e, length, pitch, blocks, _ptr(d_src),
+                                              _ptr(d_par), cptr, u, _ptr(d_lost),
+                                              REBUILD_CHECK if check else 0, _ptr(d_report)),
+                   "rsgpu_rebuild_blocks")
+
     def repair_blocks(self, k, e, length, pitch, blocks, d_src, d_par, d_report, coef=None,
                       mode: str = "one_row") -> None:
         """Repair in place (include/rsgpu.h rsgpu_repair_blocks): d_src and
@@ -584,6 +607,25 @@ class GpuEncoder:
                           device=self.src.device)
         self.ctx.scrub_degraded_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,
                                        lost.shape[1], d_lost, rep, locate=locate)
+        self.ctx.synchronize()
+        return rep.cpu().numpy().view(SCRUB_REPORT_DTYPE)[: self.B].copy()
+
+    def rebuild(self, lost, check: bool = True) -> np.ndarray:
+        """Rebuilds the rows `lost` names of this encoder's blocks in place
+        (include/rsgpu.h rsgpu_rebuild_blocks): lost as scrub_degraded's, u
+        <= 7 with check, <= 8 without.  With check the degraded scrub decides
+        per block; the per-block reports as a structured array
+        (SCRUB_REPORT_DTYPE).  Synchronises (the reports are copied to the
+        host)."""
+        import torch
+        lost = np.ascontiguousarray(lost, np.uint8)
+        if lost.ndim != 2 or lost.shape[0] != self.B:
+            raise ValueError("lost must be a (blocks, u) array")
+        d_lost = torch.from_numpy(lost).to(self.src.device)
+        rep = torch.empty(max(1, self.B) * SCRUB_REPORT_DTYPE.itemsize, dtype=torch.uint8,
+                          device=self.src.device)
+        self.ctx.rebuild_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,
+                                lost.shape[1], d_lost, rep, check=check)
         self.ctx.synchronize()
         return rep.cpu().numpy().view(SCRUB_REPORT_DTYPE)[: self.B].copy()
 
