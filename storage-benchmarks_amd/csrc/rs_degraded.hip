@@ -292,12 +292,8 @@ __global__ __launch_bounds__(kDegThreads) void k_degraded_compare(DegradedArgs a
                 const Col<W> x = col_load<W>(parb + off, col);
                 const Col<W> y = col_load<W>(calcb + off, col);
 #pragma unroll
-                for (int w = 0; w < W; ++w) {
-                    const uint32_t s = x.d[w] ^ y.d[w];
-                    s0[i][w] = s & 0x07070707u;
-                    s1[i][w] = (s >> 3) & 0x07070707u;
-                    s2[i][w] = (s >> 6) & 0x03030303u;
-                }
+                for (int w = 0; w < W; ++w)
+                    sel_split(x.d[w] ^ y.d[w], s0[i][w], s1[i][w], s2[i][w]);
             }
         }
         // one walk over the rest rows, 2 kRestAhead loads in flight
@@ -330,8 +326,7 @@ __global__ __launch_bounds__(kDegThreads) void k_degraded_compare(DegradedArgs a
                             const uint32_t c = tc[i];
 #pragma unroll
                             for (int w = 0; w < W; ++w)
-                                t[w] ^= xor3(vperm(tt.y, tt.x, s0[i][w]), vperm(tt.w, tt.z, s1[i][w]),
-                                             vperm(c, c, s2[i][w]));
+                                t[w] ^= sel_mul(tt, c, s0[i][w], s1[i][w], s2[i][w]);
                         }
                     }
 #pragma unroll
@@ -383,14 +378,11 @@ hipError_t launch_w(const DegradedArgs& a, long long col0, long long col1, hipSt
 {
     const dim3 grid(columns_grid_x(col1 - col0, a.blocks, kDegThreads), (unsigned)a.blocks), block(kDegThreads);
     const int most = a.u < a.e ? a.u : a.e;  // pivot rows of any block: |D| <= n <= min(u, e)
-    const int g = most > 4 ? 8 : most > 2 ? 4 : most > 1 ? 2 : 1;
-    const size_t lds = (size_t)a.e * g * (sizeof(uint4) + sizeof(uint32_t)) + (size_t)a.e * sizeof(uint32_t);
-    switch (g) {
-    case 1: hipLaunchKernelGGL((k_degraded_compare<1, W>), grid, block, lds, st, a, col0, col1); break;
-    case 2: hipLaunchKernelGGL((k_degraded_compare<2, W>), grid, block, lds, st, a, col0, col1); break;
-    case 4: hipLaunchKernelGGL((k_degraded_compare<4, W>), grid, block, lds, st, a, col0, col1); break;
-    default: hipLaunchKernelGGL((k_degraded_compare<8, W>), grid, block, lds, st, a, col0, col1); break;
-    }
+    const int g = lane_group(most);
+    const size_t lds = lane_tables_lds(a.e, g, true);
+    with_lane_group(g, [&](auto G) {
+        hipLaunchKernelGGL((k_degraded_compare<decltype(G)::value, W>), grid, block, lds, st, a, col0, col1);
+    });
     return hipGetLastError();
 }
 

@@ -321,6 +321,12 @@ hipError_t launch_row_ptrs(const uint8_t* base, long long pitch, int rows_per_bl
 hipError_t launch_update(const uint8_t* data, uint8_t* const* coding, const uint4* tabs4,
                          const uint32_t* ctab, int rows, long long len, hipStream_t st);
 
+// The column kernels of update, degraded scrub and rebuild are instantiated
+// for G = 1, 2, 4 or 8 rows held per lane and clamp a block's count to G
+// (`nout < G ? nout : G`), so G must cover the most rows any block of the call
+// can have.  This is that rule, for the launchers and for RebuildArgs::g.
+inline int lane_group(int most) { return most > 4 ? 8 : most > 2 ? 4 : most > 1 ? 2 : 1; }
+
 // Partial-stripe update (rsgpu_update_blocks, rs_update.hip k_update_blocks):
 // per block the rows its list names are replaced (or taken as deltas) and the
 // e parity rows follow, parity[p] ^= XOR_i c[p][j_i] * delta_i.  blocks <=
@@ -415,7 +421,7 @@ struct RebuildArgs {
     uint8_t* par;          // [B][e] rows
     uint8_t* tab;          // [B] tables at tab_stride
     size_t tab_stride, src_bytes;
-    int g;                 // outputs a lane holds: 1, 2, 4 or 8, >= any block's
+    int g;                 // outputs a lane holds: lane_group(most rows of any block's list)
     const uint4* tab4;     // device [256]: perm_tables words 0-3 of every coefficient value
     const uint32_t* tabc;  // device [256]: perm_tables word 4
     ::rsgpu_scrub_report* report;  // [B]

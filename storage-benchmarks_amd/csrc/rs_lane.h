@@ -1,13 +1,17 @@
 // rs_lane.h -- what the kernels of the scrub family share (rs_kernels.hip's
 // scrub and repair, rs_update.hip, rs_degraded.hip, rs_rebuild.hip): the lane's building
-// blocks (v_perm multiply, three-way XOR, a column of one row), the fold of a
-// wave's bad columns into a block's report, the verdict on a finished fold,
-// and the grid rule of the column kernels.  Internal to librsgpu's .hip files.
+// blocks (v_perm multiply, three-way XOR, the 3-3-2 selector split of a dword
+// and the table multiply on it, a column of one row), the fold of a wave's bad
+// columns into a block's report, the verdict on a finished fold, and the
+// launch rules of the column kernels: their grid, the dispatch of the group
+// size G (rs_kernels.h lane_group) to a template argument and the LDS their
+// tables take.  Internal to librsgpu's .hip files.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/rsgpu.h"
 #include "rs_kernels.h"
@@ -22,6 +26,22 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
 __device__ __forceinline__ uint32_t vperm(uint32_t hi, uint32_t lo, uint32_t sel)
 {
     return __builtin_amdgcn_perm(hi, lo, sel);
+}
+
+// One dword of a column as the three v_perm selector dwords of the 3-3-2
+// split: bits 0-2, 3-5 and 6-7 of every byte.
+__device__ __forceinline__ void sel_split(uint32_t x, uint32_t& s0, uint32_t& s1, uint32_t& s2)
+{
+    s0 = x & 0x07070707u;
+    s1 = (x >> 3) & 0x07070707u;
+    s2 = (x >> 6) & 0x03030303u;
+}
+
+// c * x for the dword x of those selectors and the tables (t, tc) of the
+// coefficient c (gf256.h perm_tables: words 0-3 and word 4)
+__device__ __forceinline__ uint32_t sel_mul(const uint4& t, uint32_t tc, uint32_t s0, uint32_t s1, uint32_t s2)
+{
+    return xor3(vperm(t.y, t.x, s0), vperm(t.w, t.z, s1), vperm(tc, tc, s2));
 }
 
 // Row pointers fetched from memory are generic (flat) pointers; loads through
@@ -109,6 +129,26 @@ inline unsigned columns_grid_x(long long ncols, long long blocks, int threads)
 {
     const long long want = blocks >= 1024 ? 8 : (8192 + blocks - 1) / blocks;
     return (unsigned)std::max(1LL, std::min((ncols + threads - 1) / threads, want));
+}
+
+// f(std::integral_constant<int, G>) for g = lane_group(...) of rs_kernels.h:
+// the runtime group size as the kernel's template argument.
+template <class F>
+inline void with_lane_group(int g, F&& f)
+{
+    switch (g) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
+
+// LDS bytes of such a kernel: rows x g table entries (a uint4 of bits 0-5 and
+// a dword of bits 6-7 each), then with `index` one dword per row.
+inline size_t lane_tables_lds(int rows, int g, bool index)
+{
+    return (size_t)rows * g * (sizeof(uint4) + sizeof(uint32_t)) + (index ? (size_t)rows * sizeof(uint32_t) : 0);
 }
 
 }  // namespace rsgpu

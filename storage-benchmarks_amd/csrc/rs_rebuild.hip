@@ -250,11 +250,8 @@ __global__ __launch_bounds__(kRebThreads) void k_rebuild_blocks(RebuildArgs a, l
                     const uint32_t* tc = ltc + (size_t)(s0 + q) * G;
                     uint32_t v0[W], v1[W], v2[W];
 #pragma unroll
-                    for (int w = 0; w < W; ++w) {
-                        v0[w] = x[q].d[w] & 0x07070707u;
-                        v1[w] = (x[q].d[w] >> 3) & 0x07070707u;
-                        v2[w] = (x[q].d[w] >> 6) & 0x03030303u;
-                    }
+                    for (int w = 0; w < W; ++w)
+                        sel_split(x[q].d[w], v0[w], v1[w], v2[w]);
 #pragma unroll
                     for (int i = 0; i < G; ++i) {
                         if (i < nout) {
@@ -262,8 +259,7 @@ __global__ __launch_bounds__(kRebThreads) void k_rebuild_blocks(RebuildArgs a, l
                             const uint32_t c = tc[i];
 #pragma unroll
                             for (int w = 0; w < W; ++w)
-                                acc[i][w] ^= xor3(vperm(t.y, t.x, v0[w]), vperm(t.w, t.z, v1[w]),
-                                                  vperm(c, c, v2[w]));
+                                acc[i][w] ^= sel_mul(t, c, v0[w], v1[w], v2[w]);
                         }
                     }
                 }
@@ -286,13 +282,10 @@ template <int W>
 hipError_t launch_w(const RebuildArgs& a, long long col0, long long col1, hipStream_t st)
 {
     const dim3 grid(columns_grid_x(col1 - col0, a.blocks, kRebThreads), (unsigned)a.blocks), block(kRebThreads);
-    const size_t lds = (size_t)a.k * a.g * (sizeof(uint4) + sizeof(uint32_t)) + (size_t)a.k * sizeof(uint32_t);
-    switch (a.g) {
-    case 1: hipLaunchKernelGGL((k_rebuild_blocks<1, W>), grid, block, lds, st, a, col0, col1); break;
-    case 2: hipLaunchKernelGGL((k_rebuild_blocks<2, W>), grid, block, lds, st, a, col0, col1); break;
-    case 4: hipLaunchKernelGGL((k_rebuild_blocks<4, W>), grid, block, lds, st, a, col0, col1); break;
-    default: hipLaunchKernelGGL((k_rebuild_blocks<8, W>), grid, block, lds, st, a, col0, col1); break;
-    }
+    const size_t lds = lane_tables_lds(a.k, a.g, true);
+    with_lane_group(a.g, [&](auto G) {
+        hipLaunchKernelGGL((k_rebuild_blocks<decltype(G)::value, W>), grid, block, lds, st, a, col0, col1);
+    });
     return hipGetLastError();
 }
 
@@ -321,8 +314,7 @@ hipError_t launch_rebuild_blocks(const RebuildArgs& a, bool bytes, long long col
 {
     const int most = a.u + (a.check ? 1 : 0);  // rows of any block's list as it is rebuilt
     if (!args_ok(a) || !a.work || !a.src || !a.par || !a.tab4 || !a.tabc || col0 < 0 || col1 <= col0 ||
-        col1 * (bytes ? 1 : 16) > a.len || a.len > a.pitch ||
-        (a.g != 1 && a.g != 2 && a.g != 4 && a.g != 8) || a.g < (most < a.e ? most : a.e))
+        col1 * (bytes ? 1 : 16) > a.len || a.len > a.pitch || a.g != lane_group(most < a.e ? most : a.e))
         return hipErrorInvalidValue;
     return bytes ? launch_w<1>(a, col0, col1, st) : launch_w<4>(a, col0, col1, st);
 }

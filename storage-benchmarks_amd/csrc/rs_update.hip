@@ -100,11 +100,8 @@ __global__ __launch_bounds__(kUpdThreads) void k_update_blocks(UpdateArgs a, lon
                             x.d[w] ^= old.d[w];
                     }
 #pragma unroll
-                    for (int w = 0; w < W; ++w) {
-                        s0[i][w] = x.d[w] & 0x07070707u;
-                        s1[i][w] = (x.d[w] >> 3) & 0x07070707u;
-                        s2[i][w] = (x.d[w] >> 6) & 0x03030303u;
-                    }
+                    for (int w = 0; w < W; ++w)
+                        sel_split(x.d[w], s0[i][w], s1[i][w], s2[i][w]);
                 }
             }
             // one walk over the parity rows, kParityAhead loads in flight
@@ -126,8 +123,7 @@ __global__ __launch_bounds__(kUpdThreads) void k_update_blocks(UpdateArgs a, lon
                                 const uint32_t c = tc[i];
 #pragma unroll
                                 for (int w = 0; w < W; ++w)
-                                    acc[q].d[w] ^= xor3(vperm(t.y, t.x, s0[i][w]), vperm(t.w, t.z, s1[i][w]),
-                                                        vperm(c, c, s2[i][w]));
+                                    acc[q].d[w] ^= sel_mul(t, c, s0[i][w], s1[i][w], s2[i][w]);
                             }
                         }
                         col_store<W>(parb + (long long)(p0 + q) * a.pitch, col, acc[q]);
@@ -142,14 +138,11 @@ template <int W>
 hipError_t launch_w(const UpdateArgs& a, long long col0, long long col1, hipStream_t st)
 {
     const dim3 grid(columns_grid_x(col1 - col0, a.blocks, kUpdThreads), (unsigned)a.blocks), block(kUpdThreads);
-    const int g = a.u > 4 ? 8 : a.u > 2 ? 4 : a.u;
-    const size_t lds = (size_t)a.e * g * (sizeof(uint4) + sizeof(uint32_t));
-    switch (g) {
-    case 1: hipLaunchKernelGGL((k_update_blocks<1, W>), grid, block, lds, st, a, col0, col1); break;
-    case 2: hipLaunchKernelGGL((k_update_blocks<2, W>), grid, block, lds, st, a, col0, col1); break;
-    case 4: hipLaunchKernelGGL((k_update_blocks<4, W>), grid, block, lds, st, a, col0, col1); break;
-    default: hipLaunchKernelGGL((k_update_blocks<8, W>), grid, block, lds, st, a, col0, col1); break;
-    }
+    const int g = lane_group(a.u);
+    const size_t lds = lane_tables_lds(a.e, g, false);
+    with_lane_group(g, [&](auto G) {
+        hipLaunchKernelGGL((k_update_blocks<decltype(G)::value, W>), grid, block, lds, st, a, col0, col1);
+    });
     return hipGetLastError();
 }
 

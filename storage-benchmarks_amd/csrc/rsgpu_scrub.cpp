@@ -233,6 +233,15 @@ int update_tables(rsgpu_ctx* ctx, int k, int e, const unsigned char* coef)
     return RSGPU_OK;
 }
 
+// that buffer as the three fields of UpdateArgs, DegradedArgs or RebuildArgs
+template <class Args>
+void set_tables(Args& a, const rsgpu_ctx* ctx)
+{
+    a.tab4 = (const uint4*)ctx->d_update;
+    a.tabc = (const uint32_t*)((const char*)ctx->d_update + kUpdTab4Bytes);
+    a.coef = (const uint8_t*)ctx->d_update + kUpdTabBytes;
+}
+
 bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn)
 {
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
@@ -436,9 +445,7 @@ int rsgpu_update_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
         a.upd = d_upd ? d_upd + b0 * (size_t)u * pitch : nullptr;
         a.src = src_used && d_src ? d_src + b0 * (size_t)k * pitch : nullptr;
         a.par = par_used && d_parity ? d_parity + b0 * (size_t)e * pitch : nullptr;
-        a.tab4 = (const uint4*)ctx->d_update;
-        a.tabc = (const uint32_t*)((const char*)ctx->d_update + kUpdTab4Bytes);
-        a.coef = (const uint8_t*)ctx->d_update + kUpdTabBytes;
+        set_tables(a, ctx);
         a.status = d_status + b0;
         auto launch = [&](bool bytes, long long c0, long long c1) {
             return launch_update_blocks(a, bytes, c0, c1, ctx->stream);
@@ -501,11 +508,8 @@ int rsgpu_scrub_degraded_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t
         a.tab_stride = stride;
         a.rest_bytes = degraded_rest_bytes(e);
         a.report = d_report + g0;
-        if (work) {
-            a.coef = (const uint8_t*)ctx->d_update + kUpdTabBytes;
-            a.tab4 = (const uint4*)ctx->d_update;
-            a.tabc = (const uint32_t*)((const char*)ctx->d_update + kUpdTab4Bytes);
-        }
+        if (work)
+            set_tables(a, ctx);
         {
             KTimer kt(ctx, "k_degraded_prepare", ng);
             RS_HIP(ctx, launch_degraded_prepare(a, ctx->stream));
@@ -589,14 +593,12 @@ int rsgpu_rebuild_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch,
         a.tab = (uint8_t*)ctx->rebuild.p;
         a.tab_stride = stride;
         a.src_bytes = rebuild_src_bytes(k);
-        a.g = most > 4 ? 8 : most > 2 ? 4 : most > 1 ? 2 : 1;
+        a.g = lane_group(most);
         a.report = d_report + g0;
         if (work) {
             a.src = d_src + g0 * (size_t)k * pitch;
             a.par = d_parity + g0 * (size_t)e * pitch;
-            a.coef = (const uint8_t*)ctx->d_update + kUpdTabBytes;
-            a.tab4 = (const uint4*)ctx->d_update;
-            a.tabc = (const uint32_t*)((const char*)ctx->d_update + kUpdTab4Bytes);
+            set_tables(a, ctx);
         }
         {
             KTimer kt(ctx, "k_rebuild_prepare", ng);

@@ -199,6 +199,13 @@ def _ptr(x) -> int:
     raise TypeError(type(x))
 
 
+def _coef(coef):
+    """A coefficient matrix as contiguous bytes, to pass as _ptr(coef) while
+    the caller holds it; None (the built-in gf_gen_rs_matrix code) stays None
+    and goes down as a null pointer."""
+    return None if coef is None else np.ascontiguousarray(coef, np.uint8)
+
+
 # ---- host GF helpers (ISA-L C ABI) -----------------------------------------
 
 def gf_mul(a: int, b: int) -> int:
@@ -246,13 +253,10 @@ def ec_init_tables(k: int, rows: int, a: np.ndarray) -> np.ndarray:
 def scrub_locatable(k: int, e: int, coef=None) -> bool:
     """Whether rsgpu_scrub_blocks can name a damaged row for the e x k parity
     matrix ``coef`` (None: the gf_gen_rs_matrix code); include/rsgpu.h."""
-    cptr = None
-    if coef is not None:
-        coef = np.ascontiguousarray(coef, np.uint8)
-        if coef.size != k * e:
-            raise ValueError("coef must be e x k")
-        cptr = coef.ctypes.data
-    return bool(lib().rsgpu_scrub_locatable(k, e, cptr))
+    coef = _coef(coef)
+    if coef is not None and coef.size != k * e:
+        raise ValueError("coef must be e x k")
+    return bool(lib().rsgpu_scrub_locatable(k, e, _ptr(coef)))
 
 
 def erasure_patterns(seed: int, blk0: int, blocks: int, k: int, e: int) -> np.ndarray:
@@ -373,12 +377,9 @@ class Context:
 
     # batched calls
     def encode_blocks(self, k, e, length, pitch, blocks, d_src, d_par, coef=None) -> None:
-        cptr = None
-        if coef is not None:
-            coef = np.ascontiguousarray(coef, np.uint8)
-            cptr = coef.ctypes.data
+        coef = _coef(coef)
         self.check(lib().rsgpu_encode_blocks(self._h, k, e, length, pitch, blocks, _ptr(d_src),
-                                             _ptr(d_par), cptr), "rsgpu_encode_blocks")
+                                             _ptr(d_par), _ptr(coef)), "rsgpu_encode_blocks")
 
     def decode_blocks(self, k, e, length, pitch, blocks, d_src, d_par, d_err, d_out, d_ws,
                       d_status) -> None:
@@ -401,12 +402,9 @@ class Context:
     # host-resident calls (include/rsgpu.h): numpy arrays or pinned torch
     # CPU tensors; synchronous
     def encode_blocks_host(self, k, e, length, pitch, blocks, h_src, h_par, coef=None) -> None:
-        cptr = None
-        if coef is not None:
-            coef = np.ascontiguousarray(coef, np.uint8)
-            cptr = coef.ctypes.data
+        coef = _coef(coef)
         self.check(lib().rsgpu_encode_blocks_host(self._h, k, e, length, pitch, blocks, _ptr(h_src),
-                                                  _ptr(h_par), cptr), "rsgpu_encode_blocks_host")
+                                                  _ptr(h_par), _ptr(coef)), "rsgpu_encode_blocks_host")
 
     def decode_blocks_host(self, k, e, length, pitch, blocks, h_src, h_par, h_err, h_out,
                            h_status=None) -> None:
@@ -444,12 +442,9 @@ class Context:
         """Parity scrub (include/rsgpu.h rsgpu_scrub_blocks): d_report is
         device memory of blocks x 16 bytes, 8-byte aligned, read back as
         SCRUB_REPORT_DTYPE.  Enqueued on the context's stream."""
-        cptr = None
-        if coef is not None:
-            coef = np.ascontiguousarray(coef, np.uint8)
-            cptr = coef.ctypes.data
+        coef = _coef(coef)
         self.check(lib().rsgpu_scrub_blocks(self._h, k, e, length, pitch, blocks, _ptr(d_src),
-                                            _ptr(d_par), cptr, SCRUB_LOCATE if locate else 0,
+                                            _ptr(d_par), _ptr(coef), SCRUB_LOCATE if locate else 0,
                                             _ptr(d_report)), "rsgpu_scrub_blocks")
 
     def scrub_degraded_blocks(self, k, e, length, pitch, blocks, d_src, d_par, u, d_lost, d_report,
@@ -461,12 +456,9 @@ class Context:
         ascending, padded with LOST_NONE.  d_report as scrub_blocks'; the
         statuses add SCRUB_UNCHECKED, SCRUB_BAD_MATRIX and SCRUB_BAD_LIST.
         Rows are only read.  Enqueued on the context's stream."""
-        cptr = None
-        if coef is not None:
-            coef = np.ascontiguousarray(coef, np.uint8)
-            cptr = coef.ctypes.data
+        coef = _coef(coef)
         self.check(lib().rsgpu_scrub_degraded_blocks(self._h, k, e, length, pitch, blocks, _ptr(d_src),
-                                                     _ptr(d_par), cptr, u, _ptr(d_lost),
+                                                     _ptr(d_par), _ptr(coef), u, _ptr(d_lost),
                                                      SCRUB_LOCATE if locate else 0, _ptr(d_report)),
                    "rsgpu_scrub_degraded_blocks")
 
@@ -479,12 +471,9 @@ class Context:
         left alone; without it (1 <= u <= 8) every survivor is trusted.
         d_report as scrub_degraded_blocks'.  Enqueued on the context's
         stream."""
-        cptr = None
-        if coef is not None:
-            coef = np.ascontiguousarray(coef, np.uint8)
-            cptr = coef.ctypes.data
+        coef = _coef(coef)
         self.check(lib().rsgpu_rebuild_blocks(self._h, k, e, length, pitch, blocks, _ptr(d_src),
-                                              _ptr(d_par), cptr, u, _ptr(d_lost),
+                                              _ptr(d_par), _ptr(coef), u, _ptr(d_lost),
                                               REBUILD_CHECK if check else 0, _ptr(d_report)),
                    "rsgpu_rebuild_blocks")
 
@@ -494,12 +483,9 @@ class Context:
         d_par are corrected on the device, mode one_row | columns; d_report
         is device memory of blocks x 24 bytes, 8-byte aligned, read back as
         REPAIR_REPORT_DTYPE.  Enqueued on the context's stream."""
-        cptr = None
-        if coef is not None:
-            coef = np.ascontiguousarray(coef, np.uint8)
-            cptr = coef.ctypes.data
+        coef = _coef(coef)
         self.check(lib().rsgpu_repair_blocks(self._h, k, e, length, pitch, blocks, _ptr(d_src),
-                                             _ptr(d_par), cptr, REPAIR_MODES[mode],
+                                             _ptr(d_par), _ptr(coef), REPAIR_MODES[mode],
                                              _ptr(d_report)), "rsgpu_repair_blocks")
 
     def update_blocks(self, k, e, length, pitch, blocks, u, d_cols, d_upd, d_src, d_par, d_status,
@@ -510,12 +496,9 @@ class Context:
         the parity follows; with delta the rows of d_upd are new ^ old and
         d_src may be None.  d_status is device memory of blocks int32.
         Enqueued on the context's stream."""
-        cptr = None
-        if coef is not None:
-            coef = np.ascontiguousarray(coef, np.uint8)
-            cptr = coef.ctypes.data
+        coef = _coef(coef)
         self.check(lib().rsgpu_update_blocks(self._h, k, e, length, pitch, blocks, u, _ptr(d_cols),
-                                             _ptr(d_upd), _ptr(d_src), _ptr(d_par), cptr,
+                                             _ptr(d_upd), _ptr(d_src), _ptr(d_par), _ptr(coef),
                                              UPDATE_DELTA if delta else 0, _ptr(d_status)),
                    "rsgpu_update_blocks")
 
@@ -579,17 +562,34 @@ class GpuEncoder:
     def encode_all(self) -> None:
         self.ctx.encode_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par)
 
+    def _report(self, dtype):
+        """Device memory for one record of dtype per block, uninitialised."""
+        import torch
+        return torch.empty(max(1, self.B) * np.dtype(dtype).itemsize, dtype=torch.uint8,
+                           device=self.src.device)
+
+    def _read(self, rep, dtype) -> np.ndarray:
+        """Waits for the stream; the blocks' records of _report(dtype) as a
+        host array of its own."""
+        self.ctx.synchronize()
+        return rep.cpu().numpy().view(dtype)[: self.B].copy()
+
+    def _lists(self, name: str, lists):
+        """(u, device copy) of a (blocks, u) array of per-block row lists."""
+        import torch
+        lists = np.ascontiguousarray(lists, np.uint8)
+        if lists.ndim != 2 or lists.shape[0] != self.B:
+            raise ValueError(f"{name} must be a (blocks, u) array")
+        return lists.shape[1], torch.from_numpy(lists).to(self.src.device)
+
     def scrub(self, locate: bool = True) -> np.ndarray:
         """Scrubs this encoder's blocks against their stored parity; the
         per-block reports as a structured array (SCRUB_REPORT_DTYPE).
         Synchronises (the reports are copied to the host)."""
-        import torch
-        rep = torch.empty(max(1, self.B) * SCRUB_REPORT_DTYPE.itemsize, dtype=torch.uint8,
-                          device=self.src.device)
+        rep = self._report(SCRUB_REPORT_DTYPE)
         self.ctx.scrub_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, rep,
                               locate=locate)
-        self.ctx.synchronize()
-        return rep.cpu().numpy().view(SCRUB_REPORT_DTYPE)[: self.B].copy()
+        return self._read(rep, SCRUB_REPORT_DTYPE)
 
     def scrub_degraded(self, lost, locate: bool = True) -> np.ndarray:
         """Scrubs this encoder's blocks with known-lost rows (include/rsgpu.h
@@ -598,17 +598,11 @@ class GpuEncoder:
         padded with LOST_NONE.  The per-block reports as a structured array
         (SCRUB_REPORT_DTYPE).  Synchronises (the reports are copied to the
         host)."""
-        import torch
-        lost = np.ascontiguousarray(lost, np.uint8)
-        if lost.ndim != 2 or lost.shape[0] != self.B:
-            raise ValueError("lost must be a (blocks, u) array")
-        d_lost = torch.from_numpy(lost).to(self.src.device)
-        rep = torch.empty(max(1, self.B) * SCRUB_REPORT_DTYPE.itemsize, dtype=torch.uint8,
-                          device=self.src.device)
+        u, d_lost = self._lists("lost", lost)
+        rep = self._report(SCRUB_REPORT_DTYPE)
         self.ctx.scrub_degraded_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,
-                                       lost.shape[1], d_lost, rep, locate=locate)
-        self.ctx.synchronize()
-        return rep.cpu().numpy().view(SCRUB_REPORT_DTYPE)[: self.B].copy()
+                                       u, d_lost, rep, locate=locate)
+        return self._read(rep, SCRUB_REPORT_DTYPE)
 
     def rebuild(self, lost, check: bool = True) -> np.ndarray:
         """Rebuilds the rows `lost` names of this encoder's blocks in place
@@ -617,30 +611,21 @@ class GpuEncoder:
         per block; the per-block reports as a structured array
         (SCRUB_REPORT_DTYPE).  Synchronises (the reports are copied to the
         host)."""
-        import torch
-        lost = np.ascontiguousarray(lost, np.uint8)
-        if lost.ndim != 2 or lost.shape[0] != self.B:
-            raise ValueError("lost must be a (blocks, u) array")
-        d_lost = torch.from_numpy(lost).to(self.src.device)
-        rep = torch.empty(max(1, self.B) * SCRUB_REPORT_DTYPE.itemsize, dtype=torch.uint8,
-                          device=self.src.device)
+        u, d_lost = self._lists("lost", lost)
+        rep = self._report(SCRUB_REPORT_DTYPE)
         self.ctx.rebuild_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,
-                                lost.shape[1], d_lost, rep, check=check)
-        self.ctx.synchronize()
-        return rep.cpu().numpy().view(SCRUB_REPORT_DTYPE)[: self.B].copy()
+                                u, d_lost, rep, check=check)
+        return self._read(rep, SCRUB_REPORT_DTYPE)
 
     def repair(self, mode: str = "one_row") -> np.ndarray:
         """Scrubs this encoder's blocks and corrects their rows in place
         (mode one_row | columns, include/rsgpu.h rsgpu_repair_blocks); the
         per-block reports as a structured array (REPAIR_REPORT_DTYPE).
         Synchronises (the reports are copied to the host)."""
-        import torch
-        rep = torch.empty(max(1, self.B) * REPAIR_REPORT_DTYPE.itemsize, dtype=torch.uint8,
-                          device=self.src.device)
+        rep = self._report(REPAIR_REPORT_DTYPE)
         self.ctx.repair_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, rep,
                                mode=mode)
-        self.ctx.synchronize()
-        return rep.cpu().numpy().view(REPAIR_REPORT_DTYPE)[: self.B].copy()
+        return self._read(rep, REPAIR_REPORT_DTYPE)
 
     def update(self, cols, rows, delta: bool = False) -> np.ndarray:
         """Overwrites source rows of this encoder's blocks and brings the
@@ -650,19 +635,13 @@ class GpuEncoder:
         rows at this encoder's pitch (deltas, new ^ old, with delta=True).
         Returns the per-block statuses (0, or -2 for a malformed list).
         Synchronises (the statuses are copied to the host)."""
-        import torch
-        cols = np.ascontiguousarray(cols, np.uint8)
-        if cols.ndim != 2 or cols.shape[0] != self.B:
-            raise ValueError("cols must be a (blocks, u) array")
-        u = cols.shape[1]
+        u, d_cols = self._lists("cols", cols)
         if rows.numel() < self.B * u * self.pitch:
             raise ValueError("rows must hold blocks x u rows at the encoder's pitch")
-        d_cols = torch.from_numpy(cols).to(self.src.device)
-        status = torch.empty(max(1, self.B), dtype=torch.int32, device=self.src.device)
+        status = self._report(np.int32)
         self.ctx.update_blocks(self.k, self.e, self.L, self.pitch, self.B, u, d_cols, rows,
                                None if delta else self.src, self.par, status, delta=delta)
-        self.ctx.synchronize()
-        return status.cpu().numpy()[: self.B].copy()
+        return self._read(status, np.int32)
 
     def block_size(self) -> int:
         return self.m_block_size

@@ -14,207 +14,25 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 import degraded_model as dm  # noqa: E402
+import gpu_family as gf  # noqa: E402
 import rsgpu  # noqa: E402
 import scrub_model as sm  # noqa: E402
 from oracle_lib import Oracle  # noqa: E402
 
 N = dm.NONE
 DT = rsgpu.SCRUB_REPORT_DTYPE
-POISON = 0xA5
+POISON = gf.POISON
+Stripe, CASES, same, mixed_lists, damage = gf.DegradedStripe, gf.CASES, gf.same, gf.mixed_lists, gf.damage
 
 
 @pytest.fixture(scope="module")
 def ctx():
-    assert torch.cuda.is_available(), "GPU test needs a HIP device"
-    c = rsgpu.Context(0)
-    c.set_torch_stream()
-    yield c
-    torch.cuda.synchronize()
-    c.close()
+    yield from gf.device_context()
 
 
 @pytest.fixture(scope="module")
 def orc():
     return Oracle()
-
-
-def matrix(k, e, kind):
-    return sm.rs_matrix(k, e) if kind == "rs" else sm.cauchy_matrix(k, e)
-
-
-def pitch_of(L, mode):
-    """eq: pitch == len; plus48: len + 48; mis1: rows one byte past the
-    allocation's alignment; tail: a 16-byte aligned pitch around a len that
-    is no multiple of 16 (vector body, byte tail)."""
-    if mode == "plus48":
-        return L + 48, 0
-    if mode == "mis1":
-        return L, 1
-    if mode == "tail":
-        return (L + 255) // 256 * 256, 0
-    return L, 0
-
-
-class Stripe:
-    """B consistent synthetic blocks on the device, a list of lost rows per block."""
-
-    def __init__(self, ctx, k, e, L, B, u, kind="rs", mode="eq", seed=11, c=None):
-        self.ctx, self.k, self.e, self.L, self.B, self.u = ctx, k, e, L, B, u
-        self.pitch, offset = pitch_of(L, mode)
-        self.c = matrix(k, e, kind) if c is None else np.ascontiguousarray(c, np.uint8)
-        self.coef = None if kind == "rs" and c is None else self.c
-        self.dev = dev = torch.device("cuda", 0)
-
-        def alloc(rows):  # at least a byte, so that the pointer is not null
-            t = torch.empty(max(1, B * rows * self.pitch) + offset, dtype=torch.uint8, device=dev)
-            t.fill_(0x6B)
-            return t
-
-        self.src_all, self.par_all = alloc(k), alloc(e)
-        self.src, self.par = self.src_all[offset:], self.par_all[offset:]
-        ctx.fill_synthetic(self.src, B * k, L, self.pitch, seed, 0)
-        ctx.encode_blocks(k, e, L, self.pitch, B, self.src, self.par, coef=self.coef)
-        self.lost = np.full((B, u), N, np.uint8)
-        self.rep = torch.empty(B * DT.itemsize, dtype=torch.uint8, device=dev)
-        torch.cuda.synchronize()
-
-    def view(self, t, rows):
-        return t[: self.B * rows * self.pitch].view(self.B, rows, self.pitch)
-
-    def row(self, blk, row):
-        if row < self.k:
-            return self.view(self.src, self.k)[blk, row, : self.L]
-        return self.view(self.par, self.e)[blk, row - self.k, : self.L]
-
-    def xor(self, blk, row, col, x):
-        self.row(blk, row)[col] ^= x
-
-    def fill_lost(self, seed):
-        """Every listed row of every well-formed list: zero (seed None) or noise."""
-        g = torch.Generator(device="cpu").manual_seed(seed or 0)
-        for b in range(self.B):
-            for r in dm.list_rows(self.lost[b], self.k, self.e) or []:
-                if seed is None:
-                    self.row(b, r).zero_()
-                else:
-                    self.row(b, r).copy_(torch.randint(0, 256, (self.L,), dtype=torch.uint8, generator=g))
-
-    def scrub(self, locate=True):
-        d_lost = torch.from_numpy(self.lost).to(self.dev)
-        self.rep.fill_(POISON)
-        before = self.src_all.clone(), self.par_all.clone()
-        self.ctx.scrub_degraded_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, self.u,
-                                       d_lost, self.rep, coef=self.coef, locate=locate)
-        torch.cuda.synchronize()
-        assert torch.equal(self.src_all, before[0]), "source allocation written"
-        assert torch.equal(self.par_all, before[1]), "parity allocation written"
-        assert (d_lost.cpu().numpy() == self.lost).all(), "lists written"
-        return self.rep.cpu().numpy().view(DT).copy()
-
-    def model(self, orc, locate=True):
-        """The model's reports on the blocks as they are on the device now."""
-        hs = self.view(self.src, self.k)[:, :, : self.L].contiguous().cpu().numpy()
-        hp = self.view(self.par, self.e)[:, :, : self.L].contiguous().cpu().numpy()
-        g = orc.init_tables(self.k, self.e, self.c) if self.e else None
-        out = []
-        for b in range(self.B):
-            syn = hp[b].copy()
-            if self.e and self.L:
-                calc = [np.zeros(self.L, np.uint8) for _ in range(self.e)]
-                orc.encode_data(self.L, self.k, self.e, g, [np.ascontiguousarray(r) for r in hs[b]], calc)
-                syn ^= np.stack(calc)
-            out.append(dm.report_syn(self.c, syn, self.lost[b], locate))
-        return out
-
-
-def same(rep, want):
-    got = [(int(r["bad_columns"]), int(r["status"]), int(r["row"])) for r in rep]
-    assert got == [tuple(w) for w in want], [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != tuple(w)]
-
-
-def mixed_lists(k, e, u, B, seed=5):
-    """Per block n = b mod (min(u, e) + 1) lost rows, n == e included where u
-    allows; data only, parity only and both by turns; block 0 holds the first
-    rows, block 1 the last ones."""
-    rng = np.random.default_rng(seed)
-    nmax = min(u, e)
-    lost = np.full((B, u), N, np.uint8)
-    for b in range(B):
-        n = b % (nmax + 1) if B > 1 else min(nmax, max(1, e - 2))
-        kind = (b // (nmax + 1)) % 3
-        if kind == 0:  # data only
-            rows = rng.choice(k, min(n, k), replace=False)
-        elif kind == 1:  # parity only
-            rows = k + rng.choice(e, n, replace=False)
-        else:
-            rows = rng.choice(k + e, n, replace=False)
-        lost[b] = dm.pad(np.sort(rows), u)
-    if B > 2:
-        n = min(nmax, max(1, e - 2))
-        lost[0] = dm.pad(np.arange(n), u)
-        lost[1] = dm.pad(np.arange(k + e - n, k + e), u)
-    return lost
-
-
-def damage(st, seed=9):
-    """Block b gets damage kind (b // (min(u, e) + 1)) mod 7, so that every
-    kind meets every n: none; one byte of a survivor; one survivor in several
-    columns, the first and the last included; two survivors in different
-    columns; two survivors in one column; a byte of the first surviving parity
-    row (a pivot row when data rows are lost); a byte of the last surviving
-    parity row (a rest row)."""
-    rng = np.random.default_rng(seed)
-    k, e, L = st.k, st.e, st.L
-    nmax = min(st.u, e)
-    for b in range(st.B):
-        lost = dm.list_rows(st.lost[b], k, e) or []
-        surv = [r for r in range(k + e) if r not in lost]
-        spar = [r for r in surv if r >= k]
-        kind = (b // (nmax + 1)) % 7 if st.B > 1 else 2
-        x = lambda: int(rng.integers(1, 256))  # noqa: E731
-        pick = lambda n: [int(r) for r in rng.choice(surv, n, replace=False)]  # noqa: E731
-        if kind == 1:
-            st.xor(b, pick(1)[0], int(rng.integers(0, L)), x())
-        elif kind == 2:
-            r = pick(1)[0]
-            for col in sorted({0, L - 1, L // 2, (L // 3) | 1 if L > 1 else 0, min(17, L - 1)}):
-                st.xor(b, r, col, x())
-        elif kind == 3:
-            r1, r2 = pick(2)
-            st.xor(b, r1, 0, x())
-            st.xor(b, r2, L - 1 if L > 1 else 0, x())
-        elif kind == 4:
-            r1, r2 = pick(2)
-            col = int(rng.integers(0, L))
-            st.xor(b, r1, col, x())
-            st.xor(b, r2, col, x())
-        elif kind == 5 and spar:
-            st.xor(b, spar[0], int(rng.integers(0, L)), x())
-        elif kind == 6 and spar:
-            st.xor(b, spar[-1], int(rng.integers(0, L)), x())
-    torch.cuda.synchronize()
-
-
-# codes (5, 4) (16, 4) (20, 7) (64, 32) RS and Cauchy (10, 4); len in {1, 31,
-# 32, 2080, 4176} and 4099 (a 16-byte body with a 3-byte tail); the three
-# pitches; blocks in {1, 67}; u in {1, 2, 4, 8}
-CASES = [
-    (5, 4, "rs", 4176, 67, 4, "plus48"),
-    (5, 4, "rs", 1, 67, 1, "eq"),
-    (5, 4, "rs", 31, 67, 2, "eq"),
-    (5, 4, "rs", 4099, 67, 2, "tail"),
-    (16, 4, "rs", 32, 67, 8, "eq"),
-    (16, 4, "rs", 2080, 1, 2, "plus48"),
-    (16, 4, "rs", 2080, 67, 4, "mis1"),
-    (20, 7, "rs", 4176, 67, 8, "eq"),
-    (20, 7, "rs", 31, 1, 4, "plus48"),
-    (64, 32, "rs", 2080, 67, 8, "eq"),
-    (64, 32, "rs", 4176, 1, 1, "plus48"),
-    (64, 32, "rs", 32, 67, 2, "mis1"),
-    (10, 4, "cauchy", 2080, 67, 4, "plus48"),
-    (10, 4, "cauchy", 4176, 1, 8, "eq"),
-    (10, 4, "cauchy", 1, 1, 1, "mis1"),
-]
 
 
 @pytest.mark.parametrize("k,e,kind,L,B,u,mode", CASES, ids=str)

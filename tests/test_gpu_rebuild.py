@@ -1,5 +1,5 @@
 """Rebuild in place on the GPU (include/rsgpu.h rsgpu_rebuild_blocks): the
-stripes, lists and damage kinds of tests/test_gpu_degraded.py, the lost rows
+stripes, lists and damage kinds of the degraded scrub (tests/gpu_family.py), the lost rows
 overwritten with noise before every call.  What the call must leave behind is
 put together on the device from a clone of the state before the call and the
 rows the numpy model of the contract (tests/rebuild_model.py) rebuilds from
@@ -13,25 +13,20 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 import degraded_model as dm  # noqa: E402
+import gpu_family as gf  # noqa: E402
 import rebuild_model as rm  # noqa: E402
 import rsgpu  # noqa: E402
 import scrub_model as sm  # noqa: E402
-import test_gpu_degraded as tgd  # noqa: E402
 from oracle_lib import Oracle  # noqa: E402
 
 N = dm.NONE
 DT = rsgpu.SCRUB_REPORT_DTYPE
-POISON = 0xA5
+POISON = gf.POISON
 
 
 @pytest.fixture(scope="module")
 def ctx():
-    assert torch.cuda.is_available(), "GPU test needs a HIP device"
-    c = rsgpu.Context(0)
-    c.set_torch_stream()
-    yield c
-    torch.cuda.synchronize()
-    c.close()
+    yield from gf.device_context()
 
 
 @pytest.fixture(scope="module")
@@ -39,25 +34,19 @@ def orc():
     return Oracle()
 
 
-class Stripe(tgd.Stripe):
+class Stripe(gf.DegradedStripe):
     """The degraded scrub's stripe with a clone of the original encode."""
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
-        self.orig = self.src_all.clone(), self.par_all.clone()
-        self.off = self.src_all.numel() - self.src.numel()
+        self.orig = self.snapshot()
 
     def noise(self, seed):
         self.fill_lost(seed)
         torch.cuda.synchronize()
 
-    def state(self):
-        return self.src_all.clone(), self.par_all.clone()
-
-    def host(self):
-        hs = self.view(self.src, self.k)[:, :, : self.L].contiguous().cpu().numpy()
-        hp = self.view(self.par, self.e)[:, :, : self.L].contiguous().cpu().numpy()
-        return hs, hp
+    def hosts(self):
+        return self.host(self.src, self.k), self.host(self.par, self.e)
 
     def rebuild(self, check):
         d_lost = torch.from_numpy(self.lost).to(self.dev)
@@ -70,7 +59,7 @@ class Stripe(tgd.Stripe):
 
     def original(self):
         """The original encode as (B, k, pitch) and (B, e, pitch) views."""
-        return self.view(self.orig[0][self.off:], self.k), self.view(self.orig[1][self.off:], self.e)
+        return self.view(self.orig[0][self.offset:], self.k), self.view(self.orig[1][self.offset:], self.e)
 
     def is_original(self, b):
         os_, op = self.original()
@@ -83,8 +72,8 @@ class Stripe(tgd.Stripe):
         and the two allocations."""
         hs, hp = host
         es, ep = pre[0].clone(), pre[1].clone()
-        vs = self.view(es[self.off:], self.k)
-        vp = self.view(ep[self.off:], self.e)
+        vs = self.view(es[self.offset:], self.k)
+        vp = self.view(ep[self.offset:], self.e)
         want = []
         for b in range(self.B):
             sb, pb = hs[b], hp[b]
@@ -103,21 +92,21 @@ class Stripe(tgd.Stripe):
         assert torch.equal(self.par_all, ep), "parity allocation"
 
 
-same = tgd.same
+same = gf.same
 
 
-@pytest.mark.parametrize("k,e,kind,L,B,u,mode", tgd.CASES, ids=str)
+@pytest.mark.parametrize("k,e,kind,L,B,u,mode", gf.CASES, ids=str)
 def test_unchecked_against_the_model(ctx, k, e, kind, L, B, u, mode):
     """Mixed lists, n from 0 to min(u, e), consistent survivors: every block
     is CLEAN, the allocations are what the model says, which is the original
     encode; other noise in the lost rows, the same bytes and reports."""
     st = Stripe(ctx, k, e, L, B, u, kind, mode)
-    st.lost = tgd.mixed_lists(k, e, u, B)
+    st.lost = gf.mixed_lists(k, e, u, B)
     if B > 1:
         ns = {len(dm.list_rows(lst, k, e)) for lst in st.lost}
         assert ns == set(range(min(u, e) + 1))
     st.noise(1)
-    pre, host = st.state(), st.host()
+    pre, host = st.snapshot(), st.hosts()
     got = st.rebuild(check=False)
     want, es, ep = st.expect(pre, host, check=False)
     same(got, want)
@@ -135,14 +124,14 @@ def test_unchecked_with_two_damaged_survivors(ctx):
     byte for byte, in the vector body and in the byte tail."""
     k, e, L, B, u = 16, 4, 2083, 67, 4
     st = Stripe(ctx, k, e, L, B, u, "rs", "tail")
-    st.lost = tgd.mixed_lists(k, e, u, B)
+    st.lost = gf.mixed_lists(k, e, u, B)
     rng = np.random.default_rng(6)
     for b in range(B):
         surv = [r for r in range(k + e) if r not in dm.list_rows(st.lost[b], k, e)]
         for r, col in zip(rng.choice(surv, 2, replace=False), (int(rng.integers(0, L - 3)), L - 1 - b % 3)):
             st.xor(b, int(r), col, int(rng.integers(1, 256)))
     st.noise(3)
-    pre, host = st.state(), st.host()
+    pre, host = st.snapshot(), st.hosts()
     got = st.rebuild(check=False)
     want, es, ep = st.expect(pre, host, check=False)
     same(got, want)
@@ -156,7 +145,7 @@ def test_unchecked_with_two_damaged_survivors(ctx):
 def checked(st, orc):
     """One checked call on the stripe as it is, against the models; returns
     the reports."""
-    pre, host = st.state(), st.host()
+    pre, host = st.snapshot(), st.hosts()
     reports = st.model(orc)  # the degraded model on the blocks as they are
     want, es, ep = st.expect(pre, host, check=True, reports=reports)
     got = st.rebuild(check=True)
@@ -176,7 +165,7 @@ def checked(st, orc):
     return want, (es, ep)
 
 
-CHECKED = [(k, e, kind, L, B, min(u, 7), mode) for k, e, kind, L, B, u, mode in tgd.CASES]
+CHECKED = [(k, e, kind, L, B, min(u, 7), mode) for k, e, kind, L, B, u, mode in gf.CASES]
 
 
 @pytest.mark.parametrize("k,e,kind,L,B,u,mode", CHECKED, ids=str)
@@ -186,10 +175,10 @@ def test_checked_against_the_models(ctx, orc, k, e, kind, L, B, u, mode):
     blocks and ONE_ROW blocks come back as the original encode, DAMAGED ones
     keep their bytes, UNCHECKED ones are the model's."""
     st = Stripe(ctx, k, e, L, B, u, kind, mode)
-    st.lost = tgd.mixed_lists(k, e, u, B)
-    tgd.damage(st)
+    st.lost = gf.mixed_lists(k, e, u, B)
+    gf.damage(st)
     st.noise(5)
-    before = st.state()
+    before = st.snapshot()
     want, after = checked(st, orc)
     if B > 1:
         statuses = {w[1] for w in want}
@@ -202,7 +191,7 @@ def test_checked_against_the_models(ctx, orc, k, e, kind, L, B, u, mode):
     st.noise(6)
     got = st.rebuild(check=True)
     same(got, want)
-    vs, vp = st.view(after[0][st.off:], k), st.view(after[1][st.off:], e)
+    vs, vp = st.view(after[0][st.offset:], k), st.view(after[1][st.offset:], e)
     for b, w in enumerate(want):
         if w[1] in (dm.DAMAGED, dm.BAD_MATRIX):
             for r in dm.list_rows(st.lost[b], k, e):
@@ -243,7 +232,7 @@ def test_lists_and_matrices(ctx, orc, check):
     if check:
         want, _ = checked(st, orc)
     else:
-        pre, host = st.state(), st.host()
+        pre, host = st.snapshot(), st.hosts()
         got = st.rebuild(check=False)
         want, es, ep = st.expect(pre, host, check=False)
         same(got, want)

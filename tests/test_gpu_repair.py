@@ -16,6 +16,7 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+import gpu_family as gf  # noqa: E402
 import repair_model as rm  # noqa: E402
 import rsgpu  # noqa: E402
 import scrub_model as sm  # noqa: E402
@@ -35,65 +36,29 @@ _OWN = object()  # Blocks.repair: the matrix the blocks were encoded with
 
 @pytest.fixture(scope="module")
 def ctx():
-    assert torch.cuda.is_available(), "GPU test needs a HIP device"
-    c = rsgpu.Context(0)
-    c.set_torch_stream()
-    yield c
-    torch.cuda.synchronize()
-    c.set_scrub_kernel("auto")
-    c.close()
+    yield from gf.device_context(reset_scrub_kernel=True)
 
 
-class Blocks:
+class Blocks(gf.DeviceBlocks):
     """B synthetic blocks and their parity on the device."""
 
     def __init__(self, ctx, k, e, L, B, kind="rs", pitch=None, offset=0, seed=11):
-        self.ctx, self.k, self.e, self.L, self.B = ctx, k, e, L, B
-        self.pitch = pitch or (L + 255) // 256 * 256
-        self.c = sm.rs_matrix(k, e) if kind == "rs" else sm.cauchy_matrix(k, e)
-        self.coef = None if kind == "rs" else self.c
-        dev = torch.device("cuda", 0)
-        # offset: rows that start `offset` bytes past the allocation's alignment
-        self.src_all = torch.zeros(B * k * self.pitch + offset, dtype=torch.uint8, device=dev)
-        self.par_all = torch.zeros(B * e * self.pitch + offset, dtype=torch.uint8, device=dev)
-        self.src_all.fill_(0x6B)  # the padding is not zero
-        self.par_all.fill_(0x6B)
-        self.src, self.par = self.src_all[offset:], self.par_all[offset:]
-        ctx.fill_synthetic(self.src, B * k, L, self.pitch, seed, 0)
-        ctx.encode_blocks(k, e, L, self.pitch, B, self.src, self.par, coef=self.coef)
-        self.rep = torch.empty(B * DT.itemsize, dtype=torch.uint8, device=dev)
-        self.srep = torch.empty(B * rsgpu.SCRUB_REPORT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        super().__init__(ctx, k, e, L, B, pitch or (L + 255) // 256 * 256, offset, kind, seed=seed)
+        self.rep = torch.empty(B * DT.itemsize, dtype=torch.uint8, device=self.dev)
+        self.srep = torch.empty(B * rsgpu.SCRUB_REPORT_DTYPE.itemsize, dtype=torch.uint8, device=self.dev)
         torch.cuda.synchronize()
         self.pristine = self.snapshot()
 
-    def snapshot(self):
-        return self.src_all.clone(), self.par_all.clone()
-
     def equals(self, snap):
         return torch.equal(self.src_all, snap[0]) and torch.equal(self.par_all, snap[1])
-
-    def rows(self, row):
-        """[B, L] view of row `row` (source, or parity from k on) of every block."""
-        if row < self.k:
-            return self.src.view(self.B, self.k, self.pitch)[:, row, : self.L]
-        return self.par.view(self.B, self.e, self.pitch)[:, row - self.k, : self.L]
-
-    def xor(self, blk, row, col, x):
-        self.rows(row)[blk, col] ^= x
-
-    def host_block(self, blk):
-        s = self.src.view(self.B, self.k, self.pitch)[blk, :, : self.L].cpu().numpy()
-        p = self.par.view(self.B, self.e, self.pitch)[blk, :, : self.L].cpu().numpy()
-        return s, p
 
     def model(self, mode, damaged):
         """The model on the blocks `damaged` as they are now: ([verdict per
         block of the batch], the allocations as the call must leave them)."""
         want = [CLEAN] * self.B
         src, par = self.snapshot()
-        off = self.src_all.numel() - self.src.numel()
-        sv = src[off:].view(self.B, self.k, self.pitch)
-        pv = par[off:].view(self.B, self.e, self.pitch)
+        sv = self.view(src[self.offset:], self.k)
+        pv = self.view(par[self.offset:], self.e)
         for b in damaged:
             s, p = self.host_block(b)
             s2, p2, want[b] = rm.repair(self.c, s, p, mode)
@@ -127,8 +92,7 @@ class Blocks:
 
 def same(rep, want):
     """rep: structured reports; want: [(bad, repaired, status, row)] from the model."""
-    got = [(int(r["bad_columns"]), int(r["repaired_columns"]), int(r["status"]), int(r["row"])) for r in rep]
-    assert got == [tuple(w) for w in want], [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != tuple(w)]
+    gf.same(rep, want, gf.REPAIR_FIELDS)
 
 
 def run(blk, kernel, mode, want, after):

@@ -14,6 +14,7 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+import gpu_family as gf  # noqa: E402
 import rsgpu  # noqa: E402
 import scrub_model as sm  # noqa: E402
 
@@ -28,44 +29,19 @@ DT = rsgpu.SCRUB_REPORT_DTYPE
 
 @pytest.fixture(scope="module")
 def ctx():
-    assert torch.cuda.is_available(), "GPU test needs a HIP device"
-    c = rsgpu.Context(0)
-    c.set_torch_stream()
-    yield c
-    torch.cuda.synchronize()
-    c.set_scrub_kernel("auto")
-    c.close()
+    yield from gf.device_context(reset_scrub_kernel=True)
 
 
-def matrix(k, e, kind):
-    return sm.rs_matrix(k, e) if kind == "rs" else sm.cauchy_matrix(k, e)
+same = gf.same
 
 
-class Blocks:
+class Blocks(gf.DeviceBlocks):
     """B synthetic blocks and their parity on the device; scrub() returns the
     reports as a structured array."""
 
     def __init__(self, ctx, k, e, L, B, kind="rs", pitch=None, offset=0, seed=11):
-        self.ctx, self.k, self.e, self.L, self.B = ctx, k, e, L, B
-        self.pitch = pitch or (L + 255) // 256 * 256
-        self.c = matrix(k, e, kind)
-        self.coef = None if kind == "rs" else self.c
-        dev = torch.device("cuda", 0)
-        # offset: rows that start `offset` bytes past the allocation's alignment
-        self.src = torch.empty(B * k * self.pitch + offset, dtype=torch.uint8, device=dev)[offset:]
-        self.par = torch.empty(B * e * self.pitch + offset, dtype=torch.uint8, device=dev)[offset:]
-        ctx.fill_synthetic(self.src, B * k, L, self.pitch, seed, 0)
-        ctx.encode_blocks(k, e, L, self.pitch, B, self.src, self.par, coef=self.coef)
-        self.rep = torch.empty(B * DT.itemsize, dtype=torch.uint8, device=dev)
-
-    def rows(self, row):
-        """[B, L] view of row `row` (source, or parity from k on) of every block."""
-        if row < self.k:
-            return self.src.view(self.B, self.k, self.pitch)[:, row, : self.L]
-        return self.par.view(self.B, self.e, self.pitch)[:, row - self.k, : self.L]
-
-    def xor(self, blk, row, col, x):
-        self.rows(row)[blk, col] ^= x
+        super().__init__(ctx, k, e, L, B, pitch or (L + 255) // 256 * 256, offset, kind, seed=seed)
+        self.rep = torch.empty(B * DT.itemsize, dtype=torch.uint8, device=self.dev)
 
     def scrub(self, kernel="auto", locate=True, poison=0xA5, coef="own"):
         self.ctx.set_scrub_kernel(kernel)
@@ -77,17 +53,6 @@ class Blocks:
             self.ctx.set_scrub_kernel("auto")
         torch.cuda.synchronize()
         return self.rep.cpu().numpy().view(DT)
-
-    def host_block(self, blk):
-        s = self.src.view(self.B, self.k, self.pitch)[blk, :, : self.L].cpu().numpy()
-        p = self.par.view(self.B, self.e, self.pitch)[blk, :, : self.L].cpu().numpy()
-        return s, p
-
-
-def same(rep, want):
-    """rep: structured reports; want: [(bad, status, row)] from the model."""
-    got = [(int(r["bad_columns"]), int(r["status"]), int(r["row"])) for r in rep]
-    assert got == [tuple(w) for w in want], [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != tuple(w)]
 
 
 CLEAN = (0, sm.CLEAN, -1)

@@ -13,6 +13,7 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+import gpu_family as gf  # noqa: E402
 import rsgpu  # noqa: E402
 import scrub_model as sm  # noqa: E402
 import update_model as um  # noqa: E402
@@ -28,63 +29,35 @@ SDT = rsgpu.SCRUB_REPORT_DTYPE
 
 @pytest.fixture(scope="module")
 def ctx():
-    assert torch.cuda.is_available(), "GPU test needs a HIP device"
-    c = rsgpu.Context(0)
-    c.set_torch_stream()
-    yield c
-    torch.cuda.synchronize()
-    c.close()
+    yield from gf.device_context()
 
 
-def matrix(k, e, kind):
-    return sm.rs_matrix(k, e) if kind == "rs" else sm.cauchy_matrix(k, e)
-
-
-class Stripe:
+class Stripe(gf.DeviceBlocks):
     """B synthetic blocks, their parity and B x u update rows on the device."""
 
     def __init__(self, ctx, k, e, L, B, u, kind="rs", pitch=None, offset=0, parity="consistent", seed=11):
-        self.ctx, self.k, self.e, self.L, self.B, self.u = ctx, k, e, L, B, u
-        self.pitch = pitch or max(256, (L + 255) // 256 * 256)
-        self.c = matrix(k, e, kind)
-        self.coef = None if kind == "rs" else self.c
-        self.dev = dev = torch.device("cuda", 0)
-
-        def alloc(rows):  # at least a byte, so that the pointer is not null
-            t = torch.empty(max(1, B * rows * self.pitch) + offset, dtype=torch.uint8, device=dev)
-            t.fill_(0x6B)  # the padding is not zero
-            return t
-
-        # offset: rows that start `offset` bytes past the allocation's alignment
-        self.src_all, self.par_all, self.upd_all = alloc(k), alloc(e), alloc(u)
-        self.src, self.par, self.upd = self.src_all[offset:], self.par_all[offset:], self.upd_all[offset:]
-        ctx.fill_synthetic(self.src, B * k, L, self.pitch, seed, 0)
+        super().__init__(ctx, k, e, L, B, pitch or max(256, (L + 255) // 256 * 256), offset, kind, seed=seed,
+                         encode=parity == "consistent")
+        self.u = u
+        self.upd_all = self.alloc(u)
+        self.upd = self.upd_all[offset:]
         ctx.fill_synthetic(self.upd, B * u, L, self.pitch, seed + 1000, 0)
-        if parity == "consistent":
-            ctx.encode_blocks(k, e, L, self.pitch, B, self.src, self.par, coef=self.coef)
-        elif e > 0 and L > 0:
+        if parity != "consistent" and e > 0 and L > 0:
             g = torch.Generator(device="cpu").manual_seed(seed)
             rnd = torch.randint(0, 256, (B, e, L), dtype=torch.uint8, generator=g)
-            self.view(self.par, e)[:, :, :L] = rnd.to(dev)
-        self.status = torch.empty(B, dtype=torch.int32, device=dev)
+            self.view(self.par, e)[:, :, :L] = rnd.to(self.dev)
+        self.status = torch.empty(B, dtype=torch.int32, device=self.dev)
         self.cols = np.full((B, u), N, np.uint8)
         torch.cuda.synchronize()
 
-    def view(self, t, rows):
-        return t[: self.B * rows * self.pitch].view(self.B, rows, self.pitch)
-
-    def host(self, t, rows):
-        return self.view(t, rows)[:, :, : self.L].cpu().numpy()
-
     def snapshot(self):
-        return self.src_all.clone(), self.par_all.clone(), self.upd_all.clone()
+        return super().snapshot() + (self.upd_all.clone(),)
 
     def expect(self, delta=False):
         """The model on every block as it is now: (statuses, the source and
         parity allocations as the call must leave them)."""
         src, par, _ = self.snapshot()
-        off = self.src_all.numel() - self.src.numel()
-        sv, pv = self.view(src[off:], self.k), self.view(par[off:], self.e)
+        sv, pv = self.view(src[self.offset:], self.k), self.view(par[self.offset:], self.e)
         hs, hp, hu = self.host(self.src, self.k), self.host(self.par, self.e), self.host(self.upd, self.u)
         status = []
         for b in range(self.B):
@@ -247,7 +220,7 @@ def test_one_block_one_row_equals_the_pointer_form(ctx):
     st = Stripe(ctx, k, e, L0, 1, 1, parity="random")
     st.cols[0, 0] = j
     par0 = st.par_all.clone()
-    a = matrix(k, e, "rs")
+    a = gf.matrix(k, e, "rs")
     g = rsgpu.ec_init_tables(k, e, a)
     delta = st.upd[:L0] ^ st.view(st.src, k)[0, j, :L0]
     other = par0.clone()

@@ -22,37 +22,19 @@ parity rows) at the copy's rate; `over_model` is measured / modelled.
 
     python tools/degraded_measure.py out.json [--k 64 --e 32 --len 1000000 --blocks 1024 --rounds 12]
 """
-import argparse
-import json
-import os
-import sys
+import numpy as np
+import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "..", "storage-benchmarks_amd"))
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
-import rsgpu  # noqa: E402
+import measure_lib as ml  # puts the engine's directory on the path
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("out")
-    ap.add_argument("--k", type=int, default=64)
-    ap.add_argument("--e", type=int, default=32)
-    ap.add_argument("--len", type=int, default=1000000)
-    ap.add_argument("--blocks", type=int, default=1024)
-    ap.add_argument("--rounds", type=int, default=12)
-    a = ap.parse_args()
+    a = ml.shape_parser().parse_args()
     k, e, L, B = a.k, a.e, a.len, a.blocks
 
-    ctx = rsgpu.Context(0)
-    ctx.set_torch_stream()
-    enc = rsgpu.GpuEncoder(k, L, e, blocks=B, seed=5, ctx=ctx)
-    enc.encode_all()
+    ctx, enc = ml.setup(a)
     dev, pitch = enc.src.device, enc.pitch
-    rep = torch.empty(B * rsgpu.SCRUB_REPORT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    rep = ml.reports(enc)
     rng = np.random.default_rng(9)
     lists = {1: (np.arange(B) % (k + e)).astype(np.uint8).reshape(B, 1)}
     for n in (4, 8):
@@ -60,36 +42,19 @@ def main():
     d_lists = {n: torch.from_numpy(v).to(dev) for n, v in lists.items()}
     lost_parity = {n: float((v >= k).sum()) / B for n, v in lists.items()}  # mean |P|
     copy_bytes = (3 + 2 * e) * L * B // 2
-    assert copy_bytes <= enc.src.numel()
-    copy_dst = torch.empty(copy_bytes, dtype=torch.uint8, device=dev)
+    copy = ml.copy_yardstick(enc, copy_bytes)
     scratch_par = torch.empty_like(enc.par)  # the encode kind must not touch the stored parity
     torch.cuda.synchronize()
 
     def timed(fn):
-        ctx.timing_enable(True)
-        try:
-            fn()
-            torch.cuda.synchronize()
-            recs = ctx.timing_read(1 << 16)
-        finally:
-            ctx.timing_enable(False)
-        by = {}
-        for name, ms, _ in recs:
-            by[name] = by.get(name, 0.0) + float(ms)
-        return sum(by.values()), by
+        return ml.timed(ctx, fn)
 
     def run(kind):
         """One timed run: (ms, {kernel name: ms})."""
         if kind == "encode":
             return timed(lambda: ctx.encode_blocks(k, e, L, pitch, B, enc.src, scratch_par))
         if kind == "copy":
-            a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a0.record()
-            copy_dst.copy_(enc.src[:copy_bytes])
-            a1.record()
-            torch.cuda.synchronize()
-            ms = a0.elapsed_time(a1)
-            return ms, {"copy": ms}
+            return copy()
         if kind.startswith("scrub_"):
             ctx.set_scrub_kernel(kind[len("scrub_"):])
             try:
@@ -100,8 +65,7 @@ def main():
         return timed(lambda: ctx.scrub_degraded_blocks(k, e, L, pitch, B, enc.src, enc.par, n, d_lists[n], rep))
 
     def all_clean():
-        r = rep.cpu().numpy().view(rsgpu.SCRUB_REPORT_DTYPE)
-        return bool((r["status"] == rsgpu.SCRUB_CLEAN).all() and (r["bad_columns"] == 0).all())
+        return ml.all_clean(rep)
 
     kinds = ["encode", "degraded_n1", "degraded_n4", "degraded_n8", "scrub_two_pass", "scrub_fused", "copy"]
     kernels_seen = {}
@@ -112,27 +76,9 @@ def main():
         if kind.startswith(("degraded", "scrub")):
             assert all_clean(), kind
 
-    out = {"shape": {"k": k, "e": e, "len": L, "pitch": pitch, "blocks": B},
-           "device": torch.cuda.get_device_name(0), "kernels": kernels_seen,
-           "mean_lost_parity_rows": lost_parity, "runs": []}
-    order = kinds + kinds[::-1]
-    for rnd in range(a.rounds):
-        for pos, kind in enumerate(order):
-            ms, by = run(kind)
-            out["runs"].append({"round": rnd, "pos": pos, "kind": kind, "ms": ms, "kernels": by})
-
-    def stats(v):
-        v = np.array(v)
-        return {"median": float(np.median(v)), "min": float(v.min()), "max": float(v.max()),
-                "stdev": float(v.std(ddof=1)) if len(v) > 1 else 0.0, "n": int(len(v))}
-
-    summ = {}
-    for kind in kinds:
-        runs = [r for r in out["runs"] if r["kind"] == kind]
-        s = stats([r["ms"] for r in runs])
-        names = sorted({n for r in runs for n in r["kernels"]})
-        s["kernel_median_ms"] = {n: float(np.median([r["kernels"].get(n, 0.0) for r in runs])) for n in names}
-        summ[kind] = s
+    out = {**ml.header(enc), "kernels": kernels_seen, "mean_lost_parity_rows": lost_parity,
+           "runs": ml.mirrored_rounds(kinds, a.rounds, run)}
+    summ = ml.summarise(out["runs"], kinds, kernel_medians=True)
     copy_tb = 2 * copy_bytes / (summ["copy"]["median"] * 1e-3) / 1e12
     summ["copy"]["tb_per_s"] = copy_tb
     summ["encode"]["tb_per_s"] = (k + e) * L * B / (summ["encode"]["median"] * 1e-3) / 1e12
@@ -149,10 +95,7 @@ def main():
         s["compare_over_copy_rate"] = s["compare_tb_per_s"] / copy_tb if cmp_ms else None
         s["over_scrub_two_pass"] = s["median"] / summ["scrub_two_pass"]["median"]
         s["over_scrub_fused"] = s["median"] / summ["scrub_fused"]["median"]
-    out["summary"] = summ
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps(summ, indent=1))
+    ml.finish(a.out, out, summ)
     ctx.close()
 
 

@@ -24,17 +24,10 @@ copy's rate; the checked call adds the degraded scrub as measured.
 
     python tools/rebuild_measure.py out.json [--k 64 --e 32 --len 1000000 --blocks 1024 --rounds 12]
 """
-import argparse
-import json
-import os
-import sys
+import numpy as np
+import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "..", "storage-benchmarks_amd"))
-
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
+import measure_lib as ml  # puts the engine's directory on the path
 import rsgpu  # noqa: E402
 
 UNCHECKED = (1, 2, 4, 8)
@@ -42,22 +35,12 @@ CHECKED = (1, 4, 7)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("out")
-    ap.add_argument("--k", type=int, default=64)
-    ap.add_argument("--e", type=int, default=32)
-    ap.add_argument("--len", type=int, default=1000000)
-    ap.add_argument("--blocks", type=int, default=1024)
-    ap.add_argument("--rounds", type=int, default=12)
-    a = ap.parse_args()
+    a = ml.shape_parser().parse_args()
     k, e, L, B = a.k, a.e, a.len, a.blocks
 
-    ctx = rsgpu.Context(0)
-    ctx.set_torch_stream()
-    enc = rsgpu.GpuEncoder(k, L, e, blocks=B, seed=5, ctx=ctx)
-    enc.encode_all()
+    ctx, enc = ml.setup(a)
     dev, pitch = enc.src.device, enc.pitch
-    rep = torch.empty(B * rsgpu.SCRUB_REPORT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    rep = ml.reports(enc)
     rng = np.random.default_rng(9)
     sizes = sorted(set(UNCHECKED) | set(CHECKED))
     lists = {1: (np.arange(B) % (k + e)).astype(np.uint8).reshape(B, 1)}
@@ -66,8 +49,7 @@ def main():
     d_lists = {n: torch.from_numpy(v).to(dev) for n, v in lists.items()}
     lost_parity = {n: float((v >= k).sum()) / B for n, v in lists.items()}  # mean |P|
     copy_bytes = (k + 4) * L * B // 2
-    assert copy_bytes <= enc.src.numel()
-    copy_dst = torch.empty(copy_bytes, dtype=torch.uint8, device=dev)
+    copy = ml.copy_yardstick(enc, copy_bytes)
     # rsgpu_decode_general's output rows, workspace and statuses
     dec_out = torch.empty(B * max(sizes) * pitch, dtype=torch.uint8, device=dev)
     dec_ws = {n: torch.empty(rsgpu.decode_general_workspace_bytes(k, k + e, n, B), dtype=torch.uint8, device=dev)
@@ -76,28 +58,12 @@ def main():
     torch.cuda.synchronize()
 
     def timed(fn):
-        ctx.timing_enable(True)
-        try:
-            fn()
-            torch.cuda.synchronize()
-            recs = ctx.timing_read(1 << 16)
-        finally:
-            ctx.timing_enable(False)
-        by = {}
-        for name, ms, _ in recs:
-            by[name] = by.get(name, 0.0) + float(ms)
-        return sum(by.values()), by
+        return ml.timed(ctx, fn)
 
     def run(kind):
         """One timed run: (ms, {kernel name: ms})."""
         if kind == "copy":
-            a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a0.record()
-            copy_dst.copy_(enc.src[:copy_bytes])
-            a1.record()
-            torch.cuda.synchronize()
-            ms = a0.elapsed_time(a1)
-            return ms, {"copy": ms}
+            return copy()
         what, n = kind.split("_n")
         n = int(n)
         if what == "decode":
@@ -110,8 +76,7 @@ def main():
                                                 check=what == "checked"))
 
     def all_clean():
-        r = rep.cpu().numpy().view(rsgpu.SCRUB_REPORT_DTYPE)
-        return bool((r["status"] == rsgpu.SCRUB_CLEAN).all() and (r["bad_columns"] == 0).all())
+        return ml.all_clean(rep)
 
     kinds = ([f"rebuild_n{n}" for n in UNCHECKED] + [f"checked_n{n}" for n in CHECKED] +
              [f"decode_n{n}" for n in UNCHECKED] + [f"degraded_n{n}" for n in CHECKED] + ["copy"])
@@ -130,27 +95,9 @@ def main():
     torch.cuda.synchronize()
     assert all_clean(), "the blocks after the rebuilds"
 
-    out = {"shape": {"k": k, "e": e, "len": L, "pitch": pitch, "blocks": B},
-           "device": torch.cuda.get_device_name(0), "kernels": kernels_seen,
-           "mean_lost_parity_rows": lost_parity, "runs": []}
-    order = kinds + kinds[::-1]
-    for rnd in range(a.rounds):
-        for pos, kind in enumerate(order):
-            ms, by = run(kind)
-            out["runs"].append({"round": rnd, "pos": pos, "kind": kind, "ms": ms, "kernels": by})
-
-    def stats(v):
-        v = np.array(v)
-        return {"median": float(np.median(v)), "min": float(v.min()), "max": float(v.max()),
-                "stdev": float(v.std(ddof=1)) if len(v) > 1 else 0.0, "n": int(len(v))}
-
-    summ = {}
-    for kind in kinds:
-        runs = [r for r in out["runs"] if r["kind"] == kind]
-        s = stats([r["ms"] for r in runs])
-        names = sorted({n for r in runs for n in r["kernels"]})
-        s["kernel_median_ms"] = {n: float(np.median([r["kernels"].get(n, 0.0) for r in runs])) for n in names}
-        summ[kind] = s
+    out = {**ml.header(enc), "kernels": kernels_seen, "mean_lost_parity_rows": lost_parity,
+           "runs": ml.mirrored_rounds(kinds, a.rounds, run)}
+    summ = ml.summarise(out["runs"], kinds, kernel_medians=True)
     copy_tb = 2 * copy_bytes / (summ["copy"]["median"] * 1e-3) / 1e12
     summ["copy"]["tb_per_s"] = copy_tb
     for n in UNCHECKED:
@@ -168,25 +115,8 @@ def main():
         s["model_ms"] = summ[f"degraded_n{n}"]["median"] + (k + n) * L * B / (copy_tb * 1e12) * 1e3
         s["over_model"] = s["median"] / s["model_ms"]
         s["over_degraded"] = s["median"] / summ[f"degraded_n{n}"]["median"]
-    out["summary"] = summ
-    with open(a.out, "w") as f:
-        f.write(dumps(out))
-    print(json.dumps(summ, indent=1))
+    ml.finish(a.out, out, summ)
     ctx.close()
-
-
-def dumps(out):
-    """The result as JSON with one line per run and per summarised kind."""
-    runs, summ = out["runs"], out["summary"]
-    head = {key: v for key, v in out.items() if key not in ("runs", "summary")}
-    lines = ["{"] + [f" {json.dumps(key)}: {json.dumps(v)}," for key, v in head.items()]
-    lines.append(' "runs": [')
-    lines += ["  " + json.dumps(r) + ("," if i + 1 < len(runs) else "") for i, r in enumerate(runs)]
-    lines.append(' ],\n "summary": {')
-    lines += [f"  {json.dumps(kind)}: {json.dumps(s)}" + ("," if i + 1 < len(summ) else "")
-              for i, (kind, s) in enumerate(summ.items())]
-    lines.append(" }\n}\n")
-    return "\n".join(lines)
 
 
 if __name__ == "__main__":

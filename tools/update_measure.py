@@ -17,81 +17,49 @@ the rounds: the per-block loop over rsgpu_ec_encode_data_update for u = 1.
 
     python tools/update_measure.py out.json [--k 64 --e 32 --len 1000000 --blocks 1024 --rounds 12]
 """
-import argparse
-import json
-import os
-import sys
 import time
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "..", "storage-benchmarks_amd"))
+import numpy as np
+import torch
 
-import numpy as np  # noqa: E402
-import torch  # noqa: E402
-
+import measure_lib as ml  # puts the engine's directory on the path
 import rsgpu  # noqa: E402
 
 GROUP = 8  # rows of a list one walk over the parity serves (rs_update.hip)
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("out")
-    ap.add_argument("--k", type=int, default=64)
-    ap.add_argument("--e", type=int, default=32)
-    ap.add_argument("--len", type=int, default=1000000)
-    ap.add_argument("--blocks", type=int, default=1024)
-    ap.add_argument("--rounds", type=int, default=12)
+    ap = ml.shape_parser()
     ap.add_argument("--counts", default="1,4,8,9,16,32")
     a = ap.parse_args()
     k, e, L, B = a.k, a.e, a.len, a.blocks
     counts = [int(x) for x in a.counts.split(",")]
     umax = max(counts)
 
-    ctx = rsgpu.Context(0)
-    ctx.set_torch_stream()
-    enc = rsgpu.GpuEncoder(k, L, e, blocks=B, seed=5, ctx=ctx)
-    enc.encode_all()
+    ctx, enc = ml.setup(a)
     dev, pitch = enc.src.device, enc.pitch
     upd = torch.empty(B * umax * pitch, dtype=torch.uint8, device=dev)
     ctx.fill_synthetic(upd, B * umax, L, pitch, 77, 0)
     status = torch.empty(B, dtype=torch.int32, device=dev)
-    srep = torch.empty(B * rsgpu.SCRUB_REPORT_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    srep = ml.reports(enc)
     rng = np.random.default_rng(9)
     lists = {u: np.stack([np.sort(rng.choice(k, u, replace=False)) for _ in range(B)]).astype(np.uint8)
              for u in counts}
     d_lists = {u: torch.from_numpy(v).to(dev) for u, v in lists.items()}
     # the copy: as many bytes as the u = 1 update moves, half read, half written
     copy_bytes = (3 + 2 * e) * L * B // 2
-    assert copy_bytes <= enc.src.numel()
-    copy_dst = torch.empty(copy_bytes, dtype=torch.uint8, device=dev)
+    copy = ml.copy_yardstick(enc, copy_bytes)
     torch.cuda.synchronize()
 
     def timed(fn):
-        ctx.timing_enable(True)
-        try:
-            fn()
-            torch.cuda.synchronize()
-            recs = ctx.timing_read()
-        finally:
-            ctx.timing_enable(False)
-        by = {}
-        for name, ms, _ in recs:
-            by[name] = by.get(name, 0.0) + float(ms)
-        return sum(by.values()), by
+        return ml.timed(ctx, fn)
 
     def run(kind):
         """One timed run: (ms, {kernel name: ms})."""
         if kind == "encode":
             return timed(lambda: ctx.encode_blocks(k, e, L, pitch, B, enc.src, enc.par))
         if kind == "copy":
-            a0, a1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a0.record()
-            copy_dst.copy_(enc.src[:copy_bytes])
-            a1.record()
-            torch.cuda.synchronize()
-            ms = a0.elapsed_time(a1)
-            return ms, {"copy": ms}
+            return copy()
         delta = kind.endswith("_delta")
         u = int(kind.split("_")[1][1:])
         return timed(lambda: ctx.update_blocks(k, e, L, pitch, B, u, d_lists[u], upd, None if delta else enc.src,
@@ -100,8 +68,7 @@ def main():
     def all_clean():
         ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, srep)
         torch.cuda.synchronize()
-        r = srep.cpu().numpy().view(rsgpu.SCRUB_REPORT_DTYPE)
-        return bool((r["status"] == rsgpu.SCRUB_CLEAN).all())
+        return ml.all_clean(srep)
 
     kinds = ["encode"] + [f"update_u{u}" for u in counts] + ["update_u1_delta", "copy"]
     # untimed and checked, one run of each kind
@@ -115,13 +82,7 @@ def main():
             run(kind)               # the same deltas again cancel
         assert all_clean(), kind
 
-    out = {"shape": {"k": k, "e": e, "len": L, "pitch": pitch, "blocks": B},
-           "device": torch.cuda.get_device_name(0), "runs": []}
-    order = kinds + kinds[::-1]
-    for rnd in range(a.rounds):
-        for pos, kind in enumerate(order):
-            ms, by = run(kind)
-            out["runs"].append({"round": rnd, "pos": pos, "kind": kind, "ms": ms, "kernels": by})
+    out = {**ml.header(enc), "runs": ml.mirrored_rounds(kinds, a.rounds, run)}
     assert all_clean(), "after the rounds"
 
     # once: the pointer form, one call per block, u = 1 (the update row taken
@@ -148,11 +109,6 @@ def main():
     loop()
     assert all_clean(), "after the pointer form"
 
-    def stats(v):
-        v = np.array(v)
-        return {"median": float(np.median(v)), "min": float(v.min()), "max": float(v.max()),
-                "stdev": float(v.std(ddof=1)) if len(v) > 1 else 0.0, "n": int(len(v))}
-
     def rows_moved(kind):
         """Rows of len bytes per block, read plus written (the byte model)."""
         if kind == "encode":
@@ -163,13 +119,12 @@ def main():
         passes = (u + GROUP - 1) // GROUP
         return (u if kind.endswith("_delta") else 3 * u) + 2 * e * passes
 
-    summ = {}
+    summ = ml.summarise(out["runs"], kinds)
     for kind in kinds:
-        s = stats([r["ms"] for r in out["runs"] if r["kind"] == kind])
+        s = summ[kind]
         s["rows_moved_per_block"] = rows_moved(kind)
         s["bytes"] = rows_moved(kind) * L * B
         s["tb_per_s"] = s["bytes"] / (s["median"] * 1e-3) / 1e12
-        summ[kind] = s
     copy_rate = summ["copy"]["tb_per_s"]
     for kind in kinds:
         summ[kind]["rate_over_copy"] = summ[kind]["tb_per_s"] / copy_rate
@@ -189,10 +144,7 @@ def main():
                           "u1_over_copy": sum(t["update_u1"]) / sum(t["copy"])})
     summ["per_round"] = per_round
     summ["u1_faster_than_encode_in_every_round"] = all(r["u1_faster_than_encode"] for r in per_round)
-    out["summary"] = summ
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print(json.dumps(summ, indent=1))
+    ml.finish(a.out, out, summ)
     ctx.close()
 
 
