@@ -429,9 +429,11 @@ int rsgpu_scrub_degraded_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t
  *
  * Layout, `coef` and d_lost exactly as rsgpu_scrub_degraded_blocks: [blocks][u]
  * bytes, rows in [0, k + e) strictly ascending, then RSGPU_LOST_NONE; n may
- * differ from block to block.  Any len, any pitch >= len, any alignment.  u is
- * in [1, 8] without RSGPU_REBUILD_CHECK and in [1, 7] with it: the located row
- * may join the list, and a lane holds at most 8 output rows.  d_report
+ * differ from block to block.  Any len, any pitch >= len, any alignment.
+ * Without RSGPU_REBUILD_CHECK u is in [1, max(8, min(e, RSGPU_REBUILD_MAX_LOST))]:
+ * everything up to 8, and beyond 8 a list as long as the code has parity rows,
+ * up to 32; with RSGPU_REBUILD_CHECK u is in [1, 7]: the located row may join
+ * the list, and the degraded scrub holds at most 8 rows per lane.  d_report
  * [blocks] is the 16-byte rsgpu_scrub_report, DEVICE memory, 8-byte aligned,
  * overwritten by every call.
  *
@@ -495,19 +497,56 @@ int rsgpu_scrub_degraded_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t
  * lane the kernel is bound by its arithmetic (172 instructions per 16-byte
  * column and source).  rsgpu_decode_general with the same uniform lists took
  * 11.9 / 12.2 / 13.2 / 15.5 ms: equal at one row, 5 % and 9 % faster at two
- * and four, 1.48 x faster at eight.  A caller whose blocks ALL have many (7,
- * 8) lost rows and whose survivors are trusted is better served by
- * rsgpu_decode_general plus a copy of the rows back; this call is for lists
- * that differ from block to block, for rows that should come back in place,
- * and for the check.  Checked, with clean survivors: 46.8 ms (n = 1), 51.2 ms
- * (n = 4), 58.5 ms (n = 7), the degraded scrub alone being 34.9 / 36.5 / 38.0
- * ms.  Not built: host-resident blocks, a bit-sliced or generated-code form
- * for many lost rows per block, and more than one located row per block. */
+ * and four, 1.48 x faster at eight.  Checked, with clean survivors: 46.8 ms
+ * (n = 1), 51.2 ms (n = 4), 58.5 ms (n = 7), the degraded scrub alone being
+ * 34.9 / 36.5 / 38.0 ms.
+ *
+ * Lists of more than 8 rows, and rsgpu_set_rebuild_kernel below: LANES runs
+ * k_rebuild_blocks in passes of at most 8 outputs, one more walk over the k
+ * sources each; THREADED runs k_rs_tc, the bit-sliced threaded code of the
+ * encode and decode, once for up to 32 rows, with a row count per block and
+ * the rows written in place, after k_rebuild_wide_prepare (one wave per block,
+ * the elimination spread over the wave) has written its row pointers and
+ * handler addresses, 16 KB per block at k = 64, into a context-owned buffer of
+ * at most 64 MiB per group of blocks.  Measured in one process at the same
+ * shape with the same n rows lost in every block (profiles/rebuild_wide; the
+ * copy ran at 4.85 TB/s), n = 8 / 16 / 32: THREADED 21.1 / 22.0 / 28.7 ms, LANES
+ * 23.1 / 45.8 / 92.3 ms, THREADED the faster one in every mirrored pair;
+ * rsgpu_decode_general with the same lists 16.3 / 18.2 / 23.6 ms; lists of 0 to
+ * 32 rows mixed in one call: THREADED 22.5 ms, LANES 55.0 ms; the wide prepare
+ * 0.1 / 0.2 / 0.6 ms of the call.  AUTO therefore takes THREADED above 8 rows
+ * and, for now, leaves u + check <= 8 on LANES.  A caller whose blocks ALL
+ * lose the same number of rows, whose survivors are trusted and who does not
+ * need the rows in place is served 1.2 - 1.3 x faster by rsgpu_decode_general;
+ * this call is for lists that differ from block to block, for rows that
+ * should come back in place, and for the check.  Not built: host-resident
+ * blocks, a generated-code form, the check with more than 7 listed rows, lists
+ * of more than 32 rows, and more than one located row per block. */
 #define RSGPU_REBUILD_CHECK 1 /* flags: scrub the survivors first, let the verdict decide */
+#define RSGPU_REBUILD_MAX_LOST 32 /* the longest list without RSGPU_REBUILD_CHECK (and at most e) */
 int rsgpu_rebuild_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                          unsigned char *d_src, unsigned char *d_parity,
                          const unsigned char *coef, int u, const unsigned char *d_lost,
                          int flags, rsgpu_scrub_report *d_report);
+
+/* Kernel of rsgpu_rebuild_blocks (per context; every choice writes the same
+ * bytes and reports):
+ *   AUTO      LANES whenever u + check <= 8; for longer lists THREADED where
+ *             it applies, otherwise LANES
+ *   LANES     k_rebuild_blocks: a lane holds up to 8 outputs of its column;
+ *             lists longer than 8 run in passes of at most 8 outputs, each one
+ *             more walk over the k sources (the passes are independent: no row
+ *             is both read and written); any layout
+ *   THREADED  k_rs_tc, the bit-sliced threaded code of the encode and decode,
+ *             with a row count per block and the rows written in place; needs
+ *             pitch % 16 == 0, 16-byte aligned d_src and d_parity and
+ *             32 <= len < 4 GiB; covers the columns [0, len - len % 32), the
+ *             last len % 32 bytes of every row go through LANES' byte form
+ * A choice that does not apply falls back to LANES. */
+#define RSGPU_REBUILD_AUTO 0
+#define RSGPU_REBUILD_LANES 1
+#define RSGPU_REBUILD_THREADED 2
+int rsgpu_set_rebuild_kernel(rsgpu_ctx *ctx, int kernel);
 
 /* ---- repair in place of what the scrub locates ---------------------------- */
 

@@ -433,4 +433,35 @@ hipError_t launch_rebuild_prepare(const RebuildArgs& a, hipStream_t st);
 // rows; bytes == true: byte columns, any alignment
 hipError_t launch_rebuild_blocks(const RebuildArgs& a, bool bytes, long long col0, long long col1, hipStream_t st);
 
+// Lists of up to RSGPU_REBUILD_MAX_LOST rows (k_rebuild_wide_prepare): the
+// list judged, the verdict taken, Q chosen and c[Q][D] inverted as
+// k_rebuild_prepare does, the elimination spread over the wave, and the k x n
+// matrix of factors M formed by the same formulas.  Per block it writes
+//   passes > 0  `passes` consecutive tables in k_rebuild_prepare's layout at
+//               r.tab + b r.tab_stride (r.tab_stride >= passes x
+//               rebuild_tab_stride(k)): table p serves outputs [8 p, 8 p + 8)
+//               and has state != kRebRun when the block has none of them, so
+//               k_rebuild_blocks runs once per pass with r.tab advanced
+//   slots > 0   k_rs_tc's inputs: srcs [B][k] the source rows, dsts [B][slots]
+//               the rows to write (null beyond the block's n), addr
+//               [B][k][slots] = tc_table[(o & 7) * 256 + M[s][o]] with padding
+//               slots at handler 0, and count [B] = n, 0 for a block that is
+//               not rebuilt (its srcs, dsts and addr are then not written)
+// slots = tc_rows_per_pass(most), most = min(u + check, e) <= 32.
+struct RebuildWideArgs {
+    RebuildArgs r;  // g unused
+    int passes, slots;
+    const unsigned long long* tc_table;  // the context's handler addresses [8][256]
+    const uint8_t** srcs;
+    uint8_t** dsts;
+    unsigned long long* addr;
+    int* count;
+};
+hipError_t launch_rebuild_wide_prepare(const RebuildWideArgs& a, hipStream_t st);
+// k_rs_tc with a row count per block: a.status[b] (required) is the number of
+// rows of block b to write, 0 skipping the block; a.rows, the most any block
+// has, chooses the waves.  Rows are written where dsts says: in place is safe
+// as long as no destination row is a source.
+hipError_t launch_rs_tc_counted(const TcArgs& a, long long blocks, hipStream_t st);
+
 }  // namespace rsgpu

@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 #include "../../include/rsgpu.h"
 #include "gf256.h"
 #include "rs_kernels.h"
@@ -174,6 +176,161 @@ __device__ __forceinline__ uint8_t* block_row(uint8_t* srcb, uint8_t* parb, int 
     return r < k ? srcb + (long long)r * pitch : parb + (long long)(r - k) * pitch;
 }
 
+// ---------------------------------------------------------------------------
+// k_rebuild_wide_prepare: lists of up to kWide rows, one wave per block.  Lane
+// 0 judges the list and takes the verdict as k_rebuild_prepare does; the pivot
+// walk and the elimination run on the whole wave (rs_pivots.h
+// lost_pivots_wave); then a source per lane forms its row of the k x n matrix
+// of factors M in LDS, by k_rebuild_prepare's formulas, and the wave writes
+// what the kernels read: the lane tables of the passes of 8 outputs
+// (k_rebuild_blocks) and the row pointers, handler addresses and row count of
+// the threaded code (rs_tc.hip k_rs_tc, TcHooksPerBlock).
+// ---------------------------------------------------------------------------
+constexpr int kWide = RSGPU_REBUILD_MAX_LOST;
+
+__global__ __launch_bounds__(64) void k_rebuild_wide_prepare(RebuildWideArgs wa)
+{
+    __shared__ PivotWave<kWide> w;
+    __shared__ uint8_t rows[kWide];       // the rows to write, ascending
+    __shared__ uint8_t srcl[256];         // the k source rows: S ascending, then k + Q
+    __shared__ uint8_t mf[256][kWide];    // M[s][o]
+    __shared__ int sh_go, sh_n, sh_status;
+
+    const RebuildArgs& a = wa.r;
+    const long long b = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int k = a.k, e = a.e, m = a.k + a.e;
+    const uint8_t* list = a.lost + b * a.u;
+
+    for (int r = lane; r < 256; r += 64)
+        w.lost[r] = 0;
+    if (lane == 0) {
+        int n = lost_list_rows(list, a.u, m, e);
+        bool go = false;
+        sh_status = RSGPU_SCRUB_CLEAN;
+        if (n < 0) {
+            n = 0;
+            sh_status = RSGPU_SCRUB_BAD_LIST;
+        } else if (a.work) {
+            for (int i = 0; i < n; ++i)
+                rows[i] = list[i];
+            go = true;
+            if (a.check) {
+                const rsgpu_scrub_report r = a.report[b];
+                if (r.status == RSGPU_SCRUB_ONE_ROW) {
+                    // the located row joins the list, which stays ascending
+                    go = r.row >= 0 && r.row < m && n < kWide && n < e;
+                    int at = 0;
+                    while (go && at < n && rows[at] < r.row)
+                        ++at;
+                    go = go && (at == n || rows[at] != r.row);
+                    if (go) {
+                        for (int i = n; i > at; --i)
+                            rows[i] = rows[i - 1];
+                        rows[at] = (uint8_t)r.row;
+                        ++n;
+                    }
+                } else if (r.status != RSGPU_SCRUB_CLEAN && r.status != RSGPU_SCRUB_UNCHECKED) {
+                    go = false;  // DAMAGED, BAD_MATRIX: the scrub's report is final
+                }
+            }
+            go = go && n > 0;
+        }
+        sh_go = go ? 1 : 0;
+        sh_n = n;
+    }
+    __syncthreads();
+    const int n = sh_n;
+    int nd = -2;  // -2: the matrix is not looked at
+    if (sh_go)
+        nd = lost_pivots_wave(w, rows, n, a.coef, k, e, lane);
+    const bool run = nd >= 0;
+    if (lane == 0) {
+        // without check every report is written here; with check only the one
+        // verdict the scrub does not reach: BAD_MATRIX of a list with n == e
+        if (nd == -1 || !a.check) {
+            rsgpu_scrub_report r;
+            r.bad_columns = 0;
+            r.status = nd == -1 ? RSGPU_SCRUB_BAD_MATRIX : sh_status;
+            r.row = -1;
+            a.report[b] = r;
+        }
+        if (wa.slots > 0)
+            wa.count[b] = run ? n : 0;
+        if (run) {
+            int ns = 0;
+            for (int j = 0; j < k; ++j)
+                if (!w.lost[j])
+                    srcl[ns++] = (uint8_t)j;
+            for (int q = 0; q < nd; ++q)
+                srcl[ns++] = (uint8_t)(k + w.ql[q]);
+        }
+    }
+    // the lane tables' headers: a pass the block has no row of does not run
+    const size_t pass_stride = sizeof(RebuildHdr) + a.src_bytes + (size_t)k * 8;  // rebuild_tab_stride(k)
+    uint8_t* tab0 = a.tab + (size_t)b * a.tab_stride;
+    for (int p = lane; p < wa.passes; p += 64) {
+        RebuildHdr* hdr = reinterpret_cast<RebuildHdr*>(tab0 + (size_t)p * pass_stride);
+        const int np = run ? (n - 8 * p < 8 ? n - 8 * p : 8) : 0;
+        hdr->state = np > 0 ? kRebRun : kRebStop;
+        hdr->nout = (uint8_t)(np > 0 ? np : 0);
+        for (int i = 0; i < 8; ++i)
+            hdr->out[i] = i < np ? rows[8 * p + i] : 0;
+    }
+    if (!run)
+        return;  // uniform
+    __syncthreads();
+    for (int s = lane; s < k; s += 64) {
+        const int r = srcl[s];
+        // the factor of source s in lost data row D_i
+        for (int i = 0; i < nd; ++i) {
+            uint8_t x = 0;
+            if (r < k) {
+                for (int q = 0; q < nd; ++q)
+                    x ^= gf_mul_slow(w.inv(i, q), a.coef[(size_t)w.ql[q] * k + r]);
+            } else {
+                x = w.inv(i, s - (k - nd));
+            }
+            mf[s][i] = x;
+        }
+        // outputs: the rows of D first (the list is ascending), then parity rows
+        for (int o = nd; o < kWide; ++o) {
+            uint8_t x = 0;
+            if (o < n) {
+                const size_t p = (size_t)(rows[o] - k) * k;
+                x = r < k ? a.coef[p + r] : 0;
+                for (int i = 0; i < nd; ++i)
+                    x ^= gf_mul_slow(a.coef[p + w.dl[i]], mf[s][i]);
+            }
+            mf[s][o] = x;
+        }
+    }
+    __syncthreads();
+    uint8_t* srcb = a.src + b * k * a.pitch;
+    uint8_t* parb = a.par + b * e * a.pitch;
+    for (int p = 0; p < wa.passes && 8 * p < n; ++p) {
+        uint8_t* tab = tab0 + (size_t)p * pass_stride;
+        uint8_t* t_src = tab + sizeof(RebuildHdr);
+        uint8_t* t_m = t_src + a.src_bytes;
+        for (int s = lane; s < k; s += 64)
+            t_src[s] = srcl[s];
+        for (int idx = lane; idx < k * 8; idx += 64)
+            t_m[idx] = mf[idx >> 3][8 * p + (idx & 7)];
+    }
+    if (wa.slots > 0) {
+        const int slots = wa.slots;
+        for (int s = lane; s < k; s += 64)
+            wa.srcs[(size_t)b * k + s] = block_row(srcb, parb, srcl[s], k, a.pitch);
+        for (int o = lane; o < slots; o += 64)
+            wa.dsts[(size_t)b * slots + o] = o < n ? block_row(srcb, parb, rows[o], k, a.pitch) : nullptr;
+        unsigned long long* ad = wa.addr + (size_t)b * k * slots;
+        for (int idx = lane; idx < k * slots; idx += 64) {
+            const int s = idx / slots, o = idx - s * slots;
+            ad[idx] = wa.tc_table[(o & 7) * 256 + (o < n ? mf[s][o] : 0)];
+        }
+    }
+}
+
 // A rebuilt column: nobody reads it again soon, so the 16-byte store is
 // non-temporal (1 - 3 % of the call at one or two rows per block, nothing at
 // eight; profiles/rebuild).
@@ -307,6 +464,24 @@ hipError_t launch_rebuild_prepare(const RebuildArgs& a, hipStream_t st)
     if (!args_ok(a) || (a.work && !a.coef) || (a.check && a.u > 7))
         return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_rebuild_prepare, dim3((unsigned)a.blocks), dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_rebuild_wide_prepare(const RebuildWideArgs& wa, hipStream_t st)
+{
+    const RebuildArgs& a = wa.r;
+    const int most = std::min(a.u + (a.check ? 1 : 0), a.e);
+    if (a.blocks <= 0 || a.blocks > (long long)kMaxGridBlocks || a.k <= 0 || a.e < 0 ||
+        a.k + a.e > RSGPU_MAX_SOURCES || a.u < 1 || a.u > kWide || (a.check && a.u > 7) || !a.lost || !a.report ||
+        (a.work && (!a.coef || !a.src || !a.par)) || wa.passes < 0 || wa.slots < 0)
+        return hipErrorInvalidValue;
+    if (wa.passes > 0 && (!a.work || !a.tab || wa.passes * 8 < most || a.src_bytes != rebuild_src_bytes(a.k) ||
+                          a.tab_stride < (size_t)wa.passes * rebuild_tab_stride(a.k)))
+        return hipErrorInvalidValue;
+    if (wa.slots > 0 && (!a.work || wa.slots != tc_rows_per_pass(most) || wa.slots > kWide || !wa.tc_table ||
+                         !wa.srcs || !wa.dsts || !wa.addr || !wa.count))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_rebuild_wide_prepare, dim3((unsigned)a.blocks), dim3(64), 0, st, wa);
     return hipGetLastError();
 }
 

@@ -100,6 +100,19 @@ struct TcHooks {
     };
 };
 
+// How many rows of a block k_rs_tc writes is part of its policy H.  TcHooks:
+// a.rows of every block that a.status (when given) does not skip.  A policy
+// with a member `per_block` (TcHooksPerBlock: the wide rebuild, rs_rebuild.hip):
+// a.status[b] is block b's own count, and a block with none leaves as a whole
+// workgroup before any load.  A wave whose 8 rows all lie beyond the count
+// still loads and transposes its share of every chunk; its handler addresses
+// are the padding's (handler 0), and it stores nothing.
+struct TcHooksPerBlock : TcHooks {
+    static constexpr bool per_block = true;
+};
+template <class H>
+constexpr bool tc_per_block = requires { H::per_block; };
+
 // Read accumulator slot S (asm-owned v[64+8S : 64+8S+7]) into W, two planes
 // per v_mov_b64.
 template <int S>
@@ -134,8 +147,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void 
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const int b = blockIdx.y;
-    if (a.status && a.status[b] != 0)
-        return;  // uniform per workgroup: the whole block is skipped
+    int own_rows = 0;
+    if constexpr (tc_per_block<H>) {
+        own_rows = __builtin_amdgcn_readfirstlane(a.status[b]);
+        if (own_rows <= 0)
+            return;  // uniform per workgroup: nothing of this block is written
+    } else {
+        if (a.status && a.status[b] != 0)
+            return;  // uniform per workgroup: the whole block is skipped
+    }
     // this workgroup's consecutive 2 KB column tiles of block b
     const long long ntile = (a.len + 2047) / 2048;
     const long long tile0 = (long long)blockIdx.x * tiles_per_wg;
@@ -235,7 +255,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void 
                     (
                         [&] {
                             const int r = wave * 8 + Ss;
-                            if (r < a.rows) {
+                            if (r < (tc_per_block<H> ? own_rows : a.rows)) {
                                 uint32_t W[8];
                                 read_slot<Ss>(W);
                                 tr8(W, m4, m2, m1);
@@ -617,6 +637,24 @@ hipError_t launch_rs_tc(const TcArgs& a, long long blocks, hipStream_t st)
     case 2: hipLaunchKernelGGL(tc::k_rs_tc<2>, grid, dim3(128), pad, st, a, tpw); break;
     case 3: hipLaunchKernelGGL(tc::k_rs_tc<3>, grid, dim3(192), pad, st, a, tpw); break;
     case 4: hipLaunchKernelGGL(tc::k_rs_tc<4>, grid, dim3(256), pad, st, a, tpw); break;
+    default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_rs_tc_counted(const TcArgs& a, long long blocks, hipStream_t st)
+{
+    const int nw = tc_rows_per_pass(a.rows) / 8;
+    if (a.rows <= 0 || a.rows > 32 || a.k <= 0 || !a.status || a.len <= 0 || a.len % 32 || blocks <= 0 ||
+        blocks > (long long)kMaxGridBlocks || a.dst_stride < a.rows)
+        return hipErrorInvalidValue;
+    dim3 grid((unsigned)((a.len + 2047) / 2048), (unsigned)blocks);
+    using P = tc::TcHooksPerBlock;
+    switch (nw) {
+    case 1: hipLaunchKernelGGL((tc::k_rs_tc<1, P>), grid, dim3(64), 0, st, a, 1); break;
+    case 2: hipLaunchKernelGGL((tc::k_rs_tc<2, P>), grid, dim3(128), 0, st, a, 1); break;
+    case 3: hipLaunchKernelGGL((tc::k_rs_tc<3, P>), grid, dim3(192), 0, st, a, 1); break;
+    case 4: hipLaunchKernelGGL((tc::k_rs_tc<4, P>), grid, dim3(256), 0, st, a, 1); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

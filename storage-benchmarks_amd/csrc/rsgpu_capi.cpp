@@ -176,6 +176,16 @@ int tc_init(rsgpu_ctx* ctx)
 
 bool tc_ready(rsgpu_ctx* ctx) { return tc_init(ctx) == 1; }
 
+}  // namespace
+
+namespace rsgpu {
+
+bool tc_handlers_ready(rsgpu_ctx* ctx) { return tc_ready(ctx); }
+
+}  // namespace rsgpu
+
+namespace {
+
 hsa_status_t pick_coarse_pool(hsa_amd_memory_pool_t p, void* out)
 {
     hsa_amd_segment_t seg;

@@ -95,6 +95,18 @@ struct rsgpu_ctx {
     // rebuild in place (rsgpu_rebuild_blocks): the per-block tables
     // k_rebuild_prepare writes for one group of blocks
     DevBuf rebuild;
+    // its kernel choice (rsgpu_set_rebuild_kernel), and of the wide lists'
+    // tables (RebuildWideArgs) the layout of the last group, which the test
+    // hooks read: offsets into rebuild.p, 0 bytes = none written yet
+    int rebuild_kernel = RSGPU_REBUILD_AUTO;
+    struct RebuildWideLayout {
+        size_t blocks = 0, lane = 0, lane_stride = 0, addr = 0, srcs = 0, dsts = 0, count = 0;
+        int k = 0, passes = 0, slots = 0;
+    } rebuild_wide;
+    // test hooks (rsgpu_testhooks.cpp): blocks per group of the wide lists
+    // (0: the 64 MiB rule), and stop after the wide prepare
+    size_t rebuild_group_max = 0;
+    bool rebuild_prepare_only = false;
     // pinned host staging for small uploads, guarded by an event
     void* h_stage = nullptr;
     size_t stage_bytes = 0;

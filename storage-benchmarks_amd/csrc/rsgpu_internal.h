@@ -27,6 +27,10 @@ int upload(rsgpu_ctx* ctx, void* d_dst, size_t bytes, size_t dst_off = 0, size_t
 
 hipEvent_t pool_event(rsgpu_ctx* ctx);
 
+// the handler table of k_rs_tc (rs_tc.hip) is located and ctx->d_tc_table holds
+// its addresses; probed once per context
+bool tc_handlers_ready(rsgpu_ctx* ctx);
+
 // Brackets one kernel launch with events when timing is enabled.
 struct KTimer {
     rsgpu_ctx* ctx;

@@ -252,6 +252,132 @@ bool ranges_overlap(const void* a, size_t an, const void* b, size_t bn)
 // the computed parity is: a slice holds no more blocks than fit kDegTabBytes.
 constexpr size_t kDegTabBytes = 64u << 20;
 
+constexpr const char* kRebuildPassNames[3] = {"k_rebuild_blocks(pass)", "k_rebuild_blocks(pass)",
+                                              "k_rebuild_blocks(pass)"};
+
+size_t round16(size_t n) { return (n + 15) / 16 * 16; }
+
+// The rebuild of lists that the narrow prepare does not take (u > 8), and of
+// any list under THREADED.  Per group of blocks: k_rebuild_wide_prepare, then
+//   threaded   k_rs_tc with a row count per block over [0, len - len % 32) and
+//              k_rebuild_blocks' byte form, in passes of 8 outputs, over the
+//              bytes that leaves
+//   otherwise  k_rebuild_blocks in passes of 8 outputs over all of len
+// A group's tables (lane tables of the passes; handler addresses, row pointers
+// and counts of the threaded code) fit kDegTabBytes, its blocks fit a grid.
+int rebuild_wide(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks, unsigned char* d_src,
+                 unsigned char* d_parity, const unsigned char* coef, int u, const unsigned char* d_lost, bool check,
+                 bool threaded, rsgpu_scrub_report* d_report)
+{
+    const bool work = e > 0 && len > 0;
+    const int most = std::min(u + (check ? 1 : 0), e);  // rows of any block's list as it is rebuilt
+    const size_t len32 = threaded ? len - len % 32 : 0;
+    const int slots = threaded ? tc_rows_per_pass(most) : 0;
+    const int passes = work && len32 < len ? (most + 7) / 8 : 0;
+    const size_t lane_stride = (size_t)passes * rebuild_tab_stride(k);
+    const size_t per_block = lane_stride + ((size_t)k * slots + k + slots) * 8 + (slots ? 4 : 0);
+    const size_t fit = kDegTabBytes / std::max<size_t>(1, per_block);
+    size_t group = std::max<size_t>(1, std::min({blocks, kMaxGridBlocks, fit}));
+    if (ctx->rebuild_group_max)
+        group = std::min(group, ctx->rebuild_group_max);
+    rsgpu_ctx::RebuildWideLayout lay;
+    lay.blocks = group;
+    lay.k = k;
+    lay.passes = passes;
+    lay.slots = slots;
+    lay.lane = 0;
+    lay.lane_stride = lane_stride;
+    lay.addr = round16(group * lane_stride);
+    lay.srcs = lay.addr + group * (size_t)k * slots * 8;
+    lay.dsts = lay.srcs + (slots ? group * (size_t)k * 8 : 0);
+    lay.count = lay.dsts + group * (size_t)slots * 8;
+    int rc = ensure_device(ctx, ctx->rebuild, lay.count + group * 4 + 16);
+    if (rc)
+        return rc;
+    ctx->rebuild_wide = lay;
+    if (work) {
+        // the v_perm tables of every coefficient value and the matrix, on the device
+        rc = update_tables(ctx, k, e, coef);
+        if (rc)
+            return rc;
+    }
+    char* base = (char*)ctx->rebuild.p;
+    for (size_t g0 = 0; g0 < blocks; g0 += group) {
+        const size_t ng = std::min(group, blocks - g0);
+        RebuildWideArgs wa{};
+        RebuildArgs& a = wa.r;
+        a.k = k;
+        a.e = e;
+        a.u = u;
+        a.check = check && work ? 1 : 0;
+        a.work = work ? 1 : 0;
+        a.pitch = (long long)pitch;
+        a.len = (long long)len;
+        a.blocks = (long long)ng;
+        a.lost = d_lost + g0 * (size_t)u;
+        a.tab = passes ? (uint8_t*)base + lay.lane : nullptr;
+        a.tab_stride = lane_stride;
+        a.src_bytes = rebuild_src_bytes(k);
+        a.report = d_report + g0;
+        if (work) {
+            a.src = d_src + g0 * (size_t)k * pitch;
+            a.par = d_parity + g0 * (size_t)e * pitch;
+            set_tables(a, ctx);
+        }
+        wa.passes = passes;
+        wa.slots = slots;
+        if (slots) {
+            wa.tc_table = ctx->d_tc_table;
+            wa.addr = (unsigned long long*)(base + lay.addr);
+            wa.srcs = (const uint8_t**)(base + lay.srcs);
+            wa.dsts = (uint8_t**)(base + lay.dsts);
+            wa.count = (int*)(base + lay.count);
+        }
+        {
+            KTimer kt(ctx, "k_rebuild_wide_prepare", ng);
+            RS_HIP(ctx, launch_rebuild_wide_prepare(wa, ctx->stream));
+        }
+        if (!work || ctx->rebuild_prepare_only)
+            continue;  // the prepare has written every report
+        if (slots) {
+            TcArgs t{};
+            t.srcs = wa.srcs;
+            t.dsts = wa.dsts;
+            t.dst_stride = slots;
+            t.addr = wa.addr;
+            t.addr_stride = (long long)k * slots;
+            t.k = k;
+            t.rows = most;
+            t.len = (long long)len32;
+            t.status = wa.count;
+            KTimer kt(ctx, "k_rs_tc(rebuild)", ng);
+            RS_HIP(ctx, launch_rs_tc_counted(t, (long long)ng, ctx->stream));
+        }
+        // the lane kernel on what is left, a pass of at most 8 outputs at a time
+        const bool vec = !slots && pitch % 16 == 0 && (uintptr_t)d_src % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
+        const long long n16 = vec ? (long long)(len / 16) : 0;
+        for (int p = 0; p < passes; ++p) {
+            RebuildArgs pa = a;
+            pa.u = std::min(8, most - 8 * p);  // this pass's most rows: the launcher's G
+            pa.check = 0;
+            pa.tab = a.tab + (size_t)p * rebuild_tab_stride(k);
+            pa.g = lane_group(pa.u);
+            auto launch = [&](bool bytes, long long c0, long long c1) {
+                return launch_rebuild_blocks(pa, bytes, c0, c1, ctx->stream);
+            };
+            if (slots) {
+                KTimer kt(ctx, kRebuildPassNames[0], ng);
+                RS_HIP(ctx, launch(true, (long long)len32, (long long)len));
+            } else {
+                rc = launch_head_and_tail(ctx, kRebuildPassNames, ng, n16, (long long)len, launch);
+                if (rc)
+                    return rc;
+            }
+        }
+    }
+    return RSGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -269,6 +395,14 @@ int rsgpu_set_scrub_kernel(rsgpu_ctx* ctx, int kernel)
     if (!ctx || kernel < RSGPU_SCRUB_AUTO || kernel > RSGPU_SCRUB_TWO_PASS)
         return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_scrub_kernel: unknown kernel");
     ctx->scrub_kernel = kernel;
+    return RSGPU_OK;
+}
+
+int rsgpu_set_rebuild_kernel(rsgpu_ctx* ctx, int kernel)
+{
+    if (!ctx || kernel < RSGPU_REBUILD_AUTO || kernel > RSGPU_REBUILD_THREADED)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_rebuild_kernel: unknown kernel");
+    ctx->rebuild_kernel = kernel;
     return RSGPU_OK;
 }
 
@@ -547,9 +681,11 @@ int rsgpu_rebuild_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch,
     if (rc)
         return rc;
     const bool check = (flags & RSGPU_REBUILD_CHECK) != 0;
-    // with the check the located row may join the list, and a lane holds 8 rows
-    if (!d_report || (uintptr_t)d_report % 8 != 0 || (flags & ~RSGPU_REBUILD_CHECK) != 0 || u < 1 ||
-        u > (check ? 7 : 8) || !d_lost)
+    // with the check the located row may join the list, and the compare's lanes
+    // hold 8 rows; without it a list is as long as the code has parity rows
+    const int umax = check ? 7 : std::max(8, std::min(e, RSGPU_REBUILD_MAX_LOST));
+    if (!d_report || (uintptr_t)d_report % 8 != 0 || (flags & ~RSGPU_REBUILD_CHECK) != 0 || u < 1 || u > umax ||
+        !d_lost)
         return fail(ctx, RSGPU_ERR_ARG, "rsgpu_rebuild_blocks: bad report pointer, flags, u or list");
     const bool work = e > 0 && len > 0;
     if (work && (!d_src || !d_parity))
@@ -562,6 +698,16 @@ int rsgpu_rebuild_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch,
         if (rc)
             return rc;
     }
+    const bool vec = pitch % 16 == 0 && (uintptr_t)d_src % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
+    // the kernel: AUTO changes nothing for u + check <= 8
+    const bool long_list = u + (check ? 1 : 0) > 8;
+    const bool threaded = work && vec && len >= 32 && len < (1ull << 32) &&
+                          (ctx->rebuild_kernel == RSGPU_REBUILD_THREADED ||
+                           (ctx->rebuild_kernel == RSGPU_REBUILD_AUTO && long_list)) &&
+                          tc_handlers_ready(ctx);
+    if (threaded || long_list)
+        return rebuild_wide(ctx, k, e, len, pitch, blocks, d_src, d_parity, coef, u, d_lost, check, threaded,
+                            d_report);
     // a group of blocks shares one prepare: its tables fit kDegTabBytes, its
     // blocks fit a grid
     const size_t stride = rebuild_tab_stride(k);
@@ -575,7 +721,6 @@ int rsgpu_rebuild_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch,
         if (rc)
             return rc;
     }
-    const bool vec = pitch % 16 == 0 && (uintptr_t)d_src % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
     const long long n16 = work && vec ? (long long)(len / 16) : 0;
     const int most = std::min(u + (check ? 1 : 0), e);  // rows of any block's list as it is rebuilt
     for (size_t g0 = 0; g0 < blocks; g0 += group) {

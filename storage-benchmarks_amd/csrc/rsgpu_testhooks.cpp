@@ -112,6 +112,66 @@ int rsgpu_internal_set_decode_pipeline(rsgpu_ctx* ctx, int n)
     return RSGPU_OK;
 }
 
+// Test hooks (not part of include/rsgpu.h) of the rebuild of long lists
+// (rsgpu_scrub.cpp rebuild_wide).  k_rs_tc jumps to the addresses
+// k_rebuild_wide_prepare writes, so the GPU suite looks at them before the
+// first launch: with prepare_only set, rsgpu_rebuild_blocks stops after the
+// wide prepare (reports written, no row touched); rebuild_wide_layout then
+// tells where the last group's tables lie in the context's buffer --
+// out[0..9] = blocks of a group, k, passes, slots, bytes between blocks' lane
+// tables, and the offsets of the lane tables, handler addresses [B][k][slots],
+// source pointers [B][k], destination pointers [B][slots] and counts [B] --
+// rebuild_wide_read copies bytes of that buffer to the host, and tc_table
+// gives the context's 2048 handler addresses [slot & 7][coefficient] (-1
+// before the first call that needed them).  rebuild_group caps the blocks of a
+// group (0: the 64 MiB rule), so that a small call runs as several groups.
+int rsgpu_internal_set_rebuild_prepare_only(rsgpu_ctx* ctx, int on)
+{
+    if (!ctx)
+        return RSGPU_ERR_ARG;
+    ctx->rebuild_prepare_only = on != 0;
+    return RSGPU_OK;
+}
+
+int rsgpu_internal_set_rebuild_group(rsgpu_ctx* ctx, long long blocks)
+{
+    if (!ctx || blocks < 0)
+        return RSGPU_ERR_ARG;
+    ctx->rebuild_group_max = (size_t)blocks;
+    return RSGPU_OK;
+}
+
+int rsgpu_internal_rebuild_wide_layout(rsgpu_ctx* ctx, long long* out)
+{
+    if (!ctx || !out || ctx->rebuild_wide.blocks == 0)
+        return RSGPU_ERR_ARG;
+    const rsgpu_ctx::RebuildWideLayout& l = ctx->rebuild_wide;
+    const long long v[10] = {(long long)l.blocks, l.k, l.passes, l.slots, (long long)l.lane_stride,
+                             (long long)l.lane, (long long)l.addr, (long long)l.srcs, (long long)l.dsts,
+                             (long long)l.count};
+    std::memcpy(out, v, sizeof v);
+    return RSGPU_OK;
+}
+
+int rsgpu_internal_rebuild_wide_read(rsgpu_ctx* ctx, size_t offset, void* out, size_t bytes)
+{
+    if (!ctx || !out || !ctx->rebuild.p || offset > ctx->rebuild.bytes || bytes > ctx->rebuild.bytes - offset)
+        return RSGPU_ERR_ARG;
+    if (hipMemcpyAsync(out, (const char*)ctx->rebuild.p + offset, bytes, hipMemcpyDeviceToHost, ctx->stream) !=
+            hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess)
+        return RSGPU_ERR_HIP;
+    return RSGPU_OK;
+}
+
+int rsgpu_internal_tc_table(rsgpu_ctx* ctx, unsigned long long* out)
+{
+    if (!ctx || !out || ctx->tc_state != 1)
+        return RSGPU_ERR_ARG;
+    std::memcpy(out, ctx->h_tc_table, sizeof ctx->h_tc_table);
+    return RSGPU_OK;
+}
+
 // Test hook (not in include/rsgpu.h): the host-built code of an e x k matrix
 // shared by every block (jit_prog.h, the GENERATED encode), for the CPU
 // suite to disassemble and interpret.  Returns the bytes needed, or -1;

@@ -39,7 +39,7 @@ __all__ = [
     "SCRUB_ONE_ROW", "SCRUB_DAMAGED", "REPAIR_REPORT_DTYPE", "REPAIR_MODES", "REPAIR_ONE_ROW",
     "REPAIR_COLUMNS", "REPAIR_CLEAN", "REPAIR_REPAIRED", "REPAIR_PARTIAL", "REPAIR_DAMAGED",
     "UPDATE_NONE", "UPDATE_DELTA", "LOST_NONE", "SCRUB_UNCHECKED", "SCRUB_BAD_MATRIX",
-    "SCRUB_BAD_LIST", "REBUILD_CHECK",
+    "SCRUB_BAD_LIST", "REBUILD_CHECK", "REBUILD_MAX_LOST", "REBUILD_KERNELS",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -79,6 +79,10 @@ SCRUB_UNCHECKED, SCRUB_BAD_MATRIX, SCRUB_BAD_LIST = 3, -1, -2
 # rsgpu_rebuild_blocks' flag (include/rsgpu.h); lists and reports as the
 # degraded scrub's
 REBUILD_CHECK = 1
+# the longest list without the check (and at most e), and the
+# rsgpu_set_rebuild_kernel choices
+REBUILD_MAX_LOST = 32
+REBUILD_KERNELS = {"auto": 0, "lanes": 1, "threaded": 2}
 
 vp = C.c_void_p
 sz = C.c_size_t
@@ -133,6 +137,7 @@ _SIGS = {
                                        vp]),
     "rsgpu_repair_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp]),
     "rsgpu_set_scrub_kernel": (C.c_int, [vp, C.c_int]),
+    "rsgpu_set_rebuild_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_update_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, C.c_int, vp, vp, vp, vp, vp,
                                       C.c_int, vp]),
     "rsgpu_host_alloc": (C.c_int, [vp, C.POINTER(vp), sz]),
@@ -437,6 +442,12 @@ class Context:
         self.check(lib().rsgpu_set_scrub_kernel(self._h, SCRUB_KERNELS[kernel]),
                    "rsgpu_set_scrub_kernel")
 
+    def set_rebuild_kernel(self, kernel: str) -> None:
+        """Kernel of rebuild_blocks: auto | lanes | threaded (include/rsgpu.h
+        rsgpu_set_rebuild_kernel); every choice writes the same bytes."""
+        self.check(lib().rsgpu_set_rebuild_kernel(self._h, REBUILD_KERNELS[kernel]),
+                   "rsgpu_set_rebuild_kernel")
+
     def scrub_blocks(self, k, e, length, pitch, blocks, d_src, d_par, d_report, coef=None,
                      locate: bool = True) -> None:
         """Parity scrub (include/rsgpu.h rsgpu_scrub_blocks): d_report is
@@ -468,9 +479,10 @@ class Context:
         d_lost names (as scrub_degraded_blocks') are written back into d_src
         and d_par.  With check (1 <= u <= 7) the degraded scrub runs first and
         decides per block: a located row is rebuilt too, a DAMAGED block is
-        left alone; without it (1 <= u <= 8) every survivor is trusted.
-        d_report as scrub_degraded_blocks'.  Enqueued on the context's
-        stream."""
+        left alone; without it every survivor is trusted and a list may be
+        as long as the code has parity rows: 1 <= u <= max(8, min(e,
+        REBUILD_MAX_LOST)).  d_report as scrub_degraded_blocks'.  The kernel
+        is set_rebuild_kernel's.  Enqueued on the context's stream."""
         coef = _coef(coef)
         self.check(lib().rsgpu_rebuild_blocks(self._h, k, e, length, pitch, blocks, _ptr(d_src),
                                               _ptr(d_par), _ptr(coef), u, _ptr(d_lost),
@@ -607,10 +619,10 @@ class GpuEncoder:
     def rebuild(self, lost, check: bool = True) -> np.ndarray:
         """Rebuilds the rows `lost` names of this encoder's blocks in place
         (include/rsgpu.h rsgpu_rebuild_blocks): lost as scrub_degraded's, u
-        <= 7 with check, <= 8 without.  With check the degraded scrub decides
-        per block; the per-block reports as a structured array
-        (SCRUB_REPORT_DTYPE).  Synchronises (the reports are copied to the
-        host)."""
+        <= 7 with check, <= max(8, min(e, REBUILD_MAX_LOST)) without.  With
+        check the degraded scrub decides per block; the per-block reports as
+        a structured array (SCRUB_REPORT_DTYPE).  Synchronises (the reports
+        are copied to the host)."""
         u, d_lost = self._lists("lost", lost)
         rep = self._report(SCRUB_REPORT_DTYPE)
         self.ctx.rebuild_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,

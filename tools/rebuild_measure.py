@@ -23,7 +23,21 @@ copy's rate; the checked call adds the degraded scrub as measured.
 `over_model` is measured / modelled, `over_decode` measured / decode_general.
 
     python tools/rebuild_measure.py out.json [--k 64 --e 32 --len 1000000 --blocks 1024 --rounds 12]
+
+With --wide the lists of 9 to 32 rows and the kernel choice are measured
+instead (profiles/rebuild_wide/README.md).  Kinds: `threaded_n8`, `_n16`,
+`_n32` and `lanes_n8`, `_n16`, `_n32` (rsgpu_set_rebuild_kernel THREADED and
+LANES, random full lists, u = n, no check; LANES runs in passes of 8 outputs
+above 8), `decode_n8` ... `_n32` (rsgpu_decode_general, the same lists),
+`threaded_mixed` and `lanes_mixed` (n drawn from 0 .. 32 per block, u = 32),
+`prepare_n8` ... `_n32` and `prepare_mixed` (the wide prepare alone, through
+the test hook that stops the call after it) and `copy`.  A list the code does
+not determine (BAD_MATRIX) is drawn again before anything is timed.  Besides
+the medians the summary holds, for n = 8, 16, 32 and mixed, whether THREADED
+was the faster one in every mirrored pair (same round, same half).
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -34,8 +48,131 @@ UNCHECKED = (1, 2, 4, 8)
 CHECKED = (1, 4, 7)
 
 
+WIDE = (8, 16, 32)
+
+
+def wide(a):
+    k, e, L, B = a.k, a.e, a.len, a.blocks
+    ctx, enc = ml.setup(a)
+    dev, pitch = enc.src.device, enc.pitch
+    rep = ml.reports(enc)
+    rng = np.random.default_rng(9)
+    hooks = rsgpu.testhooks()
+    hooks.rsgpu_internal_set_rebuild_prepare_only.argtypes = [C.c_void_p, C.c_int]
+
+    def draw(n):
+        return rsgpu.LOST_NONE if n == 0 else np.sort(rng.choice(k + e, n, replace=False))
+
+    def full(n, u):
+        row = np.full(u, rsgpu.LOST_NONE, np.uint8)
+        row[:n] = draw(n)
+        return row
+
+    nmix = rng.integers(0, min(e, 32) + 1, B)
+    lists = {str(n): np.stack([full(n, n) for _ in range(B)]) for n in WIDE}
+    lists["mixed"] = np.stack([full(int(n), 32) for n in nmix])
+    d_lists = {}
+
+    def call(key, kernel, prepare_only=False):
+        u = lists[key].shape[1]
+        ctx.set_rebuild_kernel(kernel)
+        hooks.rsgpu_internal_set_rebuild_prepare_only(ctx.handle, 1 if prepare_only else 0)
+        try:
+            ctx.rebuild_blocks(k, e, L, pitch, B, enc.src, enc.par, u, d_lists[key], rep, check=False)
+        finally:
+            hooks.rsgpu_internal_set_rebuild_prepare_only(ctx.handle, 0)
+            ctx.set_rebuild_kernel("auto")
+
+    # lists the code determines: the prepare alone judges them, the rest is drawn again
+    redrawn = {}
+    for key, v in lists.items():
+        for _ in range(20):
+            d_lists[key] = torch.from_numpy(v).to(dev)
+            call(key, "threaded", prepare_only=True)
+            torch.cuda.synchronize()
+            bad = np.flatnonzero(rep.cpu().numpy().view(rsgpu.SCRUB_REPORT_DTYPE)["status"] != rsgpu.SCRUB_CLEAN)
+            if not len(bad):
+                break
+            redrawn[key] = redrawn.get(key, 0) + int(len(bad))
+            for b in bad:
+                n = int((v[b] != rsgpu.LOST_NONE).sum())
+                v[b] = full(n, v.shape[1])
+        else:
+            raise SystemExit(f"lists {key}: still undetermined ones")
+    copy_bytes = (k + 4) * L * B // 2
+    copy = ml.copy_yardstick(enc, copy_bytes)
+    dec_out = torch.empty(B * max(WIDE) * pitch, dtype=torch.uint8, device=dev)
+    dec_ws = {n: torch.empty(rsgpu.decode_general_workspace_bytes(k, k + e, n, B), dtype=torch.uint8, device=dev)
+              for n in WIDE}
+    dec_status = torch.empty(B, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+
+    def run(kind):
+        if kind == "copy":
+            return copy()
+        what, key = kind.split("_")
+        key = key.lstrip("n")
+        if what == "decode":
+            n = int(key)
+            return ml.timed(ctx, lambda: ctx.decode_general(k, k + e, L, pitch, B, None, enc.src, enc.par,
+                                                            d_lists[key], n, dec_out, dec_ws[n], dec_status))
+        if what == "prepare":
+            return ml.timed(ctx, lambda: call(key, "threaded", prepare_only=True))
+        return ml.timed(ctx, lambda: call(key, what))
+
+    keys = [f"n{n}" for n in WIDE] + ["mixed"]
+    kinds = ([f"{w}_{key}" for key in keys for w in ("threaded", "lanes")] + [f"decode_n{n}" for n in WIDE] +
+             [f"prepare_{key}" for key in keys] + ["copy"])
+    kernels_seen = {}
+    for kind in kinds:  # untimed and checked
+        rep.fill_(0xA5)
+        dec_status.fill_(-9)
+        _, by = run(kind)
+        kernels_seen[kind] = sorted(by)
+        if kind.startswith("decode"):
+            assert bool((dec_status == 0).all()), kind
+        elif kind != "copy":
+            assert ml.all_clean(rep), kind
+    ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, rep)
+    torch.cuda.synchronize()
+    assert ml.all_clean(rep), "the blocks after the rebuilds"
+
+    out = {**ml.header(enc), "kernels": kernels_seen, "redrawn_lists": redrawn,
+           "mean_rows_mixed": float(nmix.mean()), "runs": ml.mirrored_rounds(kinds, a.rounds, run)}
+    summ = ml.summarise(out["runs"], kinds, kernel_medians=True)
+    copy_tb = 2 * copy_bytes / (summ["copy"]["median"] * 1e-3) / 1e12
+    summ["copy"]["tb_per_s"] = copy_tb
+    half = len(kinds)
+
+    def pairs(x, y):
+        """(x ms, y ms) of the runs of a round's same half"""
+        at = {(r["round"], r["pos"] >= half, r["kind"]): r["ms"] for r in out["runs"]}
+        return [(at[(rnd, h, x)], at[(rnd, h, y)]) for rnd in range(a.rounds) for h in (False, True)]
+
+    for key in keys:
+        rows = k + (float(nmix.mean()) if key == "mixed" else int(key[1:]))
+        model = rows * L * B / (copy_tb * 1e12) * 1e3
+        t, ln = summ[f"threaded_{key}"], summ[f"lanes_{key}"]
+        for s in (t, ln):
+            s["model_ms"] = model
+            s["over_model"] = s["median"] / model
+        pr = pairs(f"threaded_{key}", f"lanes_{key}")
+        t["over_lanes"] = t["median"] / ln["median"]
+        t["faster_than_lanes_in_pairs"] = f"{sum(x < y for x, y in pr)} of {len(pr)}"
+        t["prepare_share"] = summ[f"prepare_{key}"]["median"] / t["median"]
+        if key != "mixed":
+            t["over_decode"] = t["median"] / summ[f"decode_{key}"]["median"]
+            ln["over_decode"] = ln["median"] / summ[f"decode_{key}"]["median"]
+    ml.finish(a.out, out, summ)
+    ctx.close()
+
+
 def main():
-    a = ml.shape_parser().parse_args()
+    ap = ml.shape_parser()
+    ap.add_argument("--wide", action="store_true", help="lists of up to 32 rows and the kernel choice")
+    a = ap.parse_args()
+    if a.wide:
+        return wide(a)
     k, e, L, B = a.k, a.e, a.len, a.blocks
 
     ctx, enc = ml.setup(a)
