@@ -1,7 +1,7 @@
 // rs_tc.hip -- bit-sliced GF(2^8) dot product with RUNTIME coefficients via
 // threaded code: out_i = sum_p c[i][p] * src_p for per-block matrices c.
 // Uses: the decode (the e x k rows of inv(b) over the k - e survivors and the
-// e parity rows, rsgpu_capi.cpp / k_decode_prepare_syn; or the rows of the
+// e parity rows, rsgpu_decode.cpp / k_decode_prepare_syn; or the rows of the
 // k x k inversion for codes without compile-time kernels), the split
 // decode's solve, and every runtime-coefficient encode (ec_encode_data with
 // any tables, Cauchy).

@@ -1,11 +1,47 @@
 // rsgpu_internal.h -- host helpers that rsgpu_capi.cpp defines and the other
-// host files of librsgpu share (rsgpu_scrub.cpp).  Internal: rsgpu.map keeps
-// all of it out of the library's exports.
+// host files of librsgpu share (rsgpu_decode.cpp, rsgpu_scrub.cpp), and the
+// small rules all three follow.  Internal: rsgpu.map keeps all of it out of
+// the library's exports.
 #pragma once
+#include <algorithm>
+#include <vector>
+
 #include "gf256.h"
+#include "rs_kernels.h"
 #include "rsgpu_ctx.h"
 
 namespace rsgpu {
+
+// column tiles of a row: what one workgroup of the row kernels covers
+constexpr size_t kTileBytes = 2048;
+inline size_t tiles(size_t len) { return (len + kTileBytes - 1) / kTileBytes; }
+
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// rows the kernels may read and write as 16-byte vectors
+inline bool ptrs_aligned(size_t pitch, const void* a, const void* b, const void* c = nullptr)
+{
+    return pitch % 16 == 0 && (uintptr_t)a % 16 == 0 && (uintptr_t)b % 16 == 0 && (uintptr_t)c % 16 == 0;
+}
+// ... of a length the threaded and the generated code take
+inline bool rows_aligned(size_t len, size_t pitch, const void* a, const void* b, const void* c = nullptr)
+{
+    return len % 32 == 0 && ptrs_aligned(pitch, a, b, c);
+}
+
+// The block index is grid.y: f(b0, nb) over consecutive slices of at most
+// kMaxGridBlocks blocks, in stream order, up to the first error.
+template <class F>
+int for_grid_slices(size_t blocks, F&& f)
+{
+    for (size_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks)
+        if (const int rc = f(b0, std::min(kMaxGridBlocks, blocks - b0)))
+            return rc;
+    return RSGPU_OK;
+}
+
+// the e x k parity matrix of a call: `coef`, or the gf_gen_rs_matrix rows
+std::vector<uint8_t> parity_matrix(int k, int e, const unsigned char* coef);
 
 const GfTables& host_gf();
 uint8_t hmul(uint8_t a, uint8_t b);
@@ -27,9 +63,51 @@ int upload(rsgpu_ctx* ctx, void* d_dst, size_t bytes, size_t dst_off = 0, size_t
 
 hipEvent_t pool_event(rsgpu_ctx* ctx);
 
+// a timing-disabled event for cross-stream ordering, recycled round-robin
+hipEvent_t sync_event(rsgpu_ctx* ctx);
+
 // the handler table of k_rs_tc (rs_tc.hip) is located and ctx->d_tc_table holds
 // its addresses; probed once per context
 bool tc_handlers_ready(rsgpu_ctx* ctx);
+
+// the device has a pool for executable allocations (1), or not (-1); probed
+// once per context
+int jit_probe(rsgpu_ctx* ctx);
+
+// >= bytes of executable device memory at ctx->d_jit, a new generation when regrown
+int jit_ensure(rsgpu_ctx* ctx, size_t bytes);
+
+// (block, 2 KB tile) pairs below which the one-launch kernels of small batches serve
+constexpr long long kTcSplitMaxWork = 2048;
+
+// k_rs_tc over `rows` output rows in passes of <= 32, or k_rs_tc_split for a
+// small batch of <= 8 rows; addr_stride elements between blocks' tables
+int tc_launch(rsgpu_ctx* ctx, const char* name, const uint8_t* const* d_srcs, uint8_t* const* d_dsts,
+              const unsigned long long* d_addr, long long addr_stride, int k, int rows, long long len,
+              long long blocks, const int* d_status);
+
+// v_perm table rows per source of k_dot_generic: `rows` padded to its pass
+int rows_pad_for(int rows);
+
+// the context's scratch grown to >= bytes
+int ensure_scratch(rsgpu_ctx* ctx, size_t bytes);
+
+// the fields every k_rs_tc launch fills, in TcArgs' order
+inline TcArgs tc_args(const uint8_t* const* srcs, uint8_t* const* dsts, int dst_stride,
+                      const unsigned long long* addr, long long addr_stride, int k, int rows, long long len,
+                      const int* status)
+{
+    return TcArgs{srcs, dsts, dst_stride, addr, addr_stride, k, rows, len, status};
+}
+
+// the fields every generated-code launch fills (k_rs_jit, k_rs_jitw), in
+// JitArgs' order: `rows` rows from dsts on, block_stride bytes between
+// blocks' code (0: every block on the same code); the rest at its default
+inline JitArgs jit_args(const uint8_t* const* srcs, uint8_t* const* dsts, const void* code, long long chunk_stride,
+                        long long block_stride, int k, int rows, int dst_stride, long long len, const int* status)
+{
+    return JitArgs{srcs, dsts, (const uint8_t*)code, chunk_stride, block_stride, k, rows, dst_stride, len, status};
+}
 
 // Brackets one kernel launch with events when timing is enabled.
 struct KTimer {

@@ -2,7 +2,8 @@
 // scrub, repair in place, partial-stripe update, degraded scrub and rebuild in
 // place.  Argument checks and launch sequences; the kernels are rs_kernels.hip
 // (two-pass compare, finalise), rs_bitsliced.hip (fused), rs_update.hip,
-// rs_degraded.hip, rs_rebuild.hip.
+// rs_degraded.hip, rs_rebuild.hip.  The encode and the decode are
+// rsgpu_capi.cpp and rsgpu_decode.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,20 +19,6 @@
 namespace {
 
 using namespace rsgpu;
-
-// the e x k parity matrix of a call: `coef`, or the gf_gen_rs_matrix rows
-std::vector<uint8_t> scrub_matrix(int k, int e, const unsigned char* coef)
-{
-    std::vector<uint8_t> c((size_t)e * k);
-    if (coef) {
-        std::memcpy(c.data(), coef, c.size());
-    } else {
-        std::vector<uint8_t> a((size_t)(k + e) * k);
-        rsgpu_gf_gen_rs_matrix(a.data(), k + e, k);
-        std::memcpy(c.data(), a.data() + (size_t)k * k, c.size());
-    }
-    return c;
-}
 
 // (k, e, matrix): what the device copy of a matrix's tables is kept under
 std::vector<uint8_t> matrix_key(int k, int e, const std::vector<uint8_t>& c)
@@ -75,7 +62,7 @@ struct Locator {
 int locator(rsgpu_ctx* ctx, int k, int e, const unsigned char* coef, const char* msg, Locator& loc)
 {
     if (e >= 2)
-        loc.c = scrub_matrix(k, e, coef);
+        loc.c = parity_matrix(k, e, coef);
     if (e < 2 || !scrub_locatable(k, e, loc.c.data(), loc.rowtab))
         return fail(ctx, RSGPU_ERR_UNSUPPORTED, msg);
     return RSGPU_OK;
@@ -201,7 +188,7 @@ int update_tables(rsgpu_ctx* ctx, int k, int e, const unsigned char* coef)
     }
     std::vector<uint8_t> c, key;
     if (e > 0) {
-        c = scrub_matrix(k, e, coef);
+        c = parity_matrix(k, e, coef);
         key = matrix_key(k, e, c);
     }
     const bool matrix = e > 0 && key != ctx->update_key;
@@ -340,21 +327,13 @@ int rebuild_wide(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t 
         if (!work || ctx->rebuild_prepare_only)
             continue;  // the prepare has written every report
         if (slots) {
-            TcArgs t{};
-            t.srcs = wa.srcs;
-            t.dsts = wa.dsts;
-            t.dst_stride = slots;
-            t.addr = wa.addr;
-            t.addr_stride = (long long)k * slots;
-            t.k = k;
-            t.rows = most;
-            t.len = (long long)len32;
-            t.status = wa.count;
+            const TcArgs t = tc_args(wa.srcs, wa.dsts, slots, wa.addr, (long long)k * slots, k, most,
+                                     (long long)len32, wa.count);
             KTimer kt(ctx, "k_rs_tc(rebuild)", ng);
             RS_HIP(ctx, launch_rs_tc_counted(t, (long long)ng, ctx->stream));
         }
         // the lane kernel on what is left, a pass of at most 8 outputs at a time
-        const bool vec = !slots && pitch % 16 == 0 && (uintptr_t)d_src % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
+        const bool vec = !slots && ptrs_aligned(pitch, d_src, d_parity);
         const long long n16 = vec ? (long long)(len / 16) : 0;
         for (int p = 0; p < passes; ++p) {
             RebuildArgs pa = a;
@@ -386,7 +365,7 @@ int rsgpu_scrub_locatable(int k, int e, const unsigned char* coef)
 {
     if (k <= 0 || e < 2 || k + e > RSGPU_MAX_SOURCES)
         return 0;
-    const std::vector<uint8_t> c = scrub_matrix(k, e, coef);
+    const std::vector<uint8_t> c = parity_matrix(k, e, coef);
     return scrub_locatable(k, e, c.data(), nullptr) ? 1 : 0;
 }
 
@@ -565,9 +544,7 @@ int rsgpu_update_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
     const bool vec = pitch % 16 == 0 && (uintptr_t)d_upd % 16 == 0 && (!src_used || (uintptr_t)d_src % 16 == 0) &&
                      (!par_used || (uintptr_t)d_parity % 16 == 0);
     const long long n16 = work && vec ? (long long)(len / 16) : 0;
-    // block index in grid.y: larger batches as consecutive slices
-    for (size_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks) {
-        const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
+    return for_grid_slices(blocks, [&](size_t b0, size_t nb) {
         UpdateArgs a{};
         a.k = k;
         a.e = e;
@@ -584,11 +561,8 @@ int rsgpu_update_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
         auto launch = [&](bool bytes, long long c0, long long c1) {
             return launch_update_blocks(a, bytes, c0, c1, ctx->stream);
         };
-        rc = launch_head_and_tail(ctx, kUpdateNames, nb, n16, work ? (long long)len : 0, launch);
-        if (rc)
-            return rc;
-    }
-    return RSGPU_OK;
+        return launch_head_and_tail(ctx, kUpdateNames, nb, n16, work ? (long long)len : 0, launch);
+    });
 }
 
 int rsgpu_scrub_degraded_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
@@ -698,7 +672,7 @@ int rsgpu_rebuild_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch,
         if (rc)
             return rc;
     }
-    const bool vec = pitch % 16 == 0 && (uintptr_t)d_src % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
+    const bool vec = ptrs_aligned(pitch, d_src, d_parity);
     // the kernel: AUTO changes nothing for u + check <= 8
     const bool long_list = u + (check ? 1 : 0) > 8;
     const bool threaded = work && vec && len >= 32 && len < (1ull << 32) &&

@@ -90,12 +90,19 @@ def test_every_timed_kernel_has_algorithmic_bytes():
     """Each kernel the C-ABI times under an (encode)/(decode) name is priced
     in bench.alg_bytes: an unpriced one would print alg_GBps 0 and a zero
     roofline when it is the step's dominant kernel."""
+    import glob
     import re
 
     import bench
-    src = open(os.path.join(ROOT, "storage-benchmarks_amd", "csrc", "rsgpu_capi.cpp")).read()
-    names = set(re.findall(r'"(k_[a-z0-9_]+\((?:encode|decode)\))"', src))
-    assert names, "no timed kernels found"
+    names = set()
+    for path in glob.glob(os.path.join(ROOT, "storage-benchmarks_amd", "csrc", "*.cpp")):
+        names |= set(re.findall(r'"(k_[a-z0-9_]+\((?:encode|decode)\))"', open(path).read()))
+    # the names the host code timed when it was one file: none may go missing
+    assert names >= {
+        "k_dot_generic(decode)", "k_rs_bs(encode)", "k_rs_bs_split(encode)", "k_rs_jit(decode)", "k_rs_jit(encode)",
+        "k_rs_jit10(decode)", "k_rs_jit10x4(decode)", "k_rs_jit12(decode)", "k_rs_jit12x4(decode)",
+        "k_rs_jit16(decode)", "k_rs_jit16x4(decode)", "k_rs_jitw_passes(decode)", "k_rs_syn_split(decode)",
+        "k_rs_tc(decode)", "k_rs_tc(encode)", "k_rs_tc_fused(decode)"}, sorted(names)
     priced = bench.alg_bytes(16, 4, 1000)
     missing = sorted(n for n in names if priced.get(n, 0.0) <= 0.0)
     assert not missing, missing
