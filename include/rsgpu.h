@@ -329,10 +329,31 @@ int rsgpu_scrub_locatable(int k, int e, const unsigned char *coef);
  *             scratch (at most 128 MiB, or one block's parity when that is
  *             larger) by the encode dispatch, then k_scrub_compare; any
  *             geometry
+ *   GENERATED the generated encode's shared program of the call's matrix
+ *             (built once per matrix and context, the one a GENERATED encode of
+ *             the same matrix runs) with FUSED's epilogue for a matrix known
+ *             at run time (k_rs_jit_scrub): any matrix, with or without
+ *             `coef`, for 1 <= e <= 64, 16-byte aligned rows (pitch % 16 == 0),
+ *             len % 32 == 0 and len < 4 GiB, on a device with an executable
+ *             memory pool; no parity scratch, a clean tile writes nothing.
+ *             Opt-in: AUTO never takes it.  rsgpu_repair_blocks and
+ *             rsgpu_scrub_degraded_blocks do not use it: under GENERATED the
+ *             repair runs its TWO_PASS form.
+ *             Measured on an MI355X, 1 MB rows, 1.5 GB of rows per call, clean
+ *             data, kernel times, medians of 24 runs: (10,4) 0.37 ms against
+ *             0.49 ms TWO_PASS (gf_gen_rs_matrix and Cauchy alike), (6,3) 0.40
+ *             / 0.54, (12,4) 0.35 / 0.45, (17,3) 0.32 / 0.39, (20,7) 0.37 /
+ *             0.47, (64,32) 0.40 / 0.56: 0.70 - 0.82 of TWO_PASS, no shape
+ *             loses to it.  It is not the generated encode's time, as FUSED is
+ *             the compiled encode's: 1.05 ((64,32)) to 1.27 ((6,3)) of the
+ *             GENERATED encode of the same rows, and 1.18 ((20,7)) and 1.34
+ *             ((64,32)) of FUSED, which stays the faster choice for the
+ *             compiled codes (profiles/scrub_generated/).
  * A choice that does not apply falls back to TWO_PASS. */
 #define RSGPU_SCRUB_AUTO 0
 #define RSGPU_SCRUB_FUSED 1
 #define RSGPU_SCRUB_TWO_PASS 2
+#define RSGPU_SCRUB_GENERATED 3
 int rsgpu_set_scrub_kernel(rsgpu_ctx *ctx, int kernel);
 
 /* ---- degraded scrub: a block with known-lost rows ------------------------ */

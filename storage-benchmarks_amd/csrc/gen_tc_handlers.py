@@ -285,6 +285,13 @@ def main() -> None:
         body = "".join(f"v_mov_b64 %{q}, v[{A16 + 8 * slot + 2 * q}:{A16 + 8 * slot + 2 * q + 1}]\\n"
                        for q in range(4))
         lines.append(f'#define RSGPU_JW_READ_SLOT64_{slot} "{body}"')
+    # the scrub epilogues of rs_jit.hip: a slot's 8 planes XORed into 8
+    # compiler-owned registers (operands 0..7, read and written), so the slot
+    # is never copied out
+    for name, base, slots in (("TC", ACC, 8), ("JW", A16, 16)):
+        for slot in range(slots):
+            body = "".join(f"v_xor_b32 %{q}, %{q}, v{base + 8 * slot + q}\\n" for q in range(8))
+            lines.append(f'#define RSGPU_{name}_XOR_SLOT_{slot} "{body}"')
     lines.append("#define RSGPU_JW_CALL_CLOBBERS " + ", ".join(f'"v{r}"' for r in range(10, 40)))
     vclob = sorted(set(range(STAGE, STAGE + 8)) | set(TABLE_REGS))
     sclob = list(range(BANK[0], BANK[0] + 16)) + [SM0, RET, RET + 1] + list(range(BANK[1], BANK[1] + 16))

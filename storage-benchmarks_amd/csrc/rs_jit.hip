@@ -30,6 +30,7 @@
 #include "diag_clock.h"
 #include "rs_jit.h"
 #include "rs_kernels.h"
+#include "rs_lane.h"
 #include "tc_handlers.inc"
 
 namespace rsgpu {
@@ -93,33 +94,270 @@ __device__ __forceinline__ void read_slot(uint32_t (&W)[8])
     }
 }
 
-// amdgpu_num_vgpr(64): the compiler allocates v0..v63 only (minus the
-// registers the call clobbers); the accumulators v64..v127 are touched by asm
-// and generated code alone.  (Holding the block's row pointers in VGPRs and
-// reading them with v_readlane instead of scalar loads measured slower:
-// 26.3 vs 25.1 ms at C3, tools/jit_profile.)
-// SH: one program shared by every block (the GENERATED encode; a distinct
-// symbol, so profiles tell it from the per-block decode)
-template <int NW, bool SH, class H = JitHooks>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void k_rs_jit(JitArgs a)
-{
-    __shared__ uint4 lds[2][C * 2 * 64];
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    int b = blockIdx.y;
-    long long tile = blockIdx.x;
-    if (a.xcd_order) {
-        // workgroups are dealt round-robin over the 8 XCDs: give each XCD a
-        // contiguous range of (block, tile), so all tiles of a block (and its
-        // code) stay in one XCD's L2 -- it matters when a block has few tiles
-        const unsigned g = blockIdx.x + gridDim.x * blockIdx.y, tot = gridDim.x * gridDim.y;
-        const unsigned xcd = g & 7, q8 = tot >> 3, r8 = tot & 7;
-        const unsigned lin = xcd * q8 + min(xcd, r8) + (g >> 3);
-        b = (int)(lin / gridDim.x);
-        tile = lin - (unsigned)b * gridDim.x;
+// k_rs_jit's eight slots, as the scrub epilogue reads them
+struct Slots8 {
+    static constexpr int N = 8;
+    template <int S>
+    __device__ __forceinline__ static void read(uint32_t (&W)[8])
+    {
+        read_slot<S>(W);
     }
-    if (a.status && a.status[b] != 0)
-        return;  // uniform per workgroup: the whole block is skipped
+    // P ^= the slot's planes, the slot never copied out
+    template <int S>
+    __device__ __forceinline__ static void xor_into(uint32_t (&P)[8])
+    {
+#define RSGPU_JIT_XS(TEXT)                                                                                       \
+    asm volatile(TEXT : "+v"(P[0]), "+v"(P[1]), "+v"(P[2]), "+v"(P[3]), "+v"(P[4]), "+v"(P[5]), "+v"(P[6]), \
+                 "+v"(P[7]))
+        if constexpr (S == 0) RSGPU_JIT_XS(RSGPU_TC_XOR_SLOT_0);
+        if constexpr (S == 1) RSGPU_JIT_XS(RSGPU_TC_XOR_SLOT_1);
+        if constexpr (S == 2) RSGPU_JIT_XS(RSGPU_TC_XOR_SLOT_2);
+        if constexpr (S == 3) RSGPU_JIT_XS(RSGPU_TC_XOR_SLOT_3);
+        if constexpr (S == 4) RSGPU_JIT_XS(RSGPU_TC_XOR_SLOT_4);
+        if constexpr (S == 5) RSGPU_JIT_XS(RSGPU_TC_XOR_SLOT_5);
+        if constexpr (S == 6) RSGPU_JIT_XS(RSGPU_TC_XOR_SLOT_6);
+        if constexpr (S == 7) RSGPU_JIT_XS(RSGPU_TC_XOR_SLOT_7);
+#undef RSGPU_JIT_XS
+    }
+};
+
+// log / antilog tables of the scrub's cold path
+alignas(16) __device__ const GfTables kGfJit = make_gf_tables();
+
+// ---------------------------------------------------------------------------
+// The scrub epilogue of the generated kernels (rsgpu_scrub_blocks under
+// RSGPU_SCRUB_GENERATED; k_rs_jit_scrub, k_rs_jitw_scrub), in place of the
+// parity store: scrub_tile (rs_bitsliced.hip) for a matrix known at run time.
+// The wave holds rows [r0, r0 + nrow) of the computed parity as planes in its
+// slots (SL: Slots8, SlotsW); dsts names the block's STORED parity rows, which
+// are only read.  Wave `wave` of NV of tile `tw` of the workgroup's TPW.
+//
+// Per row: the lane's 32 stored bytes (one row's load in flight ahead, no
+// further), one tr8 on them -- the stored side: the slot's planes are then
+// XORed in straight from the accumulators, never copied out -- and the OR of
+// the syndrome planes over planes and rows
+// is the lane's bad-byte mask (bit 8 q + w: byte 4 w + q).  A lane past the
+// row end, and every lane of a tile past the last one, reads the row head
+// (po = 0) and gives no mask (inb false); it takes every barrier below.
+//
+// Then a workgroup barrier (other waves may still be reading the last chunk's
+// planes), and the masks meet in the chunk buffers, now free: [NV TPW][64]
+// u32 at ldsb.  A clean workgroup ends there and has written nothing.  Wave 0
+// of a bad tile adds the tile's bad columns to the block's fold, one 64-bit
+// atomicAdd.  With `locate` the whole workgroup (the barriers are its own)
+// enters the cold path, small code and not fast code: in 8 passes the waves
+// lay 4 bytes per lane of all e syndrome rows into LDS (syn [e][256] per
+// tile, behind the masks: kScrubMaskBytes + TPW e 256 bytes, e <= 64), and a
+// tile's threads walk the 256 columns with the rule of a general locatable
+// matrix (rs_lane.h scrub_locate_row; rowtab and the matrix at s.tab).  The
+// maxima of row + 1 and of kScrubBias - row go into the fold, one atomicMax
+// pair per wave.
+// ---------------------------------------------------------------------------
+constexpr int kScrubMaskBytes = 2048;  // >= 4 NV TPW 64: at most 6 waves
+
+struct JitScrub {
+    ScrubFold* fold;
+    const uint8_t* tab;
+    int locate;
+};
+
+template <class SL, int NV, int TPW>
+__device__ __forceinline__ void scrub_slots(const JitScrub& s, int k, int e, uint8_t* const* dsts, int b, int r0,
+                                            int nrow, int wave, int tw, bool inb, uint32_t po, uint8_t* ldsb,
+                                            uint32_t m4, uint32_t m2, uint32_t m1)
+{
+    static_assert(4 * NV * TPW * 64 <= kScrubMaskBytes, "the masks fit their part");
+    // the lane index afresh: the body's copy, kept live to the end of the cold
+    // path, cost k_rs_jitw_scrub one VGPR spilled to scratch across its main
+    // loop (9 registers survive the call there)
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    // the stored rows' pointers: scalar loads under one wait, clamped in bounds
+    typedef const uint8_t* const __attribute__((address_space(4)))* CRows;
+    const uint8_t* dp[SL::N];
+#pragma unroll
+    for (int i = 0; i < SL::N; ++i)
+        dp[i] = ((CRows)dsts)[min(r0 + i, e - 1)];
+    uint32_t mine = 0;
+    uint32_t Pn[8];
+    bs::load32(dp[0], po, true, Pn);
+    [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
+        (
+            [&] {
+                if (Ss < nrow) {
+                    uint32_t Pw[8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q)
+                        Pw[q] = Pn[q];
+                    if constexpr (Ss + 1 < SL::N)
+                        if (Ss + 1 < nrow)
+                            bs::load32(dp[Ss + 1], po, true, Pn);
+                    tr8(Pw, m4, m2, m1);
+                    SL::template xor_into<Ss>(Pw);  // the syndromes, as planes
+#pragma unroll
+                    for (int q = 0; q < 8; ++q)
+                        mine |= Pw[q];
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }(),
+            ...);
+    }(std::make_integer_sequence<int, SL::N>{});
+    uint32_t* wmask = reinterpret_cast<uint32_t*>(ldsb);
+    __syncthreads();
+    wmask[(tw * NV + wave) * 64 + lane] = inb ? mine : 0u;
+    __syncthreads();
+    uint32_t tm = 0, any = 0;  // this lane's columns: of the tile, of the workgroup
+#pragma unroll
+    for (int g = 0; g < NV * TPW; ++g) {
+        const uint32_t m = wmask[g * 64 + lane];
+        any |= m;
+        tm |= g / NV == tw ? m : 0u;
+    }
+    if (__ballot(any != 0) == 0)
+        return;  // the same for every wave of the workgroup
+    ScrubFold* f = s.fold + b;
+    if (wave == 0) {
+        unsigned n = __builtin_popcount(tm);
+        for (int o = 32; o > 0; o >>= 1)
+            n += __shfl_down(n, o, 64);
+        if (lane == 0 && n)
+            atomicAdd(&f->bad, (unsigned long long)n);
+    }
+    if (!s.locate)
+        return;
+    // LDS through its own address space, the stored dword through an SGPR base
+    // and one VGPR offset, every loop rolled: what the compiler would otherwise
+    // hoist out of the pass loop (a 64-bit address per slot and row) took
+    // k_rs_jitw_scrub's allocation past v39, into the accumulators -- num_vgpr
+    // is no hard limit below 64 registers
+    typedef __attribute__((address_space(3))) uint8_t lds_u8;
+    typedef __attribute__((address_space(3))) uint32_t lds_u32;
+    lds_u8* syn = (lds_u8*)ldsb + kScrubMaskBytes + tw * e * 256;
+    unsigned hi1 = 0, lo1 = 0;
+#pragma unroll 1
+    for (int pass = 0; pass < 8; ++pass) {
+        // bytes 4 pass .. 4 pass + 3 of the lane's 32 of every row (zeros from an idle lane)
+        lds_u32* mine4 = (lds_u32*)(syn + r0 * 256 + lane * 4);
+        const uint32_t po4 = po + 4 * pass;
+        [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
+            (
+                [&] {
+                    if (Ss < nrow) {
+                        uint32_t W[8], st;
+                        // (s_nop 4: the row pointer may come straight from a
+                        // v_readlane -- k_rs_jitw_scrub<J16> keeps some of its 16 in
+                        // VGPR lanes -- and a VALU write of an SGPR needs 5 wait
+                        // states before a vector memory instruction reads it; the
+                        // compiler does not look into asm text for that)
+                        asm volatile("s_nop 4\n global_load_dword %0, %1, %2\n s_waitcnt vmcnt(0)"
+                                     : "=v"(st)
+                                     : "v"(po4), "s"(dp[Ss])
+                                     : "memory");
+                        SL::template read<Ss>(W);
+                        tr8(W, m4, m2, m1);  // computed parity, bytes
+                        uint32_t d = W[0];
+#pragma unroll
+                        for (int q = 1; q < 8; ++q)
+                            d = pass == q ? W[q] : d;
+                        mine4[Ss * 64] = inb ? d ^ st : 0u;
+                        __builtin_amdgcn_sched_barrier(0);  // slot by slot
+                    }
+                }(),
+                ...);
+        }(std::make_integer_sequence<int, SL::N>{});
+        __syncthreads();
+        for (int c = wave * 64 + lane; c < 256; c += 64 * NV) {
+            int nz = 0, p0 = 0;
+#pragma unroll 1
+            for (int p = 0; p < e; ++p) {
+                const bool on = syn[p * 256 + c] != 0;
+                nz += on;
+                p0 = on ? p : p0;
+            }
+            if (!nz)
+                continue;
+            // locate: the matrix is locatable, so e >= 2
+            const int row = scrub_locate_row(k, e, s.tab, s.tab + 256, kGfJit, syn[c], syn[256 + c], nz, p0,
+                                             [&](int p) { return syn[p * 256 + c]; });
+            hi1 = max(hi1, row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
+            lo1 = max(lo1, row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
+        }
+        __syncthreads();  // the next pass overwrites syn
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        hi1 = max(hi1, (unsigned)__shfl_down((int)hi1, o, 64));
+        lo1 = max(lo1, (unsigned)__shfl_down((int)lo1, o, 64));
+    }
+    if (lane == 0 && hi1) {
+        atomicMax(&f->hi1, hi1);
+        atomicMax(&f->lo1, lo1);
+    }
+}
+
+// The epilogues of k_rs_jit's body (jit_run).  The store: outputs back to
+// bytes and out (every source of this tile was read before the last barrier).
+struct JitStore {
+    template <int NW>
+    __device__ __forceinline__ void run(const JitArgs& a, uint8_t* const* const& dsts, int, const int& wave, int,
+                                        const long long& off, uint4*, const uint32_t& m4, const uint32_t& m2,
+                                        const uint32_t& m1) const
+    {
+        if (off + 32 <= a.len) {
+            [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
+                (
+                    [&] {
+                        const int r = wave * 8 + Ss;
+                        if (r < a.rows) {
+                            uint32_t W[8];
+                            read_slot<Ss>(W);
+                            tr8(W, m4, m2, m1);
+                            store32((uint8_t*)sload_ptr((const uint8_t* const*)(dsts + r)), off, W);
+                        }
+                    }(),
+                    ...);
+            }(std::make_integer_sequence<int, 8>{});
+        }
+    }
+};
+
+// The scrub: wave w's rows [8 w, 8 w + 8) against the stored ones
+struct JitScrub8 : JitScrub {
+    template <int NW>
+    __device__ __forceinline__ void run(const JitArgs& a, uint8_t* const* dsts, int b, int wave, int,
+                                        long long off, uint4* lds, uint32_t m4, uint32_t m2, uint32_t m1) const
+    {
+        static_assert(kScrubMaskBytes + 32 * 256 <= 2 * C * 2 * 64 * 16, "rows <= 32: syn fits the chunk buffers");
+        const bool inb = off + 32 <= a.len;
+        scrub_slots<Slots8, NW, 1>(*this, a.k, a.rows, dsts, b, wave * 8, min(8, a.rows - wave * 8), wave, 0, inb,
+                                   inb ? (uint32_t)off : 0u, reinterpret_cast<uint8_t*>(lds), m4, m2, m1);
+    }
+};
+
+// `int B` and `long long TILE`: this workgroup's block and its tile
+// (k_rs_jitw: its index) within the block.  Workgroups are dealt round-robin
+// over the 8 XCDs: A.xcd_order gives each XCD a contiguous range of (block,
+// tile), so all tiles of a block (and its code) stay in one XCD's L2 -- it
+// matters when a block has few tiles.  (A macro: as a function taking
+// references it changed the code of k_rs_jit and k_rs_jitw.)
+#define RSGPU_JIT_PLACE(A, B, TILE)                                                                 \
+    int B = blockIdx.y;                                                                             \
+    long long TILE = blockIdx.x;                                                                    \
+    if ((A).xcd_order) {                                                                            \
+        const unsigned g = blockIdx.x + gridDim.x * blockIdx.y, tot = gridDim.x * gridDim.y;        \
+        const unsigned xcd = g & 7, q8 = tot >> 3, r8 = tot & 7;                                    \
+        const unsigned lin = xcd * q8 + min(xcd, r8) + (g >> 3);                                    \
+        B = (int)(lin / gridDim.x);                                                                 \
+        TILE = lin - (unsigned)B * gridDim.x;                                                       \
+    }
+
+// The body of k_rs_jit and k_rs_jit_scrub on block b, tile `tile`: the
+// accumulation, then the epilogue `epi` on the wave's slots (JitStore,
+// JitScrub8).  The kernels place the workgroup (RSGPU_JIT_PLACE) and skip a
+// block by its status themselves: a `return` in here would be a branch to the
+// kernel's one exit, and k_rs_jit's code another than it was.
+template <int NW, bool SH, class H, class Epi>
+__device__ __forceinline__ void jit_run(const JitArgs& a, uint4 (&lds)[2][C * 2 * 64], int wave, int lane, int b,
+                                        long long tile, const Epi& epi)
+{
     const int k = a.k;
     const int nch = (k + C - 1) / C;
     const uint8_t* const* srcs = a.srcs + (size_t)b * k;
@@ -214,25 +452,40 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void 
                        RSGPU_TC_ACC_CLOBBERS);
         jp.mark(4);
     }
-    // outputs back to bytes and out (every source of this tile was read
-    // before the last barrier)
-    if (off + 32 <= a.len) {
-        [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
-            (
-                [&] {
-                    const int r = wave * 8 + Ss;
-                    if (r < a.rows) {
-                        uint32_t W[8];
-                        read_slot<Ss>(W);
-                        tr8(W, m4, m2, m1);
-                        store32((uint8_t*)sload_ptr((const uint8_t* const*)(dsts + r)), off, W);
-                    }
-                }(),
-                ...);
-        }(std::make_integer_sequence<int, 8>{});
-    }
+    epi.template run<NW>(a, dsts, b, wave, lane, off, &lds[0][0], m4, m2, m1);
     jp.mark(5);
     jp.end(lane);
+}
+
+// amdgpu_num_vgpr(64): the compiler allocates v0..v63 only (minus the
+// registers the call clobbers); the accumulators v64..v127 are touched by asm
+// and generated code alone.  (Holding the block's row pointers in VGPRs and
+// reading them with v_readlane instead of scalar loads measured slower:
+// 26.3 vs 25.1 ms at C3, tools/jit_profile.)
+// SH: one program shared by every block (the GENERATED encode; a distinct
+// symbol, so profiles tell it from the per-block decode)
+template <int NW, bool SH, class H = JitHooks>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void k_rs_jit(JitArgs a)
+{
+    __shared__ uint4 lds[2][C * 2 * 64];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(a, b, tile)
+    if (a.status && a.status[b] != 0)
+        return;  // uniform per workgroup: the whole block is skipped
+    jit_run<NW, SH, H>(a, lds, wave, lane, b, tile, JitStore{});
+}
+
+// The generated scrub for e <= 16: k_rs_jit<NW, true>'s accumulation on the
+// matrix's shared program, then the scrub epilogue (scrub_slots)
+template <int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void k_rs_jit_scrub(JitScrubArgs s)
+{
+    __shared__ uint4 lds[2][C * 2 * 64];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(s.j, b, tile)
+    jit_run<NW, true, JitHooks>(s.j, lds, wave, lane, b, tile, JitScrub8{{s.fold, s.tab, s.locate}});
 }
 
 template <int S>
@@ -264,6 +517,91 @@ __device__ __forceinline__ void read_slotw(uint32_t (&W)[8])
     }
 }
 
+// k_rs_jitw's R slots, as the scrub epilogue reads them
+template <int R>
+struct SlotsW {
+    static constexpr int N = R;
+    template <int S>
+    __device__ __forceinline__ static void read(uint32_t (&W)[8])
+    {
+        read_slotw<S>(W);
+    }
+    template <int S>
+    __device__ __forceinline__ static void xor_into(uint32_t (&P)[8])
+    {
+#define RSGPU_JW_XS(TEXT)                                                                                        \
+    asm volatile(TEXT : "+v"(P[0]), "+v"(P[1]), "+v"(P[2]), "+v"(P[3]), "+v"(P[4]), "+v"(P[5]), "+v"(P[6]), \
+                 "+v"(P[7]))
+        if constexpr (S == 0) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_0);
+        if constexpr (S == 1) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_1);
+        if constexpr (S == 2) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_2);
+        if constexpr (S == 3) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_3);
+        if constexpr (S == 4) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_4);
+        if constexpr (S == 5) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_5);
+        if constexpr (S == 6) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_6);
+        if constexpr (S == 7) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_7);
+        if constexpr (S == 8) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_8);
+        if constexpr (S == 9) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_9);
+        if constexpr (S == 10) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_10);
+        if constexpr (S == 11) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_11);
+        if constexpr (S == 12) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_12);
+        if constexpr (S == 13) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_13);
+        if constexpr (S == 14) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_14);
+        if constexpr (S == 15) RSGPU_JW_XS(RSGPU_JW_XOR_SLOT_15);
+#undef RSGPU_JW_XS
+    }
+};
+
+// The epilogues of k_rs_jitw's body (jitw_run): the store ...
+struct JitwStore {
+    template <class W, int TPW, int NV>
+    __device__ __forceinline__ void run(const JitArgs& a, uint8_t* const* const& dsts, int, const int& wave, int,
+                                        int, const long long& off, uint4*) const
+    {
+        constexpr int R = W::R;
+        // the output pointers likewise: all R loads under one wait
+        typedef uint8_t* const __attribute__((address_space(4)))* CDsts;
+        const int r0 = jit::wide_row0(a.rows, wave), nrow = jit::wide_row0(a.rows, wave + 1) - r0;
+        uint8_t* dp[R];
+#pragma unroll
+        for (int i = 0; i < R; ++i)
+            dp[i] = ((CDsts)dsts)[min(r0 + i, a.rows - 1)];
+        if (off + 32 <= a.len) {
+            const uint32_t m4 = vconst(0x0F0F0F0Fu), m2 = vconst(0x33333333u), m1 = vconst(0x55555555u);
+            [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
+                (
+                    [&] {
+                        if (Ss < nrow) {
+                            uint32_t Wd[8];
+                            read_slotw<Ss>(Wd);
+                            tr8(Wd, m4, m2, m1);
+                            store32(dp[Ss], off, Wd);
+                        }
+                    }(),
+                    ...);
+            }(std::make_integer_sequence<int, R>{});
+        }
+    }
+};
+
+// ... and the scrub: the wave's rows [wide_row0(e, wave), wide_row0(e, wave +
+// 1)) against the stored ones.  (tile index >= ntile with TPW > 1: off is
+// past the row end, so every lane of that tile is idle.)
+struct JitwScrub : JitScrub {
+    template <class W, int TPW, int NV>
+    __device__ __forceinline__ void run(const JitArgs& a, uint8_t* const* dsts, int b, int wave, int tw, int,
+                                        long long off, uint4* lds) const
+    {
+        static_assert(kScrubMaskBytes + TPW * (NV == 4 ? 64 : 32) * 256 <= 2 * TPW * W::CS * 2 * 64 * 16,
+                      "e <= 32 (two waves), e <= 64 (four): syn fits the chunk buffers");
+        const uint32_t m4 = vconst(0x0F0F0F0Fu), m2 = vconst(0x33333333u), m1 = vconst(0x55555555u);
+        const int r0 = jit::wide_row0(a.rows, wave), nrow = jit::wide_row0(a.rows, wave + 1) - r0;
+        const bool inb = off + 32 <= a.len;
+        scrub_slots<SlotsW<W::R>, NV, TPW>(*this, a.k, a.rows, dsts, b, r0, nrow, wave, tw, inb,
+                                           inb ? (uint32_t)off : 0u, reinterpret_cast<uint8_t*>(lds), m4, m2, m1);
+    }
+};
+
 // The same decode with R rows per wave (rs_jit.h Wide): 2 waves per column
 // tile; R = 16: 168 VGPRs (3 waves per SIMD), chunks of 6 sources (6
 // workgroups per CU); R = 10: 120 VGPRs (4 waves per SIMD), chunks of 5 (8
@@ -279,28 +617,13 @@ __device__ __forceinline__ void read_slotw(uint32_t (&W)[8])
 // TPW waves; wave w: tile w / 2, rows of wave w % 2), so the TPW waves with
 // the same rows run the same code between the same chunk barriers and share
 // its instruction-cache lines.
-template <class W, int TPW, int NV>
-__global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40))) void k_rs_jitw(JitArgs a)
+// The body of k_rs_jitw and k_rs_jitw_scrub on block b, the block's workgroup
+// wg (as jit_run): the accumulation, then the epilogue `epi` on the wave's slots.
+template <class W, int TPW, int NV, class Epi>
+__device__ __forceinline__ void jitw_run(const JitArgs& a, uint4 (&lds)[2][TPW][W::CS * 2 * 64], int wv, int wave,
+                                         int tw, int lane, int b, long long wg, long long tile, const Epi& epi)
 {
     constexpr int CS = W::CS, R = W::R;
-    __shared__ uint4 lds[2][TPW][CS * 2 * 64];
-    RSGPU_DIAG_BEGIN()
-    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int wave = wv % NV, tw = wv / NV;  // rows of the wave, its tile in the workgroup
-    const int lane = threadIdx.x & 63;
-    int b = blockIdx.y;
-    long long tile = blockIdx.x;
-    if (a.xcd_order) {  // as k_rs_jit
-        const unsigned g = blockIdx.x + gridDim.x * blockIdx.y, tot = gridDim.x * gridDim.y;
-        const unsigned xcd = g & 7, q8 = tot >> 3, r8 = tot & 7;
-        const unsigned lin = xcd * q8 + min(xcd, r8) + (g >> 3);
-        b = (int)(lin / gridDim.x);
-        tile = lin - (unsigned)b * gridDim.x;
-    }
-    const long long wg = tile;  // this workgroup's index within its block
-    tile = tile * TPW + tw;
-    if (a.status && a.status[b] != 0)
-        return;
     const int k = a.k;
     const int nch = (k + CS - 1) / CS;
     const int bw = (int)Hooks::data_block(b);
@@ -459,31 +782,39 @@ __global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40)))
                          : RSGPU_JW_CALL_CLOBBERS, "s82", "s83", "scc", "memory", RSGPU_J10_ACC_CLOBBERS);
         ph.mark(5);  // phase 5: the generated code
     }
-    // the output pointers likewise: all R loads under one wait
-    typedef uint8_t* const __attribute__((address_space(4)))* CDsts;
-    const int r0 = jit::wide_row0(a.rows, wave), nrow = jit::wide_row0(a.rows, wave + 1) - r0;
-    uint8_t* dp[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i)
-        dp[i] = ((CDsts)dsts)[min(r0 + i, a.rows - 1)];
-    if (off + 32 <= a.len) {
-        const uint32_t m4 = vconst(0x0F0F0F0Fu), m2 = vconst(0x33333333u), m1 = vconst(0x55555555u);
-        [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
-            (
-                [&] {
-                    if (Ss < nrow) {
-                        uint32_t Wd[8];
-                        read_slotw<Ss>(Wd);
-                        tr8(Wd, m4, m2, m1);
-                        store32(dp[Ss], off, Wd);
-                    }
-                }(),
-                ...);
-        }(std::make_integer_sequence<int, R>{});
-    }
-    ph.mark(6);  // phase 6: output transposes and stores
+    epi.template run<W, TPW, NV>(a, dsts, bw, wave, tw, lane, off, &lds[0][0][0]);
+    ph.mark(6);  // phase 6: output transposes and stores (the scrub: stored rows, compare)
     ph.end(wv);
+}
+
+template <class W, int TPW, int NV>
+__global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40))) void k_rs_jitw(JitArgs a)
+{
+    __shared__ uint4 lds[2][TPW][W::CS * 2 * 64];
+    RSGPU_DIAG_BEGIN()
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wv % NV, tw = wv / NV;  // rows of the wave, its tile in the workgroup
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(a, b, wg)  // wg: this workgroup's index within its block
+    const long long tile = wg * TPW + tw;
+    if (a.status && a.status[b] != 0)
+        return;
+    jitw_run<W, TPW, NV>(a, lds, wv, wave, tw, lane, b, wg, tile, JitwStore{});
     RSGPU_DIAG_END();
+}
+
+// The generated scrub for 16 < e <= 64: k_rs_jitw's accumulation on the
+// matrix's shared program, then the scrub epilogue (scrub_slots)
+template <class W, int TPW, int NV>
+__global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40))) void k_rs_jitw_scrub(JitScrubArgs s)
+{
+    __shared__ uint4 lds[2][TPW][W::CS * 2 * 64];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wv % NV, tw = wv / NV;
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(s.j, b, wg)
+    const long long tile = wg * TPW + tw;
+    jitw_run<W, TPW, NV>(s.j, lds, wv, wave, tw, lane, b, wg, tile, JitwScrub{{s.fold, s.tab, s.locate}});
 }
 
 // every 8-byte slot a return: a call that lands in code never written
@@ -833,6 +1164,48 @@ hipError_t launch_rs_jit(const JitArgs& a, long long blocks, hipStream_t st)
     case 8: hipLaunchKernelGGL((jitk::k_rs_jit<4, false>), grid, dim3(256), 0, st, a); break;
     default: hipLaunchKernelGGL((jitk::k_rs_jit<4, true>), grid, dim3(256), 0, st, a); break;
     }
+    return hipGetLastError();
+}
+
+// The grids and the kernel choice of launch_rs_jit (shared program) and
+// launch_rs_jitw, on the scrub kernels.
+hipError_t launch_rs_jit_scrub(const JitScrubArgs& s, long long blocks, hipStream_t st)
+{
+    const JitArgs& a = s.j;
+    if (a.rows <= 0 || a.rows > 64 || a.dst_stride < a.rows || a.k <= 0 || !a.code || a.chunk_stride <= 0 ||
+        a.block_stride != 0 || a.status || a.len <= 0 || a.len % 32 || a.len >= (1LL << 32) || blocks <= 0 ||
+        blocks > (long long)kMaxGridBlocks || !s.fold || (s.locate && !s.tab))
+        return hipErrorInvalidValue;
+    const long long ntile = (a.len + 2047) / 2048;
+    if (!jitw_rows(a.rows)) {  // e <= 16
+        dim3 grid((unsigned)ntile, (unsigned)blocks);
+        if (a.rows <= 8)
+            hipLaunchKernelGGL((jitk::k_rs_jit_scrub<1>), grid, dim3(64), 0, st, s);
+        else
+            hipLaunchKernelGGL((jitk::k_rs_jit_scrub<2>), grid, dim3(128), 0, st, s);
+        return hipGetLastError();
+    }
+    const int nv = jit::wide_waves(a.rows);
+    const int tpw = nv == 4 ? 1 : a.tiles_per_wg >= 3 ? 3 : a.tiles_per_wg == 2 ? 2 : 1;
+    dim3 grid((unsigned)((ntile + tpw - 1) / tpw), (unsigned)blocks);
+    dim3 blk(64 * nv * tpw);
+#define RSGPU_JW_LAUNCH(WT)                                                                              \
+    if (nv == 4)                                                                                         \
+        hipLaunchKernelGGL((jitk::k_rs_jitw_scrub<WT, 1, 4>), grid, blk, 0, st, s);                      \
+    else                                                                                                 \
+        switch (tpw) {                                                                                   \
+        case 3: hipLaunchKernelGGL((jitk::k_rs_jitw_scrub<WT, 3, 2>), grid, blk, 0, st, s); break;      \
+        case 2: hipLaunchKernelGGL((jitk::k_rs_jitw_scrub<WT, 2, 2>), grid, blk, 0, st, s); break;      \
+        default: hipLaunchKernelGGL((jitk::k_rs_jitw_scrub<WT, 1, 2>), grid, blk, 0, st, s); break;     \
+        }
+    if (jitw_rows(a.rows) == 16) {
+        RSGPU_JW_LAUNCH(jit::J16)
+    } else if (jitw_rows(a.rows) == 12) {
+        RSGPU_JW_LAUNCH(jit::J12)
+    } else {
+        RSGPU_JW_LAUNCH(jit::J10)
+    }
+#undef RSGPU_JW_LAUNCH
     return hipGetLastError();
 }
 

@@ -235,6 +235,19 @@ size_t jitw_pass_offset(int k, int e, int p);
 hipError_t launch_jitw_emit(int k, int e, long long blocks, const uint8_t* coef, const int* status,
                             uint8_t* code, hipStream_t st);
 hipError_t launch_rs_jitw(const JitArgs& a, long long blocks, hipStream_t st);
+// The generated scrub (k_rs_jit_scrub, k_rs_jitw_scrub): the shared program's
+// accumulation exactly as the encode runs it, then the stored parity rows read
+// through j.dsts (never written) and compared in registers.  j.rows = e <= 64
+// in one launch, j.block_stride == 0, j.status == nullptr, j.len < 2^32; the
+// fold zeroed before the launch; tab (read only with locate): [rowtab 256 B |
+// e x k matrix], the head of the two-pass scratch.
+struct JitScrubArgs {
+    JitArgs j;
+    ScrubFold* fold;     // [B]
+    const uint8_t* tab;
+    int locate;
+};
+hipError_t launch_rs_jit_scrub(const JitScrubArgs& a, long long blocks, hipStream_t st);
 // small uploads through the kernel arguments (k_put_words): bytes % 8 == 0,
 // at most sizeof(PutArgs::w)
 struct PutArgs {

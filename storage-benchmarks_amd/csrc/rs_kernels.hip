@@ -679,10 +679,6 @@ __global__ __launch_bounds__(256) void k_compare_rows(const uint8_t* __restrict_
 // Any alignment, any length; this path is the yardstick, the compiled codes
 // scrub in k_rs_bs_scrub.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint8_t scrub_mul(uint8_t a, uint8_t b)
-{
-    return (a && b) ? kGfTables.exp[kGfTables.log[a] + kGfTables.log[b]] : 0;
-}
 // a / b, b != 0
 __device__ __forceinline__ uint8_t scrub_div(uint8_t a, uint8_t b)
 {
@@ -716,20 +712,9 @@ __device__ __forceinline__ void scrub_column(const A& a, const uint8_t* calc, co
     ++bad;
     if (!a.locate)
         return;
-    int row = -1;
-    if (s0 && s1) {
-        const int r = a.rowtab[scrub_div(s1, s0)];
-        if (r != 255) {
-            const uint8_t x = scrub_div(s0, a.coef[r]);  // c[0][r] != 0: the matrix is locatable
-            bool ok = true;
-            for (int p = 2; p < a.e; ++p)
-                ok &= (uint8_t)(calc[(size_t)p * a.pitch + i] ^ par[(size_t)p * a.pitch + i]) ==
-                      scrub_mul(a.coef[(size_t)p * a.k + r], x);
-            row = ok ? r : -1;
-        }
-    } else if (nz == 1) {
-        row = a.k + p0;
-    }
+    const int row = scrub_locate_row(a.k, a.e, a.rowtab, a.coef, kGfTables, s0, s1, nz, p0, [&](int p) {
+        return (uint8_t)(calc[(size_t)p * a.pitch + i] ^ par[(size_t)p * a.pitch + i]);
+    });
     if constexpr (A::kRepair) {
         if (a.mode != kRepairLocate && row >= 0) {
             if (row < a.k)

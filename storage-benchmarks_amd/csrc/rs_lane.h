@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "../../include/rsgpu.h"
+#include "gf256.h"
 #include "rs_kernels.h"
 
 namespace rsgpu {
@@ -83,6 +84,36 @@ __device__ __forceinline__ void col_store(uint8_t* row, long long c, const Col<W
     } else {
         ((g_u8*)row)[c] = (uint8_t)v.d[0];
     }
+}
+
+// The row that explains a bad byte column of a locatable matrix (rsgpu.h), or
+// -1: with s_0 and s_1 non-zero the ratio s_1 / s_0 picks the only source row
+// r that can (rowtab, 255: none), x = s_0 / c[0][r], and every other syndrome
+// must equal c[p][r] x; a column whose only non-zero syndrome is s_p0 is
+// parity row k + p0.  nz: the column's non-zero syndromes (>= 1), p0: the
+// last of them, syn(p): syndrome p of the column.  coef: the e x k matrix.
+// One copy for k_scrub_compare, k_repair_compare (rs_kernels.hip) and the
+// generated scrub's cold path (rs_jit.hip).
+template <class Syn>
+__host__ __device__ __forceinline__ int scrub_locate_row(int k, int e, const uint8_t* rowtab, const uint8_t* coef,
+                                                         const GfTables& gf, uint8_t s0, uint8_t s1, int nz, int p0,
+                                                         Syn&& syn)
+{
+    if (s0 && s1) {
+        const int r = rowtab[gf.exp[gf.log[s1] + 255 - gf.log[s0]]];
+        if (r == 255)
+            return -1;
+        // log x of x = s_0 / c[0][r] (c[0][r] != 0: the matrix is locatable), in [0, 255)
+        int lx = gf.log[s0] + 255 - gf.log[coef[r]];
+        lx = lx >= 255 ? lx - 255 : lx;
+        bool ok = true;
+        for (int p = 2; p < e; ++p) {
+            const uint8_t c = coef[(size_t)p * k + r];
+            ok &= (uint8_t)syn(p) == (c ? gf.exp[gf.log[c] + lx] : 0);
+        }
+        return ok ? r : -1;
+    }
+    return nz == 1 ? k + p0 : -1;
 }
 
 // A wave's bad columns into its block's fold (rs_kernels.h ScrubFold): one

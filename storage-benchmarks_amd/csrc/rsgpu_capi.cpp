@@ -187,6 +187,39 @@ const rsgpu_ctx::SharedProg* shared_program(rsgpu_ctx* ctx, const uint8_t* coef,
     return &ctx->progs.back();
 }
 
+// The launch arguments of pass p of the shared program pg of `rows` rows, on
+// the row pointers d_srcs [B][k] and d_dsts [B][rows]: a pass of <= 64 rows of
+// the two- / four-wave kernel (jitw_layout(rows)), else of <= 32 rows of the
+// 8-row kernel; every block on the same code.  The encode and the generated
+// scrub launch with these settings.
+JitArgs shared_pass_args(const rsgpu_ctx* ctx, const rsgpu_ctx::SharedProg* pg, int k, int rows, int p,
+                         long long len, const uint8_t* const* d_srcs, uint8_t* const* d_dsts)
+{
+    if (jitw_layout(rows)) {
+        JitArgs j = jit_args(d_srcs, d_dsts + jit::wide_pass_row0(rows, p),
+                             (const uint8_t*)pg->code + pg->passes[p].first, pg->passes[p].second, 0, k,
+                             jit::wide_pass_rows(rows, p), rows, len, nullptr);
+        j.tiles_per_wg = ctx->jitw_tpw ? ctx->jitw_tpw : 2;
+        // every block on the same code: the start-time chunk rotation
+        // (k_rs_jitw) lines up the workgroups of a CU pair on one chunk
+        // (same-process ABBA x6, profiles/r05_rot/shared/: C5 encode 12.96
+        // -> 12.37 ms, step -2.7 %; (48, 24) step -0.7 %; C3's generated
+        // encode 22.65 -> 21.73 ms, still 1.7 % behind k_rs_bs)
+        j.chunk_rot_ticks = ctx->jitw_rot >= 0 ? ctx->jitw_rot : jitw_rot_ticks(j.rows);
+        j.prio = ctx->jitw_prio;
+        return j;
+    }
+    const int nch = (k + 7) / 8;
+    JitArgs j = jit_args(d_srcs, d_dsts + 32 * p, (const uint8_t*)pg->code + (size_t)p * 4 * nch * pg->chunk_stride,
+                         pg->chunk_stride, 0, k, std::min(32, rows - 32 * p), rows, len, nullptr);
+    // no wave priority for the shared 8-row program: (32, 8)'s encode
+    // measured 15.25 -> 17.06 ms with it, (8, 2)'s +1 % (same process
+    // ABBA x6, profiles/r06_prio/r06_prio_small_e/); the per-block 8-row
+    // decode keeps it (16, 4) -1.4 %, (64, 16) -3.2 %
+    j.prio = 0;
+    return j;
+}
+
 // dsts[b][i] = sum_j coef[i][j] srcs[b][j] through the shared generated code,
 // in passes of <= 32 rows (aligned rows, len % 32 == 0)
 int shared_program_launch(rsgpu_ctx* ctx, const uint8_t* coef, int k, int rows, long long len,
@@ -197,36 +230,11 @@ int shared_program_launch(rsgpu_ctx* ctx, const uint8_t* coef, int k, int rows, 
     const rsgpu_ctx::SharedProg* pg = shared_program(ctx, coef, k, rows, &rc);
     if (!pg)
         return rc;
-    if (jitw_layout(rows)) {  // the two- / four-wave kernel, every block on the same code
-        for (int p = 0; p < jit::wide_passes(rows); ++p) {  // one pass up to 64 rows
-            JitArgs j = jit_args(d_srcs, d_dsts + jit::wide_pass_row0(rows, p),
-                                 (const uint8_t*)pg->code + pg->passes[p].first, pg->passes[p].second, 0, k,
-                                 jit::wide_pass_rows(rows, p), rows, len, nullptr);
-            j.tiles_per_wg = ctx->jitw_tpw ? ctx->jitw_tpw : 2;
-            // every block on the same code: the start-time chunk rotation
-            // (k_rs_jitw) lines up the workgroups of a CU pair on one chunk
-            // (same-process ABBA x6, profiles/r05_rot/shared/: C5 encode 12.96
-            // -> 12.37 ms, step -2.7 %; (48, 24) step -0.7 %; C3's generated
-            // encode 22.65 -> 21.73 ms, still 1.7 % behind k_rs_bs)
-            j.chunk_rot_ticks = ctx->jitw_rot >= 0 ? ctx->jitw_rot : jitw_rot_ticks(j.rows);
-            j.prio = ctx->jitw_prio;
-            KTimer kt(ctx, name, (size_t)blocks);
-            RS_HIP(ctx, launch_rs_jitw(j, blocks, ctx->stream));
-        }
-        return RSGPU_OK;
-    }
-    const int nch = (k + 7) / 8;
-    for (int p = 0; p * 32 < rows; ++p) {
-        JitArgs j = jit_args(d_srcs, d_dsts + 32 * p,
-                             (const uint8_t*)pg->code + (size_t)p * 4 * nch * pg->chunk_stride, pg->chunk_stride, 0,
-                             k, std::min(32, rows - 32 * p), rows, len, nullptr);
-        // no wave priority for the shared 8-row program: (32, 8)'s encode
-        // measured 15.25 -> 17.06 ms with it, (8, 2)'s +1 % (same process
-        // ABBA x6, profiles/r06_prio/r06_prio_small_e/); the per-block 8-row
-        // decode keeps it (16, 4) -1.4 %, (64, 16) -3.2 %
-        j.prio = 0;
+    const bool wide = jitw_layout(rows);  // one pass up to 64 rows
+    for (int p = 0; wide ? p < jit::wide_passes(rows) : p * 32 < rows; ++p) {
+        const JitArgs j = shared_pass_args(ctx, pg, k, rows, p, len, d_srcs, d_dsts);
         KTimer kt(ctx, name, (size_t)blocks);
-        RS_HIP(ctx, launch_rs_jit(j, blocks, ctx->stream));
+        RS_HIP(ctx, wide ? launch_rs_jitw(j, blocks, ctx->stream) : launch_rs_jit(j, blocks, ctx->stream));
     }
     return RSGPU_OK;
 }
@@ -396,6 +404,24 @@ int encode_slice(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t 
 }  // namespace
 
 namespace rsgpu {
+
+int shared_program_scrub(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long blocks,
+                         const uint8_t* const* d_srcs, const uint8_t* const* d_par, ScrubFold* fold,
+                         const uint8_t* tab, int locate, const char* name)
+{
+    int rc = RSGPU_OK;
+    const rsgpu_ctx::SharedProg* pg = shared_program(ctx, coef, k, e, &rc);
+    if (!pg)
+        return rc;
+    JitScrubArgs s{};
+    s.j = shared_pass_args(ctx, pg, k, e, 0, len, d_srcs, (uint8_t* const*)d_par);  // e <= 64: one pass
+    s.fold = fold;
+    s.tab = tab;
+    s.locate = locate;
+    KTimer kt(ctx, name, (size_t)blocks);
+    RS_HIP(ctx, launch_rs_jit_scrub(s, blocks, ctx->stream));
+    return RSGPU_OK;
+}
 
 const GfTables& host_gf()
 {

@@ -74,6 +74,16 @@ bool tc_handlers_ready(rsgpu_ctx* ctx);
 // once per context
 int jit_probe(rsgpu_ctx* ctx);
 
+// The generated scrub of `blocks` blocks on the shared program of the e x k
+// matrix `coef` (e <= 64, jit_probe(ctx) == 1; the program the GENERATED encode
+// of the same matrix runs, built on first use), with the encode's launch
+// settings: d_srcs [B][k] and d_par [B][e] row pointers (16-byte aligned rows,
+// len % 32 == 0, the parity only read), rs_kernels.h JitScrubArgs for the
+// rest.  Recorded as `name`.
+int shared_program_scrub(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long blocks,
+                         const uint8_t* const* d_srcs, const uint8_t* const* d_par, ScrubFold* fold,
+                         const uint8_t* tab, int locate, const char* name);
+
 // >= bytes of executable device memory at ctx->d_jit, a new generation when regrown
 int jit_ensure(rsgpu_ctx* ctx, size_t bytes);
 

@@ -72,7 +72,7 @@ int locator(rsgpu_ctx* ctx, int k, int e, const unsigned char* coef, const char*
 bool fused_eligible(const rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, const void* d_src,
                     const void* d_parity, const unsigned char* coef)
 {
-    return ctx->scrub_kernel != RSGPU_SCRUB_TWO_PASS && !coef && rs_bitsliced_available(k, e) && len % 32 == 0 &&
+    return (ctx->scrub_kernel == RSGPU_SCRUB_AUTO || ctx->scrub_kernel == RSGPU_SCRUB_FUSED) && !coef && rs_bitsliced_available(k, e) && len % 32 == 0 &&
            len < (1ull << 32) && pitch % 16 == 0 && (uintptr_t)d_src % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
 }
 
@@ -94,6 +94,25 @@ int grow_parity_scratch(rsgpu_ctx* ctx, size_t blocks, size_t per_block)
     return ensure_device(ctx, ctx->scrub, kScrubTabBytes + parity_slice(blocks, per_block) * per_block);
 }
 
+// The tables of `loc` at the head of ctx->scrub (>= kScrubTabBytes), uploaded
+// when it holds another matrix's
+int upload_locator(rsgpu_ctx* ctx, int k, int e, const Locator& loc)
+{
+    std::vector<uint8_t> key = matrix_key(k, e, loc.c);
+    if (key == ctx->scrub.key)
+        return RSGPU_OK;
+    void* stage;
+    int rc = get_stage(ctx, 256 + loc.c.size(), &stage);
+    if (rc)
+        return rc;
+    std::memcpy(stage, loc.rowtab, 256);
+    std::memcpy((char*)stage + 256, loc.c.data(), loc.c.size());
+    rc = upload(ctx, ctx->scrub.p, 256 + loc.c.size());
+    if (!rc)
+        ctx->scrub.key = std::move(key);
+    return rc;
+}
+
 // The two-pass walk over blocks [first, first + count) of d_src: the scratch
 // grown, the tables of `loc` (when given) at its head, uploaded when it holds
 // another matrix's; then slice by slice the encode into the scratch and
@@ -105,18 +124,8 @@ int two_pass(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t firs
 {
     const size_t per_block = (size_t)e * pitch, slice = parity_slice(count, per_block);
     int rc = grow_parity_scratch(ctx, count, per_block);
-    std::vector<uint8_t> key;
-    if (!rc && loc && (key = matrix_key(k, e, loc->c)) != ctx->scrub.key) {
-        void* stage;
-        rc = get_stage(ctx, 256 + loc->c.size(), &stage);
-        if (rc)
-            return rc;
-        std::memcpy(stage, loc->rowtab, 256);
-        std::memcpy((char*)stage + 256, loc->c.data(), loc->c.size());
-        rc = upload(ctx, ctx->scrub.p, 256 + loc->c.size());
-        if (!rc)
-            ctx->scrub.key = std::move(key);
-    }
+    if (!rc && loc)
+        rc = upload_locator(ctx, k, e, *loc);
     uint8_t* calc = (uint8_t*)ctx->scrub.p + kScrubTabBytes;
     for (size_t b0 = first; !rc && b0 < first + count; b0 += slice) {
         const size_t nb = std::min(slice, first + count - b0);
@@ -371,7 +380,7 @@ int rsgpu_scrub_locatable(int k, int e, const unsigned char* coef)
 
 int rsgpu_set_scrub_kernel(rsgpu_ctx* ctx, int kernel)
 {
-    if (!ctx || kernel < RSGPU_SCRUB_AUTO || kernel > RSGPU_SCRUB_TWO_PASS)
+    if (!ctx || kernel < RSGPU_SCRUB_AUTO || kernel > RSGPU_SCRUB_GENERATED)
         return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_scrub_kernel: unknown kernel");
     ctx->scrub_kernel = kernel;
     return RSGPU_OK;
@@ -416,9 +425,42 @@ int rsgpu_scrub_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, s
         return RSGPU_OK;
     };
     const bool fused = fused_eligible(ctx, k, e, len, pitch, d_src, d_parity, coef);
+    // GENERATED: any matrix, with or without `coef` (rsgpu.h)
+    const bool generated = work && ctx->scrub_kernel == RSGPU_SCRUB_GENERATED &&
+                           rows_aligned(len, pitch, d_src, d_parity) && len < (1ull << 32) && e <= 64 &&
+                           jit_probe(ctx) == 1;
+    // the matrix's shared program on a slice, the stored parity compared in
+    // registers: row pointers into the context's scratch as the encode's, the
+    // locate tables where the two-pass scratch has them, no parity scratch
+    auto generated_slice = [&](size_t b0, size_t nb) -> int {
+        const std::vector<uint8_t> c = locate ? loc.c : parity_matrix(k, e, coef);
+        const size_t src_ptr_bytes = align_up(sizeof(void*) * (size_t)k * nb, 256);
+        const size_t par_ptr_bytes = align_up(sizeof(void*) * (size_t)e * nb, 256);
+        int grc = ensure_scratch(ctx, src_ptr_bytes + par_ptr_bytes);
+        if (!grc)
+            grc = ensure_device(ctx, ctx->scrub, kScrubTabBytes);
+        if (!grc && locate)
+            grc = upload_locator(ctx, k, e, loc);
+        if (grc)
+            return grc;
+        char* d = (char*)ctx->scratch.p;
+        RS_HIP(ctx, launch_row_ptrs(d_src + b0 * k * pitch, (long long)pitch, k, (long long)nb, (const uint8_t**)d,
+                                    ctx->stream));
+        RS_HIP(ctx, launch_row_ptrs(d_parity + b0 * e * pitch, (long long)pitch, e, (long long)nb,
+                                    (const uint8_t**)(d + src_ptr_bytes), ctx->stream));
+        return shared_program_scrub(ctx, c.data(), k, e, (long long)len, (long long)nb, (const uint8_t* const*)d,
+                                    (const uint8_t* const*)(d + src_ptr_bytes), fold + b0,
+                                    (const uint8_t*)ctx->scrub.p, locate ? 1 : 0, "k_rs_jit_scrub");
+    };
     // block index in grid.y: larger batches as consecutive slices
     for (size_t b0 = 0; work && b0 < blocks; b0 += kMaxGridBlocks) {
         const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
+        if (generated) {
+            rc = generated_slice(b0, nb);
+            if (rc)
+                return rc;
+            continue;
+        }
         if (!fused) {
             rc = two_pass(ctx, k, e, len, pitch, b0, nb, d_src, coef, locate ? &loc : nullptr, compare);
             if (rc)

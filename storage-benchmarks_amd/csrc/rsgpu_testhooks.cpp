@@ -18,6 +18,7 @@
 #include "jit_prog.h"
 #include "rs_jit.h"
 #include "rs_kernels.h"
+#include "rs_lane.h"
 #include "rsgpu_ctx.h"
 
 using namespace rsgpu;
@@ -301,6 +302,26 @@ long long rsgpu_internal_jitw_emit_device(rsgpu_ctx* ctx, int k, int e, size_t b
     (void)hipFree(d_code);
     (void)hipFree(d_status);
     return rc;
+}
+
+// Test hook (not part of include/rsgpu.h): the scrub kernels' location rule
+// (rs_lane.h scrub_locate_row) on the host, for the CPU suite to compare with
+// the model's brute force: the row that explains the syndrome column syn [e]
+// (not all zero) under the e x k matrix coef and its ratio -> row table
+// rowtab [256] (255: none), or -1.
+int rsgpu_internal_scrub_locate_row(int k, int e, const unsigned char* rowtab, const unsigned char* coef,
+                                    const unsigned char* syn)
+{
+    static const GfTables gf = make_gf_tables();
+    int nz = 0, p0 = 0;
+    for (int p = 0; p < e; ++p)
+        if (syn[p]) {
+            ++nz;
+            p0 = p;
+        }
+    if (!nz || e < 2)
+        return -1;
+    return scrub_locate_row(k, e, rowtab, coef, gf, syn[0], syn[1], nz, p0, [&](int p) { return syn[p]; });
 }
 
 }  // extern "C"

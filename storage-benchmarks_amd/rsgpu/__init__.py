@@ -58,7 +58,7 @@ DECODE_KERNELS = {"auto": 0, "one_matrix": 1, "general": 3, "generated": 4,
 ENCODE_KERNELS = {"auto": 0, "compiled": 1, "generated": 2, "threaded": 3}
 # rsgpu_set_scrub_kernel choices, rsgpu_scrub_blocks' flag and report
 # (include/rsgpu.h rsgpu_scrub_report)
-SCRUB_KERNELS = {"auto": 0, "fused": 1, "two_pass": 2}
+SCRUB_KERNELS = {"auto": 0, "fused": 1, "two_pass": 2, "generated": 3}
 SCRUB_LOCATE = 1
 SCRUB_CLEAN, SCRUB_ONE_ROW, SCRUB_DAMAGED = 0, 1, 2
 SCRUB_REPORT_DTYPE = np.dtype([("bad_columns", "<u8"), ("status", "<i4"), ("row", "<i4")])
@@ -437,8 +437,12 @@ class Context:
                    "rsgpu_verify_blocks")
 
     def set_scrub_kernel(self, kernel: str) -> None:
-        """Scrub kernel of scrub_blocks: auto | fused | two_pass
-        (include/rsgpu.h rsgpu_set_scrub_kernel)."""
+        """Scrub kernel of scrub_blocks: auto | fused | two_pass | generated
+        (include/rsgpu.h rsgpu_set_scrub_kernel).  generated: the matrix's
+        shared generated program with the stored parity compared in registers,
+        for any matrix with e <= 64 on 16-byte aligned rows of len % 32 == 0;
+        opt-in, auto never picks it.  repair_blocks runs its two-pass form
+        under it."""
         self.check(lib().rsgpu_set_scrub_kernel(self._h, SCRUB_KERNELS[kernel]),
                    "rsgpu_set_scrub_kernel")
 
