@@ -541,8 +541,9 @@ int rsgpu_scrub_degraded_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t
  * need the rows in place is served 1.2 - 1.3 x faster by rsgpu_decode_general;
  * this call is for lists that differ from block to block, for rows that
  * should come back in place, and for the check.  Not built: host-resident
- * blocks, a generated-code form, the check with more than 7 listed rows, lists
- * of more than 32 rows, and more than one located row per block. */
+ * blocks, a generated-code form, the check with more than 7 listed rows, and
+ * lists of more than 32 rows.  (Several damaged rows per block are located by
+ * rsgpu_locate_blocks below, whose lists this call takes as they are.) */
 #define RSGPU_REBUILD_CHECK 1 /* flags: scrub the survivors first, let the verdict decide */
 #define RSGPU_REBUILD_MAX_LOST 32 /* the longest list without RSGPU_REBUILD_CHECK (and at most e) */
 int rsgpu_rebuild_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
@@ -568,6 +569,91 @@ int rsgpu_rebuild_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch,
 #define RSGPU_REBUILD_LANES 1
 #define RSGPU_REBUILD_THREADED 2
 int rsgpu_set_rebuild_kernel(rsgpu_ctx *ctx, int kernel);
+
+/* ---- several damaged rows per block, located -------------------------------- */
+
+/* The scrub names at most one row per block; a block damaged in two or more
+ * rows (a torn write across two devices, two bad sectors in one stripe) ends
+ * there as DAMAGED.  This call names up to min(u, e - 1) rows, in the list
+ * format rsgpu_rebuild_blocks takes, from all the block's columns together:
+ *
+ *   s     the block's syndromes as the scrub defines them (stored ^ recomputed
+ *         parity), one column of e bytes per byte column of the block
+ *   h_r   what a unit change of row r adds to the syndromes: column r of the
+ *         matrix for a data row, the unit vector of p for parity row k + p
+ *   W     the span of the block's non-zero syndrome columns, d = dim W
+ *   R     { r in [0, k + e) : h_r in W }
+ *
+ * Status per block:
+ *   CLEAN             no bad column; the list is all RSGPU_LOST_NONE
+ *   ONE_ROW           d <= u, |R| = d, rank(h_R) = d, and d == 1: `row` is the
+ *                     row, the list holds it
+ *   RSGPU_SCRUB_ROWS  the same with d >= 2: the list holds R, `row` its lowest
+ *   DAMAGED           anything else (d > u, |R| != d, or h_R dependent): `row`
+ *                     is -1 and the list all RSGPU_LOST_NONE
+ * bad_columns is the number of non-zero syndrome columns, as in the scrub.  No
+ * matrix is refused.  For a locatable matrix (rsgpu_scrub_locatable)
+ * rsgpu_scrub_blocks with RSGPU_SCRUB_LOCATE reports CLEAN or ONE_ROW on
+ * exactly the blocks where this call does, with all three fields equal.
+ *
+ * Two properties:
+ *   1. rank(h_R) = |R| is exactly the condition under which
+ *      rsgpu_rebuild_blocks does not answer BAD_MATRIX for the list (the lost
+ *      data rows are determined by the surviving parity rows when the columns
+ *      of the listed rows are independent).  Every located list can go
+ *      straight into the rebuild; a DAMAGED block has an all-NONE list, which
+ *      the rebuild leaves untouched.
+ *   2. When the damage lies in fewer than e rows R' of a matrix whose every e
+ *      columns of [C | I] are independent (MDS: gf_gen_cauchy1_matrix always),
+ *      the verdict is R' exactly or DAMAGED, never another set: W lies in
+ *      span(h_R'), so a row outside R' with h_r in W would make |R'| + 1 <= e
+ *      columns dependent, hence R is a subset of R'; and |R| = d = rank(h_R)
+ *      makes span(h_R) = W, which holds every syndrome column, so rows of R'
+ *      outside R carry no damage.  DAMAGED arises when the damage patterns do
+ *      not span all of span(h_R') (two rows hit only in the same single
+ *      column).  Without the MDS property a dependent extra row makes
+ *      |R| > d, and the block is DAMAGED.
+ * As the scrub's ONE_ROW, a verdict is the explanation with the fewest rows,
+ * not a proof: damage in e or more rows can imitate it.
+ *
+ * Layout, `coef` and accepted geometries as rsgpu_scrub_blocks: any len, any
+ * pitch >= len, any alignment; additionally 1 <= e <= 64 where there is work
+ * (e > 64: RSGPU_ERR_UNSUPPORTED, nothing enqueued).  d_rows is DEVICE memory,
+ * [blocks][u] bytes, 1 <= u <= RSGPU_LOCATE_MAX_ROWS, written in the d_lost
+ * format of rsgpu_rebuild_blocks: rows ascending, then RSGPU_LOST_NONE.
+ * d_report [blocks] is DEVICE memory, 8-byte aligned, overwritten by every
+ * call.  Nothing of d_src or d_parity is written.  e == 0 or len == 0: every
+ * block CLEAN.  e == 1: any bad column gives DAMAGED (W is everything, R every
+ * row).  Null pointers, a misaligned report or u outside [1, 8]:
+ * RSGPU_ERR_ARG, nothing enqueued, outputs untouched.  Enqueued on the
+ * context's stream, no synchronisation; more than 65535 blocks run as
+ * consecutive slices.
+ *
+ * Cost: the TWO_PASS scrub's -- the encode of a slice into the context's
+ * scratch, then k_locate_span, whose lanes read stored and recomputed parity
+ * once as k_scrub_compare's do -- plus, per bad byte column, one
+ * wave-cooperative reduction against a basis of at most u vectors (lane p
+ * holds syndrome p: one cross-lane read and one table multiply per lane and
+ * basis vector), and k_locate_finish, one wave per block (at most (k + e) d
+ * reduction steps).  Workgroups leave their bases in a context-owned candidate
+ * area of at most 64 MiB per group of blocks.  The result is a function of the
+ * block alone.  Measured at (64, 32), 1 MB rows, 1024 blocks on one MI355X
+ * (profiles/locate; the device-to-device copy ran at 5.14 TB/s):
+ * clean blocks 34.85 ms, the TWO_PASS scrub with RSGPU_SCRUB_LOCATE in the same
+ * process 34.66 ms (ratio 0.968 - 1.017 over 24 mirrored pairs, inside the
+ * pair's run-to-run spread); one row per block bad in 1 % of the columns 50.4
+ * ms, two rows 56.1 ms: a bad 16-byte column stops its wave's other 63 and
+ * costs about 1.5 ns over the device.  Blocks damaged in most of their columns
+ * are the worst case, every column taking the cooperative path: two whole
+ * rows bad per block 175.6 ms, 5 x the scrub.  Not built: a filter that
+ * skips blocks a previous scrub called CLEAN; a form fused into the encode;
+ * e > 64; u > 8; per-column decoding of blocks that end DAMAGED. */
+#define RSGPU_SCRUB_ROWS 4        /* the damage lies in exactly the 2..u listed rows */
+#define RSGPU_LOCATE_MAX_ROWS 8
+int rsgpu_locate_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                        const unsigned char *d_src, const unsigned char *d_parity,
+                        const unsigned char *coef, int u, unsigned char *d_rows,
+                        rsgpu_scrub_report *d_report);
 
 /* ---- repair in place of what the scrub locates ---------------------------- */
 

@@ -477,4 +477,36 @@ hipError_t launch_rebuild_wide_prepare(const RebuildWideArgs& a, hipStream_t st)
 // as long as no destination row is a source.
 hipError_t launch_rs_tc_counted(const TcArgs& a, long long blocks, hipStream_t st);
 
+// Locate several damaged rows per block (rsgpu_locate_blocks, rs_locate.hip).
+// k_locate_span compares stored with recomputed parity as the scrub does and
+// keeps, per workgroup, an echelon basis of the span of the syndrome columns
+// it met: workgroup x of block b writes slot slot0 + x of the block's `slots`
+// slots in the candidate area,
+//   [n, overflow, 8 bytes unused | n <= u vectors of 64 bytes]
+// at kLocateSlotBytes, and adds its bad columns to the report's first 8 bytes
+// (zeroed before the first launch, as the scrub's fold).  Every slot of a
+// block is written by exactly one workgroup of one launch before
+// k_locate_finish (one wave per block) merges them, finds the rows whose
+// column lies in the span and writes the list rows[b][u] and the report.
+constexpr size_t kLocateSlotBytes = 16 + 8 * 64;
+struct LocateArgs {
+    int k, e, u;
+    int work;  // 0: e == 0 or len == 0, the finish reports every block CLEAN
+    long long pitch, len, blocks;
+    const uint8_t* calc;   // [B][e] rows: the parity of the sources, recomputed
+    const uint8_t* par;    // [B][e] rows: the stored parity
+    const uint8_t* coef;   // device e x k matrix (the finish)
+    uint8_t* cand;         // [B] candidate areas at cand_stride
+    size_t cand_stride;
+    int slots;             // per block
+    uint8_t* rows;         // [B][u] (the finish)
+    ::rsgpu_scrub_report* report;  // [B]
+};
+// bytes == false: columns [col0, col1) are 16-byte units of 16-byte aligned
+// rows; bytes == true: byte columns, any alignment.  gx workgroups per block,
+// writing slots [slot0, slot0 + gx).  e <= 64.
+hipError_t launch_locate_span(const LocateArgs& a, bool bytes, long long col0, long long col1, unsigned gx, int slot0,
+                              hipStream_t st);
+hipError_t launch_locate_finish(const LocateArgs& a, hipStream_t st);
+
 }  // namespace rsgpu

@@ -1,5 +1,5 @@
 // rs_lane.h -- what the kernels of the scrub family share (rs_kernels.hip's
-// scrub and repair, rs_update.hip, rs_degraded.hip, rs_rebuild.hip): the lane's building
+// scrub and repair, rs_update.hip, rs_degraded.hip, rs_rebuild.hip, rs_locate.hip): the lane's building
 // blocks (v_perm multiply, three-way XOR, the 3-3-2 selector split of a dword
 // and the table multiply on it, a column of one row), the fold of a wave's bad
 // columns into a block's report, the verdict on a finished fold, and the

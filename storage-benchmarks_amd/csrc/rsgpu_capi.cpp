@@ -652,7 +652,8 @@ int rsgpu_destroy(rsgpu_ctx* ctx)
         return RSGPU_ERR_ARG;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (void* p : {ctx->scratch.p, ctx->scrub.p, ctx->d_update, ctx->degraded.p, ctx->rebuild.p})
+    for (void* p : {ctx->scratch.p, ctx->scrub.p, ctx->d_update, ctx->degraded.p, ctx->rebuild.p,
+                    ctx->locate.p})
         if (p)
             (void)hipFree(p);
     if (ctx->h_stage)

@@ -1,9 +1,9 @@
 // rsgpu_scrub.cpp -- the scrub family of the C ABI (include/rsgpu.h): parity
-// scrub, repair in place, partial-stripe update, degraded scrub and rebuild in
-// place.  Argument checks and launch sequences; the kernels are rs_kernels.hip
-// (two-pass compare, finalise), rs_bitsliced.hip (fused), rs_update.hip,
-// rs_degraded.hip, rs_rebuild.hip.  The encode and the decode are
-// rsgpu_capi.cpp and rsgpu_decode.cpp.
+// scrub, repair in place, partial-stripe update, degraded scrub, rebuild in
+// place and the locate of several rows.  Argument checks and launch sequences;
+// the kernels are rs_kernels.hip (two-pass compare, finalise), rs_bitsliced.hip
+// (fused), rs_update.hip, rs_degraded.hip, rs_rebuild.hip, rs_locate.hip.  The
+// encode and the decode are rsgpu_capi.cpp and rsgpu_decode.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +13,7 @@
 #include "../../include/rsgpu.h"
 #include "gf256.h"
 #include "rs_kernels.h"
+#include "rs_lane.h"
 #include "rsgpu_ctx.h"
 #include "rsgpu_internal.h"
 
@@ -180,6 +181,7 @@ constexpr const char* kUpdateNames[3] = {"k_update_blocks", "k_update_blocks(tai
 constexpr const char* kDegradedNames[3] = {"k_degraded_compare", "k_degraded_compare(tail)",
                                            "k_degraded_compare(bytes)"};
 constexpr const char* kRebuildNames[3] = {"k_rebuild_blocks", "k_rebuild_blocks(tail)", "k_rebuild_blocks(bytes)"};
+constexpr const char* kLocateNames[3] = {"k_locate_span", "k_locate_span(tail)", "k_locate_span(bytes)"};
 
 // The update's device buffer: [tab4 256 x 16 B | tabc 256 x 4 B | matrix].
 constexpr size_t kUpdTab4Bytes = 256 * sizeof(uint4);
@@ -773,6 +775,93 @@ int rsgpu_rebuild_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch,
         rc = launch_head_and_tail(ctx, kRebuildNames, ng, n16, (long long)len, launch);
         if (rc)
             return rc;
+    }
+    return RSGPU_OK;
+}
+
+int rsgpu_locate_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                        const unsigned char* d_src, const unsigned char* d_parity, const unsigned char* coef, int u,
+                        unsigned char* d_rows, rsgpu_scrub_report* d_report)
+{
+    int rc = check_geom(ctx, k, e, len, pitch, blocks);
+    if (rc)
+        return rc;
+    if (!d_report || (uintptr_t)d_report % 8 != 0 || u < 1 || u > RSGPU_LOCATE_MAX_ROWS || !d_rows)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_locate_blocks: bad report pointer, u or list");
+    const bool work = e > 0 && len > 0;
+    if (work && (!d_src || !d_parity))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_locate_blocks: null rows");
+    if (e > 64)  // a lane of the wave per syndrome
+        return fail(ctx, RSGPU_ERR_UNSUPPORTED, "rsgpu_locate_blocks: needs e <= 64");
+    // Two nested slicings, as the degraded scrub's.  A group of blocks shares
+    // one finish: its candidate areas fit kDegTabBytes, its blocks fit a grid.
+    // Inside it a slice is what the scrub scratch holds of computed parity
+    // (the TWO_PASS rule): encode, then span.  A block's area has one slot
+    // per workgroup of the vector launch, then one per workgroup of the byte
+    // launch; the workgroups per block are those of the largest slice.
+    const size_t per_block = (size_t)e * pitch;
+    const bool vec = pitch % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
+    const long long n16 = work && vec ? (long long)(len / 16) : 0;
+    const long long rest = (long long)len - n16 * 16;  // byte columns
+    unsigned gx_vec = 0, gx_bytes = 0;
+    if (work) {
+        const long long most = (long long)parity_slice(std::min(blocks, kMaxGridBlocks), per_block);
+        gx_vec = n16 > 0 ? columns_grid_x(n16, most, 256) : 0;
+        gx_bytes = rest > 0 ? columns_grid_x(rest, most, 256) : 0;
+    }
+    const int slots = (int)(gx_vec + gx_bytes);
+    const size_t stride = (size_t)slots * kLocateSlotBytes;
+    size_t group = std::max<size_t>(1, std::min({blocks, kMaxGridBlocks, kDegTabBytes / std::max<size_t>(1, stride)}));
+    if (ctx->locate_group_max)
+        group = std::min(group, ctx->locate_group_max);
+    if (work) {
+        rc = ensure_device(ctx, ctx->locate, group * stride);
+        // the scratch of the largest group now, so that no walk below grows it
+        if (!rc)
+            rc = grow_parity_scratch(ctx, group, per_block);
+        // the matrix on the device (behind the update's tables)
+        if (!rc)
+            rc = update_tables(ctx, k, e, coef);
+        if (rc)
+            return rc;
+        RS_HIP(ctx, hipMemsetAsync(d_report, 0, blocks * sizeof(rsgpu_scrub_report), ctx->stream));
+    }
+    for (size_t g0 = 0; g0 < blocks; g0 += group) {
+        const size_t ng = std::min(group, blocks - g0);
+        LocateArgs a{};
+        a.k = k;
+        a.e = e;
+        a.u = u;
+        a.work = work ? 1 : 0;
+        a.pitch = (long long)pitch;
+        a.len = (long long)len;
+        a.blocks = (long long)ng;
+        a.slots = slots;
+        a.cand_stride = stride;
+        a.rows = d_rows + g0 * (size_t)u;
+        a.report = d_report + g0;
+        if (work) {
+            a.cand = (uint8_t*)ctx->locate.p;
+            a.coef = (const uint8_t*)ctx->d_update + kUpdTabBytes;
+            auto span = [&](size_t b0, size_t nb, const uint8_t* calc) {
+                LocateArgs c = a;
+                c.blocks = (long long)nb;
+                c.cand = a.cand + (b0 - g0) * stride;
+                c.report = d_report + b0;
+                c.calc = calc;
+                c.par = d_parity + b0 * per_block;
+                auto launch = [&](bool bytes, long long c0, long long c1) {
+                    return launch_locate_span(c, bytes, c0, c1, bytes ? gx_bytes : gx_vec, bytes ? (int)gx_vec : 0,
+                                              ctx->stream);
+                };
+                return launch_head_and_tail(ctx, kLocateNames, nb, n16, (long long)len, launch);
+            };
+            rc = two_pass(ctx, k, e, len, pitch, g0, ng, d_src, coef, nullptr, span);
+            if (rc)
+                return rc;
+        }
+        KTimer kt(ctx, "k_locate_finish", ng);
+        RS_HIP(ctx, launch_locate_finish(a, ctx->stream));
     }
     return RSGPU_OK;
 }

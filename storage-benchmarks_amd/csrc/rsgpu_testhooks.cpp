@@ -142,6 +142,17 @@ int rsgpu_internal_set_rebuild_group(rsgpu_ctx* ctx, long long blocks)
     return RSGPU_OK;
 }
 
+// Test hook (not part of include/rsgpu.h): caps the blocks of a group of
+// rsgpu_locate_blocks (0: the 64 MiB rule), so that a small call runs as
+// several groups.
+int rsgpu_internal_set_locate_group(rsgpu_ctx* ctx, long long blocks)
+{
+    if (!ctx || blocks < 0)
+        return RSGPU_ERR_ARG;
+    ctx->locate_group_max = (size_t)blocks;
+    return RSGPU_OK;
+}
+
 int rsgpu_internal_rebuild_wide_layout(rsgpu_ctx* ctx, long long* out)
 {
     if (!ctx || !out || ctx->rebuild_wide.blocks == 0)

@@ -39,7 +39,8 @@ __all__ = [
     "SCRUB_ONE_ROW", "SCRUB_DAMAGED", "REPAIR_REPORT_DTYPE", "REPAIR_MODES", "REPAIR_ONE_ROW",
     "REPAIR_COLUMNS", "REPAIR_CLEAN", "REPAIR_REPAIRED", "REPAIR_PARTIAL", "REPAIR_DAMAGED",
     "UPDATE_NONE", "UPDATE_DELTA", "LOST_NONE", "SCRUB_UNCHECKED", "SCRUB_BAD_MATRIX",
-    "SCRUB_BAD_LIST", "REBUILD_CHECK", "REBUILD_MAX_LOST", "REBUILD_KERNELS",
+    "SCRUB_BAD_LIST", "REBUILD_CHECK", "REBUILD_MAX_LOST", "REBUILD_KERNELS", "SCRUB_ROWS",
+    "LOCATE_MAX_ROWS",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -83,6 +84,10 @@ REBUILD_CHECK = 1
 # rsgpu_set_rebuild_kernel choices
 REBUILD_MAX_LOST = 32
 REBUILD_KERNELS = {"auto": 0, "lanes": 1, "threaded": 2}
+# rsgpu_locate_blocks' additional status and its longest list
+# (include/rsgpu.h); lists and reports as the degraded scrub's
+SCRUB_ROWS = 4
+LOCATE_MAX_ROWS = 8
 
 vp = C.c_void_p
 sz = C.c_size_t
@@ -135,6 +140,7 @@ _SIGS = {
                                               C.c_int, vp]),
     "rsgpu_rebuild_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp, C.c_int,
                                        vp]),
+    "rsgpu_locate_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp, vp]),
     "rsgpu_repair_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp]),
     "rsgpu_set_scrub_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_set_rebuild_kernel": (C.c_int, [vp, C.c_int]),
@@ -493,6 +499,19 @@ class Context:
                                               REBUILD_CHECK if check else 0, _ptr(d_report)),
                    "rsgpu_rebuild_blocks")
 
+    def locate_blocks(self, k, e, length, pitch, blocks, d_src, d_par, u, d_rows, d_report,
+                      coef=None) -> None:
+        """Locates up to min(u, e - 1) damaged rows per block (include/rsgpu.h
+        rsgpu_locate_blocks): d_rows is device memory of blocks x u bytes
+        (1 <= u <= LOCATE_MAX_ROWS), written in rebuild_blocks' list format
+        (rows ascending, then LOST_NONE); d_report as scrub_blocks', the
+        statuses add SCRUB_ROWS.  Needs e <= 64.  Rows are only read.
+        Enqueued on the context's stream."""
+        coef = _coef(coef)
+        self.check(lib().rsgpu_locate_blocks(self._h, k, e, length, pitch, blocks, _ptr(d_src),
+                                             _ptr(d_par), _ptr(coef), u, _ptr(d_rows), _ptr(d_report)),
+                   "rsgpu_locate_blocks")
+
     def repair_blocks(self, k, e, length, pitch, blocks, d_src, d_par, d_report, coef=None,
                       mode: str = "one_row") -> None:
         """Repair in place (include/rsgpu.h rsgpu_repair_blocks): d_src and
@@ -632,6 +651,38 @@ class GpuEncoder:
         self.ctx.rebuild_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,
                                 u, d_lost, rep, check=check)
         return self._read(rep, SCRUB_REPORT_DTYPE)
+
+    def _locate(self, u: int):
+        """(report, lists) on the device after locate_blocks, not waited for."""
+        import torch
+        rep = self._report(SCRUB_REPORT_DTYPE)
+        rows = torch.empty(max(1, self.B) * u, dtype=torch.uint8, device=self.src.device)
+        self.ctx.locate_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, u,
+                               rows, rep)
+        return rep, rows
+
+    def locate(self, u: int = LOCATE_MAX_ROWS):
+        """Locates up to min(u, e - 1) damaged rows per block (include/rsgpu.h
+        rsgpu_locate_blocks).  Returns (reports, lists): the per-block
+        reports as a structured array (SCRUB_REPORT_DTYPE; CLEAN, ONE_ROW,
+        SCRUB_ROWS or DAMAGED) and a (blocks, u) uint8 array of the located
+        rows per block, ascending and padded with LOST_NONE, as rebuild takes
+        them.  Synchronises (both are copied to the host)."""
+        rep, rows = self._locate(u)
+        reports = self._read(rep, SCRUB_REPORT_DTYPE)
+        return reports, rows.cpu().numpy()[: self.B * u].reshape(self.B, u).copy()
+
+    def heal(self, u: int = LOCATE_MAX_ROWS):
+        """locate, then rebuild (without the check) of the located rows in
+        place, the lists staying on the device and both on the stream with no
+        host decision in between; a block locate calls DAMAGED has an empty
+        list and is left as it is.  Returns (locate_reports, rebuild_reports).
+        Synchronises (the reports are copied to the host)."""
+        rep, rows = self._locate(u)
+        rep2 = self._report(SCRUB_REPORT_DTYPE)
+        self.ctx.rebuild_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,
+                                u, rows, rep2, check=False)
+        return self._read(rep, SCRUB_REPORT_DTYPE), self._read(rep2, SCRUB_REPORT_DTYPE)
 
     def repair(self, mode: str = "one_row") -> np.ndarray:
         """Scrubs this encoder's blocks and corrects their rows in place

@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""The locate's measurement (profiles/locate/README.md): rsgpu_locate_blocks
+against the TWO_PASS scrub with RSGPU_SCRUB_LOCATE on the same blocks, clean
+and with three kinds of damage, and a plain copy, at one shape, in one process
+on the same buffers.
+
+Kinds: `scrub_clean` (rsgpu_scrub_blocks, TWO_PASS, LOCATE) and `locate_clean`
+on consistent blocks; `locate_one` (one data row per block, b mod k, bad in 1 %
+of the byte columns), `locate_two` (two data rows per block bad in 1 % of the
+columns each, different columns), `locate_whole` (two whole data rows per block
+bad: every column takes the cooperative path) and `copy`, a device-to-device
+copy of (k + 4) len bytes per block, read plus written (the yardstick for
+"memory-bound").  Damage is XORed into the rows before a run and XORed out
+again after it, outside the timed part, so every kind runs on the same
+buffers.  After one untimed, checked run of each kind (the reports and lists
+must name exactly the damaged rows): `rounds` mirrored rounds, every kind twice
+per round.  A run's time is the sum of its kernels' HIP-event times from
+rsgpu_timing_read (the copy: HIP events around it).
+
+Besides the statistics per kind the summary holds locate_clean / scrub_clean
+over the mirrored pairs (same round, same half), to be read against the two
+kinds' own run-to-run spread.
+
+    python tools/locate_measure.py out.json [--k 64 --e 32 --len 1000000 --blocks 1024 --rounds 12]
+"""
+import numpy as np
+import torch
+
+import measure_lib as ml  # puts the engine's directory on the path
+import rsgpu  # noqa: E402
+
+DT = rsgpu.SCRUB_REPORT_DTYPE
+U = rsgpu.LOCATE_MAX_ROWS
+
+
+def main():
+    a = ml.shape_parser().parse_args()
+    k, e, L, B = a.k, a.e, a.len, a.blocks
+    ctx, enc = ml.setup(a)
+    ctx.set_scrub_kernel("two_pass")
+    dev, pitch = enc.src.device, enc.pitch
+    rep = ml.reports(enc)
+    lists = torch.empty(B * U, dtype=torch.uint8, device=dev)
+    vs = enc.src.view(B, k, pitch)
+    rng = np.random.default_rng(9)
+    blk = torch.arange(B, device=dev)
+    r1 = torch.arange(B, device=dev) % k
+    r2 = (r1 + 1 + torch.from_numpy(rng.integers(0, k - 1, B)).to(dev)) % k  # != r1
+    ncols = max(1, L // 100)
+    cols = rng.choice(L, min(L, 2 * ncols), replace=False)
+    c1 = torch.from_numpy(np.sort(cols[:ncols])).to(dev)
+    c2 = torch.from_numpy(np.sort(cols[ncols:])).to(dev) if len(cols) > ncols else c1
+    x1 = torch.from_numpy(rng.integers(1, 256, (B, len(c1)), dtype=np.uint8)).to(dev)
+    x2 = torch.from_numpy(rng.integers(1, 256, (B, len(c2)), dtype=np.uint8)).to(dev)
+    w1 = torch.from_numpy(rng.integers(1, 256, L, dtype=np.uint8)).to(dev)
+    w2 = torch.from_numpy(rng.integers(1, 256, L, dtype=np.uint8)).to(dev)
+
+    def sparse(rows, c, x):
+        vs[blk[:, None], rows[:, None], c[None, :]] ^= x
+
+    def whole(rows, w):
+        vs[blk, rows, :L] ^= w[None, :]
+
+    # the damage of a kind: applying it twice removes it
+    damage = {
+        "locate_one": lambda: sparse(r1, c1, x1),
+        "locate_two": lambda: (sparse(r1, c1, x1), sparse(r2, c2, x2)),
+        "locate_whole": lambda: (whole(r1, w1), whole(r2, w2)),
+    }
+    copy_bytes = (k + 4) * L * B // 2
+    copy = ml.copy_yardstick(enc, copy_bytes)
+    torch.cuda.synchronize()
+
+    def run(kind):
+        """One timed run: (ms, {kernel name: ms})."""
+        if kind == "copy":
+            return copy()
+        if kind == "scrub_clean":
+            return ml.timed(ctx, lambda: ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, rep))
+        flip = damage.get(kind)
+        if flip:
+            flip()
+            torch.cuda.synchronize()
+        try:
+            return ml.timed(ctx, lambda: ctx.locate_blocks(k, e, L, pitch, B, enc.src, enc.par, U, lists, rep))
+        finally:
+            if flip:
+                flip()
+                torch.cuda.synchronize()
+
+    kinds = ["scrub_clean", "locate_clean", "locate_one", "locate_two", "locate_whole", "copy"]
+    h1, h2 = r1.cpu().numpy(), r2.cpu().numpy()
+    lo, hi = np.minimum(h1, h2), np.maximum(h1, h2)
+    kernels_seen = {}
+    for kind in kinds:  # untimed and checked
+        rep.fill_(0xA5)
+        lists.fill_(0xA5)
+        _, by = run(kind)
+        kernels_seen[kind] = sorted(by)
+        if kind == "copy":
+            continue
+        r = rep.cpu().numpy().view(DT)
+        got = lists.cpu().numpy().reshape(B, U)
+        if kind.endswith("clean"):
+            assert ml.all_clean(rep), kind
+        elif kind == "locate_one":
+            assert (r["status"] == rsgpu.SCRUB_ONE_ROW).all() and (r["row"] == h1).all(), kind
+            assert (r["bad_columns"] == len(c1)).all() and (got[:, 0] == h1).all() and (got[:, 1:] == 255).all(), kind
+        else:
+            assert (r["status"] == rsgpu.SCRUB_ROWS).all() and (r["row"] == lo).all(), kind
+            assert (got[:, 0] == lo).all() and (got[:, 1] == hi).all() and (got[:, 2:] == 255).all(), kind
+    ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, rep)
+    torch.cuda.synchronize()
+    assert ml.all_clean(rep), "the blocks after the damage was taken out again"
+
+    out = {**ml.header(enc), "kernels": kernels_seen, "bad_columns_per_row": int(len(c1)),
+           "runs": ml.mirrored_rounds(kinds, a.rounds, run)}
+    summ = ml.summarise(out["runs"], kinds, kernel_medians=True)
+    summ["copy"]["tb_per_s"] = 2 * copy_bytes / (summ["copy"]["median"] * 1e-3) / 1e12
+    half = len(kinds)
+    at = {(r["round"], r["pos"] >= half, r["kind"]): r["ms"] for r in out["runs"]}
+    ratios = [at[(rnd, h, "locate_clean")] / at[(rnd, h, "scrub_clean")] for rnd in range(a.rounds)
+              for h in (False, True)]
+    summ["locate_clean"]["over_scrub_in_pairs"] = ml.stats(ratios)
+    for kind in kinds[1:-1]:
+        summ[kind]["over_scrub"] = summ[kind]["median"] / summ["scrub_clean"]["median"]
+    ml.finish(a.out, out, summ)
+    ctx.set_scrub_kernel("auto")
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
