@@ -645,8 +645,8 @@ int rsgpu_set_rebuild_kernel(rsgpu_ctx *ctx, int kernel);
  * ms, two rows 56.1 ms: a bad 16-byte column stops its wave's other 63 and
  * costs about 1.5 ns over the device.  Blocks damaged in most of their columns
  * are the worst case, every column taking the cooperative path: two whole
- * rows bad per block 175.6 ms, 5 x the scrub.  Not built: a filter that
- * skips blocks a previous scrub called CLEAN; a form fused into the encode;
+ * rows bad per block 175.6 ms, 5 x the scrub.  The form fused into the
+ * compiled encode is rsgpu_set_locate_kernel's FUSED, below.  Not built:
  * e > 64; u > 8; per-column decoding of blocks that end DAMAGED. */
 #define RSGPU_SCRUB_ROWS 4        /* the damage lies in exactly the 2..u listed rows */
 #define RSGPU_LOCATE_MAX_ROWS 8
@@ -654,6 +654,40 @@ int rsgpu_locate_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, 
                         const unsigned char *d_src, const unsigned char *d_parity,
                         const unsigned char *coef, int u, unsigned char *d_rows,
                         rsgpu_scrub_report *d_report);
+
+/* Kernel of rsgpu_locate_blocks (per context; every choice writes the same
+ * reports and lists):
+ *   AUTO      TWO_PASS
+ *   TWO_PASS  the encode of a slice into the context's scratch, then
+ *             k_locate_span, as described above; any geometry
+ *   FUSED     k_rs_bs_locate: the FUSED scrub's kernel (the compiled encode
+ *             programs with the stored parity read and compared in registers)
+ *             whose cold path reduces a dirty tile's syndrome columns to a
+ *             basis of at most u vectors, as k_locate_span does of its
+ *             columns, and writes it to the next free slot of the block's
+ *             candidate area; k_locate_finish then reads the slots that were
+ *             claimed.  A clean tile writes nothing, there is no parity scratch
+ *             and no encode launch: a clean block costs what the FUSED scrub
+ *             costs.  Applies where the FUSED scrub does ((16,4) (16,8) (64,32)
+ *             (64,16) (100,20) (5,4) (20,7), no `coef`, pitch % 16 == 0, 16-byte
+ *             aligned d_src and d_parity, len % 32 == 0, len < 4 GiB) and one
+ *             block's candidate area (ceil(len / 2048) slots of 528 bytes)
+ *             fits 64 MiB.  Opt-in: AUTO does not take it yet.
+ *             Measured at (64, 32), 1 MB rows, 1024 blocks on one MI355X, one
+ *             process, medians of 24 runs (profiles/locate_fused, DESIGN.md
+ *             3.9): clean blocks 21.00 ms, the FUSED scrub with
+ *             RSGPU_SCRUB_LOCATE 21.57 ms (ratio 0.882 - 0.991 over 24 mirrored
+ *             pairs: it met the scrub's time), TWO_PASS locate 35.31 ms; one
+ *             row per block bad in 1 % of the columns 24.98 ms (TWO_PASS
+ *             50.64), two rows 28.84 ms (56.45), two whole rows bad per block
+ *             133.8 ms (175.9), still the worst case.
+ * A choice that does not apply falls back to TWO_PASS.  Not built: the same
+ * cold path in the generated scrub for matrices known at run time
+ * (k_rs_jit_scrub). */
+#define RSGPU_LOCATE_AUTO 0
+#define RSGPU_LOCATE_TWO_PASS 1
+#define RSGPU_LOCATE_FUSED 2
+int rsgpu_set_locate_kernel(rsgpu_ctx *ctx, int kernel);
 
 /* ---- repair in place of what the scrub locates ---------------------------- */
 

@@ -37,7 +37,9 @@
 // with another epilogue: the stored parity read and compared in registers
 // instead of the computed one written (scrub_tile).  The repair
 // (k_rs_bs_repair) is that epilogue with the rows writable: a bad column's
-// byte is corrected where its row and error value are found.
+// byte is corrected where its row and error value are found.  The locate of
+// several rows (k_rs_bs_locate) is the scrub with another cold path: a dirty
+// tile leaves the span of its syndrome columns (span_tile).
 //
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -49,6 +51,7 @@
 #include "gf256.h"
 #include "kernel_hooks.h"
 #include "rs_kernels.h"
+#include "rs_span.h"
 
 namespace rsgpu {
 namespace bs {
@@ -250,6 +253,7 @@ __device__ __forceinline__ void consume_part(uint32_t (&acc)[NR][8], uint32_t (&
 struct ScrubArgs {
     static constexpr bool kScrub = true;
     static constexpr bool kRepair = false;  // scrub_tile only reads the rows
+    static constexpr bool kSpan = false;    // its cold path names one row per column
     static constexpr int flat = 0;
     const uint8_t* src;  // [B][K] rows
     const uint8_t* par;  // [B][E] rows, the stored parity
@@ -259,11 +263,31 @@ struct ScrubArgs {
     int locate;
 };
 
+// The locate of several rows (rsgpu_locate_blocks, k_rs_bs_locate): the
+// scrub's arguments, and where a dirty tile leaves the span of its syndrome
+// columns (rs_kernels.h launch_rs_bitsliced_locate).
+struct LocArgs {
+    static constexpr bool kScrub = true;
+    static constexpr bool kRepair = false;
+    static constexpr bool kSpan = true;  // scrub_tile's cold path is span_tile
+    static constexpr int flat = 0;
+    static constexpr int locate = 1;
+    const uint8_t* src;  // [B][K] rows
+    const uint8_t* par;  // [B][E] rows, the stored parity
+    long long pitch, len;
+    long long blocks;
+    ScrubFold* fold;     // [B], zeroed before the launch; hi1 counts the block's claimed slots
+    uint8_t* cand;       // [B] candidate areas at cand_stride, a slot per tile
+    size_t cand_stride;
+    int u;
+};
+
 // The repair (rsgpu_repair_blocks, k_rs_bs_repair): the scrub's arguments
 // with writable rows, the 24-byte fold and a mode (rs_kernels.h kRepair*).
 struct RepairArgs {
     static constexpr bool kScrub = true;
     static constexpr bool kRepair = true;  // scrub_tile corrects what it locates
+    static constexpr bool kSpan = false;
     static constexpr int flat = 0;
     static constexpr int locate = 1;
     uint8_t* src;  // [B][K] rows
@@ -277,6 +301,93 @@ struct RepairArgs {
 // log / antilog tables of the cold paths (the scrub's row location, the
 // small-batch decode's solve below)
 alignas(16) __device__ const GfTables kGfBs = make_gf_tables();
+
+// scrub_tile's cold path of the locate (LocArgs): instead of one row per bad
+// column, the span of the tile's syndrome columns (rs_span.h), as
+// k_locate_span keeps it of its columns.  The syndrome planes go back to bytes
+// and in four passes into LDS as the scrub's do, at a row stride of 520 bytes:
+// lane p of a wave reads syndrome p of one column, and at 512 every lane of a
+// half-wave would meet the same bank (520 = 130 dwords: 2 lanes per bank, the
+// 8-byte writes still aligned).  After a pass's barrier the waves divide the
+// tile lanes that have a bad column in it (`tm`, the tile's bad-byte masks:
+// bit 8 q + w is byte 4 w + q, so column j of the pass is bit 8 (j % 4) +
+// 2 pass + j / 4); each wave visits its columns one after the other, all 64
+// lanes on each, under wave-uniform control, and reduces them against its own
+// basis of at most u vectors.  After the last pass's barrier wave 0 merges the
+// NW bases and writes them to the next free slot of the block's candidate
+// area, claimed with an atomicAdd on the fold's hi1, which the locate uses for
+// nothing else: a clean tile writes nothing and claims nothing, so the first
+// hi1 slots of a block are the written ones and k_locate_finish reads no
+// other.  The order of the claims is that of the workgroups' arrival; W, the
+// span of all the block's syndrome columns, does not depend on the order in
+// which its vectors are met, so no byte of the output does.
+// LDS, in the part buffers: masks 1 KiB | syn [E][520] | GF tables 768 B | NW
+// bases of 552 B.
+constexpr int kSpanRow = 520;
+template <int E, int NW, int G, int R0, int NR>
+__device__ __forceinline__ void span_tile(const LocArgs& a, uint32_t (&acc)[NR][8], bool inb, uint32_t tm,
+                                          long long blk, int lane, uint8_t* ldsb, uint32_t m4, uint32_t m2,
+                                          uint32_t m1)
+{
+    constexpr int kGfAt = 1024 + E * kSpanRow, kBasesAt = kGfAt + (int)sizeof(GfTables);
+    static_assert(NW == 1 || NW == 2 || NW == 4, "the waves divide the tile's 64 lanes");
+    static_assert(kGfAt % 8 == 0 && sizeof(GfTables) % 8 == 0, "the bases are aligned");
+    static_assert(kBasesAt + NW * sizeof(SpanBasis) <= 2 * S * 2 * 64 * 16, "locate LDS fits the part buffers");
+    uint8_t* syn = ldsb + 1024;
+    GfTables& gf = *reinterpret_cast<GfTables*>(ldsb + kGfAt);
+    SpanBasis* sb = reinterpret_cast<SpanBasis*>(ldsb + kBasesAt);
+    SpanBasis& s = sb[G];
+    load_gf(gf, kGfBs, G * 64 + lane, 64 * NW);  // read from the first pass's barrier on
+    s.n = 0;
+    s.ovf = 0;
+#pragma unroll
+    for (int rr = 0; rr < NR; ++rr)
+        tr8(acc[rr], m4, m2, m1);  // syndrome planes -> bytes, in place
+    // tile lanes G, G + NW, ... are this wave's
+    constexpr unsigned long long kShare = NW == 1 ? ~0ull : NW == 2 ? 0x5555555555555555ull : 0x1111111111111111ull;
+    for (int pass = 0; pass < 4; ++pass) {
+        // the lane's bytes 8 pass .. 8 pass + 7 of every row (zeros from an idle
+        // lane): always the row's first two dwords, the later ones move down
+        // behind the pass (register moves; an index by `pass` would put the
+        // syndromes into scratch)
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr)
+            *reinterpret_cast<uint2*>(syn + (R0 + rr) * kSpanRow + lane * 8) =
+                inb ? make_uint2(acc[rr][0], acc[rr][1]) : make_uint2(0u, 0u);
+#pragma unroll
+        for (int rr = 0; rr < NR; ++rr)
+#pragma unroll
+            for (int q = 0; q < 6; ++q)
+                acc[rr][q] = acc[rr][q + 2];
+        __syncthreads();
+        unsigned pm = 0;  // bit j: column 8 lane + j of the pass is bad
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            pm |= ((tm >> (8 * (j & 3) + 2 * pass + (j >> 2))) & 1u) << j;
+        unsigned long long todo = __ballot(pm != 0) & (kShare << G);
+        while (todo) {
+            const int from = __ffsll(todo) - 1;
+            todo &= todo - 1;
+            unsigned m = (unsigned)__builtin_amdgcn_readlane((int)pm, from);
+            while (m) {
+                const int c = from * 8 + __ffs(m) - 1;
+                m &= m - 1;
+                const uint8_t v = lane < E ? syn[lane * kSpanRow + c] : (uint8_t)0;
+                span_append(s, gf, lane, span_reduce(s, gf, lane, v), a.u);
+            }
+        }
+        __syncthreads();  // the next pass overwrites syn; the last one: the bases are complete
+    }
+    if constexpr (G == 0) {
+        unsigned at = 0;
+        if (lane == 0)
+            at = atomicAdd(&a.fold[blk].hi1, 1u);
+        at = (unsigned)uni((int)at);
+        if (at < gridDim.x)  // a slot per tile: always, with hi1 zero before the launch
+            span_publish(s, sb, NW, gf, lane, a.u,
+                         a.cand + (size_t)blk * a.cand_stride + (size_t)at * kLocateSlotBytes);
+    }
+}
 
 // Wave G's rows [R0, R0 + NR) of one tile.  The lane's 32 bytes of each
 // stored parity row, as planes, XORed into the accumulators: the syndromes,
@@ -294,6 +405,7 @@ alignas(16) __device__ const GfTables kGfBs = make_gf_tables();
 // only non-zero syndrome.  The maxima of row + 1 and of kScrubBias - row go
 // into the block's fold (order-independent atomics, one pair per wave).
 // LDS, in the part buffers: masks [NW][64] u32 | syn = 1 + E / 2 KiB of the 32.
+// The locate (A::kSpan) leaves here, after the count, for span_tile above.
 //
 // The repair (A::kRepair) corrects in that walk: the thread at column c of
 // pass `pass` has the row and the error value x (s_0 for a source row, s_p0
@@ -370,6 +482,10 @@ __device__ __forceinline__ void scrub_tile(const A& a, uint32_t (&acc)[NR][8], b
             count = count && a.mode != kRepairGated;
         if (count)
             atomicAdd(&f->bad, (unsigned long long)n);
+    }
+    if constexpr (A::kSpan) {
+        span_tile<E, NW, G, R0, NR>(a, acc, inb, tm, blk, lane, reinterpret_cast<uint8_t*>(ldsv), m4, m2, m1);
+        return;
     }
     if (!a.locate)
         return;
@@ -620,6 +736,25 @@ hipError_t launch_scrub(const ScrubArgs& a, hipStream_t st)
 {
     dim3 grid((unsigned)((a.len + 2047) / 2048), (unsigned)a.blocks);
     hipLaunchKernelGGL((k_rs_bs_scrub<K, E, C, NW>), grid, dim3(64 * NW), 0, st, a);
+    return hipGetLastError();
+}
+
+// The locate: k_rs_bs_scrub with span_tile as the cold path of the epilogue.
+template <int K, int E, int C, int NW>
+__global__ __launch_bounds__(64 * NW, (bs_waves_per_simd<E, NW>())) void k_rs_bs_locate(LocArgs a)
+{
+    __shared__ uint4 lds[2][S * 2 * 64];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    [&]<int... Gs>(std::integer_sequence<int, Gs...>) {
+        ((wave == Gs ? run_group<K, E, C, NW, Gs, true, LocArgs>(a, lds) : void()), ...);
+    }(std::make_integer_sequence<int, NW>{});
+}
+
+template <int K, int E, int C, int NW>
+hipError_t launch_locate(const LocArgs& a, hipStream_t st)
+{
+    dim3 grid((unsigned)((a.len + 2047) / 2048), (unsigned)a.blocks);
+    hipLaunchKernelGGL((k_rs_bs_locate<K, E, C, NW>), grid, dim3(64 * NW), 0, st, a);
     return hipGetLastError();
 }
 
@@ -1043,6 +1178,25 @@ hipError_t launch_rs_bitsliced_scrub(int k, int e, const uint8_t* src, const uin
     if (k == 100 && e == 20) return bs::launch_scrub<100, 20, 20, 4>(a, st);
     if (k == 5 && e == 4) return bs::launch_scrub<5, 4, 5, 1>(a, st);
     if (k == 20 && e == 7) return bs::launch_scrub<20, 7, 20, 1>(a, st);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_rs_bitsliced_locate(int k, int e, const uint8_t* src, const uint8_t* par, long long pitch,
+                                      long long len, long long blocks, ScrubFold* fold, uint8_t* cand,
+                                      size_t cand_stride, int u, hipStream_t st)
+{
+    if (blocks <= 0 || blocks > 65535 || len <= 0 || len % 32 != 0 || len >= (1ll << 32) || pitch < len ||
+        !src || !par || !fold || !cand || u < 1 || u > kLocMax ||
+        cand_stride < (size_t)((len + 2047) / 2048) * kLocateSlotBytes)
+        return hipErrorInvalidValue;
+    const bs::LocArgs a{src, par, pitch, len, blocks, fold, cand, cand_stride, u};
+    if (k == 16 && e == 4) return bs::launch_locate<16, 4, 16, 1>(a, st);
+    if (k == 16 && e == 8) return bs::launch_locate<16, 8, 16, 1>(a, st);
+    if (k == 64 && e == 32) return bs::launch_locate<64, 32, 16, 4>(a, st);
+    if (k == 64 && e == 16) return bs::launch_locate<64, 16, 16, 2>(a, st);
+    if (k == 100 && e == 20) return bs::launch_locate<100, 20, 20, 4>(a, st);
+    if (k == 5 && e == 4) return bs::launch_locate<5, 4, 5, 1>(a, st);
+    if (k == 20 && e == 7) return bs::launch_locate<20, 7, 20, 1>(a, st);
     return hipErrorInvalidValue;
 }
 

@@ -488,6 +488,8 @@ hipError_t launch_rs_tc_counted(const TcArgs& a, long long blocks, hipStream_t s
 // block is written by exactly one workgroup of one launch before
 // k_locate_finish (one wave per block) merges them, finds the rows whose
 // column lies in the span and writes the list rows[b][u] and the report.
+// (`claimed`, the fused form below: only the first report[b].hi1 slots are
+// written, each by the workgroup that claimed it, and only they are read.)
 constexpr size_t kLocateSlotBytes = 16 + 8 * 64;
 struct LocateArgs {
     int k, e, u;
@@ -499,6 +501,7 @@ struct LocateArgs {
     uint8_t* cand;         // [B] candidate areas at cand_stride
     size_t cand_stride;
     int slots;             // per block
+    int claimed;           // non-zero: the first report[b].hi1 slots are written, no other (k_rs_bs_locate)
     uint8_t* rows;         // [B][u] (the finish)
     ::rsgpu_scrub_report* report;  // [B]
 };
@@ -508,5 +511,16 @@ struct LocateArgs {
 hipError_t launch_locate_span(const LocateArgs& a, bool bytes, long long col0, long long col1, unsigned gx, int slot0,
                               hipStream_t st);
 hipError_t launch_locate_finish(const LocateArgs& a, hipStream_t st);
+// The locate of the compiled codes fused into the encode (rs_bitsliced.hip
+// k_rs_bs_locate): k_rs_bs_scrub's accumulation and compare; a workgroup whose
+// tile has a bad column adds the count to fold[b].bad, reduces the tile's
+// syndrome columns to a basis of at most u vectors and writes it to the slot
+// it claims with an atomicAdd on fold[b].hi1 (zero before the launch): slot i
+// of block b at cand + b * cand_stride + i * kLocateSlotBytes, one per tile of
+// 2048 bytes at the most.  A clean tile writes nothing.  k_locate_finish with
+// `claimed` follows.  The scrub's conditions on the rows; 1 <= u <= 8.
+hipError_t launch_rs_bitsliced_locate(int k, int e, const uint8_t* src, const uint8_t* par, long long pitch,
+                                      long long len, long long blocks, ScrubFold* fold, uint8_t* cand,
+                                      size_t cand_stride, int u, hipStream_t st);
 
 }  // namespace rsgpu

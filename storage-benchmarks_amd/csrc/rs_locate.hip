@@ -29,6 +29,7 @@
 #include "gf256.h"
 #include "rs_kernels.h"
 #include "rs_lane.h"
+#include "rs_span.h"
 
 namespace rsgpu {
 
@@ -36,88 +37,8 @@ namespace {
 
 constexpr int kLocThreads = 256, kLocWaves = kLocThreads / 64;
 constexpr int kLocAhead = 4;  // rows (stored and computed) loaded together
-constexpr int kLocMax = RSGPU_LOCATE_MAX_ROWS;
 
 __device__ const GfTables kLocGf = make_gf_tables();
-
-// a basis in reduced echelon form: vector i is 1 at coordinate piv[i], its
-// lowest non-zero one, and every other vector is 0 there
-struct SpanBasis {
-    uint8_t v[kLocMax][64];
-    int piv[kLocMax];
-    int n, ovf;  // vectors held; a vector outside the span met a full basis
-};
-
-// what a workgroup leaves of its columns: [n, ovf, pad | n vectors of 64 bytes]
-struct SlotHdr {
-    int n, ovf, pad[2];
-};
-static_assert(sizeof(SlotHdr) + kLocMax * 64 == kLocateSlotBytes, "slot layout");
-
-__device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
-
-__device__ __forceinline__ uint8_t lane_byte(uint8_t v, int l)
-{
-    return (uint8_t)__builtin_amdgcn_readlane((int)v, l);
-}
-
-__device__ __forceinline__ uint8_t loc_mul(const GfTables& gf, uint8_t a, uint8_t b)
-{
-    return a && b ? gf.exp[gf.log[a] + gf.log[b]] : 0;
-}
-
-__device__ __forceinline__ void load_gf(GfTables& gf, int t, int threads)
-{
-    for (int i = t; i < 512; i += threads)
-        gf.exp[i] = kLocGf.exp[i];
-    for (int i = t; i < 256; i += threads)
-        gf.log[i] = kLocGf.log[i];
-}
-
-// The wave's vector v (lane = coordinate) minus its components along the
-// basis.  The basis is reduced, so every factor is read from v itself: one
-// cross-lane read and one multiply per lane and step.  Whole wave, uniform
-// control.
-__device__ __forceinline__ uint8_t span_reduce(const SpanBasis& s, const GfTables& gf, int lane, uint8_t v)
-{
-    const int n = uni(s.n);
-    uint8_t r = v;
-    for (int i = 0; i < n; ++i) {
-        const uint8_t f = lane_byte(v, uni(s.piv[i]));
-        if (f)
-            r ^= loc_mul(gf, f, s.v[i][lane]);
-    }
-    return r;
-}
-
-// r: a residual of span_reduce.  Zero: nothing.  Otherwise it is normalised at
-// its lowest non-zero coordinate, cleared out of the vectors held and appended;
-// with `cap` vectors held it raises ovf instead.  Whole wave, uniform control;
-// the values that are the same in every lane are stored by every lane.
-__device__ __forceinline__ void span_append(SpanBasis& s, const GfTables& gf, int lane, uint8_t r, int cap)
-{
-    const unsigned long long nz = __ballot(r != 0);
-    if (!nz)
-        return;
-    const int n = uni(s.n);
-    if (n >= cap) {
-        s.ovf = 1;
-        return;
-    }
-    const int pv = __ffsll(nz) - 1;
-    const uint8_t lead = lane_byte(r, pv);
-    const uint8_t w = r ? gf.exp[gf.log[r] + 255 - gf.log[lead]] : 0;
-    for (int i = 0; i < n; ++i) {
-        const uint8_t g = (uint8_t)uni(s.v[i][pv]);
-        if (g)
-            s.v[i][lane] ^= loc_mul(gf, g, w);
-    }
-    s.v[n][lane] = w;
-    s.piv[n] = pv;
-    s.n = n + 1;
-    // what a lane wrote is read by the other lanes of the wave from here on
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
 
 // W: dwords per lane and row.  Columns [col0, col1) in units of 16 bytes (W =
 // 4) or bytes (W = 1).  Workgroup x of block b writes slot slot0 + x.
@@ -130,7 +51,7 @@ __global__ __launch_bounds__(kLocThreads) void k_locate_span(LocateArgs a, long 
     const long long b = blockIdx.y;
     const int e = a.e;
 
-    load_gf(gf, threadIdx.x, kLocThreads);
+    load_gf(gf, kLocGf, threadIdx.x, kLocThreads);
     sb[wave].n = 0;
     sb[wave].ovf = 0;
     __syncthreads();
@@ -203,6 +124,8 @@ __global__ __launch_bounds__(kLocThreads) void k_locate_span(LocateArgs a, long 
     }
     __syncthreads();
     if (wave == 0) {
+        // (rs_span.h span_publish, written out: through the call the compiler
+        // lays this kernel's blocks out differently)
         for (int w = 1; w < kLocWaves; ++w) {
             const int nw = uni(sb[w].n);
             if (uni(sb[w].ovf))
@@ -240,7 +163,7 @@ __global__ __launch_bounds__(64) void k_locate_finish(LocateArgs a)
     const long long b = blockIdx.x;
     const int k = a.k, e = a.e;
 
-    load_gf(gf, lane, 64);
+    load_gf(gf, kLocGf, lane, 64);
     wb.n = wb.ovf = 0;
     hb.n = hb.ovf = 0;
     __syncthreads();
@@ -250,10 +173,15 @@ __global__ __launch_bounds__(64) void k_locate_finish(LocateArgs a)
     if (bad) {
         status = RSGPU_SCRUB_DAMAGED;
         const uint8_t* cand = a.cand + (size_t)b * a.cand_stride;
+        // claimed (k_rs_bs_locate): only the block's dirty tiles wrote a slot, each
+        // the next free one; their count stands where the status will
+        int slots = a.slots;
+        if (a.claimed)
+            slots = min((int)reinterpret_cast<const ScrubFold*>(a.report)[b].hi1, slots);
         // 64 slot headers at a time; most slots of a lightly damaged block are empty
-        for (int s0 = 0; s0 < a.slots; s0 += 64) {
+        for (int s0 = 0; s0 < slots; s0 += 64) {
             int n_l = 0, o_l = 0;
-            if (s0 + lane < a.slots) {
+            if (s0 + lane < slots) {
                 const SlotHdr* hdr = reinterpret_cast<const SlotHdr*>(cand + (size_t)(s0 + lane) * kLocateSlotBytes);
                 n_l = hdr->n < kLocMax ? hdr->n : kLocMax;
                 o_l = hdr->ovf;

@@ -1,0 +1,124 @@
+// rs_span.h -- the wave-cooperative span arithmetic of the locate
+// (rsgpu_locate_blocks): an echelon basis of at most RSGPU_LOCATE_MAX_ROWS
+// vectors of GF(2^8)^64 in LDS, a lane per coordinate.  Shared by
+// rs_locate.hip (k_locate_span, k_locate_finish) and rs_bitsliced.hip
+// (k_rs_bs_locate): one copy of the basis, the slot format, the reduction and
+// the append.  The merge of a workgroup's bases into its slot (span_publish) is
+// k_rs_bs_locate's; k_locate_span has the same steps written out, which keeps
+// its instructions what they were.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/rsgpu.h"
+#include "gf256.h"
+#include "rs_kernels.h"
+
+namespace rsgpu {
+
+constexpr int kLocMax = RSGPU_LOCATE_MAX_ROWS;
+
+// a basis in reduced echelon form: vector i is 1 at coordinate piv[i], its
+// lowest non-zero one, and every other vector is 0 there
+struct SpanBasis {
+    uint8_t v[kLocMax][64];
+    int piv[kLocMax];
+    int n, ovf;  // vectors held; a vector outside the span met a full basis
+};
+
+// what a workgroup leaves of its columns: [n, ovf, pad | n vectors of 64 bytes]
+struct SlotHdr {
+    int n, ovf, pad[2];
+};
+static_assert(sizeof(SlotHdr) + kLocMax * 64 == kLocateSlotBytes, "slot layout");
+
+__device__ __forceinline__ int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
+
+__device__ __forceinline__ uint8_t lane_byte(uint8_t v, int l)
+{
+    return (uint8_t)__builtin_amdgcn_readlane((int)v, l);
+}
+
+__device__ __forceinline__ uint8_t loc_mul(const GfTables& gf, uint8_t a, uint8_t b)
+{
+    return a && b ? gf.exp[gf.log[a] + gf.log[b]] : 0;
+}
+
+// the tables `from` (device memory) into the workgroup's LDS copy
+__device__ __forceinline__ void load_gf(GfTables& gf, const GfTables& from, int t, int threads)
+{
+    for (int i = t; i < 512; i += threads)
+        gf.exp[i] = from.exp[i];
+    for (int i = t; i < 256; i += threads)
+        gf.log[i] = from.log[i];
+}
+
+// The wave's vector v (lane = coordinate) minus its components along the
+// basis.  The basis is reduced, so every factor is read from v itself: one
+// cross-lane read and one multiply per lane and step.  Whole wave, uniform
+// control.
+__device__ __forceinline__ uint8_t span_reduce(const SpanBasis& s, const GfTables& gf, int lane, uint8_t v)
+{
+    const int n = uni(s.n);
+    uint8_t r = v;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t f = lane_byte(v, uni(s.piv[i]));
+        if (f)
+            r ^= loc_mul(gf, f, s.v[i][lane]);
+    }
+    return r;
+}
+
+// r: a residual of span_reduce.  Zero: nothing.  Otherwise it is normalised at
+// its lowest non-zero coordinate, cleared out of the vectors held and appended;
+// with `cap` vectors held it raises ovf instead.  Whole wave, uniform control;
+// the values that are the same in every lane are stored by every lane.
+__device__ __forceinline__ void span_append(SpanBasis& s, const GfTables& gf, int lane, uint8_t r, int cap)
+{
+    const unsigned long long nz = __ballot(r != 0);
+    if (!nz)
+        return;
+    const int n = uni(s.n);
+    if (n >= cap) {
+        s.ovf = 1;
+        return;
+    }
+    const int pv = __ffsll(nz) - 1;
+    const uint8_t lead = lane_byte(r, pv);
+    const uint8_t w = r ? gf.exp[gf.log[r] + 255 - gf.log[lead]] : 0;
+    for (int i = 0; i < n; ++i) {
+        const uint8_t g = (uint8_t)uni(s.v[i][pv]);
+        if (g)
+            s.v[i][lane] ^= loc_mul(gf, g, w);
+    }
+    s.v[n][lane] = w;
+    s.piv[n] = pv;
+    s.n = n + 1;
+    // what a lane wrote is read by the other lanes of the wave from here on
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+}
+
+// Wave 0 of a workgroup, after the barrier behind the last append: the bases
+// sb[1 .. nw) merged into its own, s = sb[0] (ovf is sticky), and s written to
+// `slot` of a candidate area.
+__device__ __forceinline__ void span_publish(SpanBasis& s, const SpanBasis* sb, int nw, const GfTables& gf, int lane,
+                                             int cap, uint8_t* slot)
+{
+    for (int w = 1; w < nw; ++w) {
+        const int n = uni(sb[w].n);
+        if (uni(sb[w].ovf))
+            s.ovf = 1;
+        for (int i = 0; i < n; ++i)
+            span_append(s, gf, lane, span_reduce(s, gf, lane, sb[w].v[i][lane]), cap);
+    }
+    const int n = uni(s.n);
+    if (lane == 0) {
+        SlotHdr* hdr = reinterpret_cast<SlotHdr*>(slot);
+        hdr->n = n;
+        hdr->ovf = s.ovf;
+    }
+    for (int i = 0; i < n; ++i)
+        slot[sizeof(SlotHdr) + i * 64 + lane] = s.v[i][lane];
+}
+
+}  // namespace rsgpu

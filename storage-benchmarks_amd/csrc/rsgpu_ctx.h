@@ -107,9 +107,11 @@ struct rsgpu_ctx {
     // (0: the 64 MiB rule), and stop after the wide prepare
     size_t rebuild_group_max = 0;
     bool rebuild_prepare_only = false;
-    // locate (rsgpu_locate_blocks): the candidate areas k_locate_span writes
-    // for one group of blocks, and the test hook that caps a group's blocks
-    // (0: the 64 MiB rule)
+    // locate (rsgpu_locate_blocks): its kernel choice (rsgpu_set_locate_kernel),
+    // the candidate areas k_locate_span or k_rs_bs_locate writes for one group
+    // of blocks, and the test hook that caps a group's blocks (0: the 64 MiB
+    // rule)
+    int locate_kernel = RSGPU_LOCATE_AUTO;
     DevBuf locate;
     size_t locate_group_max = 0;
     // pinned host staging for small uploads, guarded by an event

@@ -69,12 +69,20 @@ int locator(rsgpu_ctx* ctx, int k, int e, const unsigned char* coef, const char*
     return RSGPU_OK;
 }
 
+// the rows the fused kernels of the compiled codes take
+bool fused_rows(int k, int e, size_t len, size_t pitch, const void* d_src, const void* d_parity,
+                const unsigned char* coef)
+{
+    return !coef && rs_bitsliced_available(k, e) && len % 32 == 0 && len < (1ull << 32) && pitch % 16 == 0 &&
+           (uintptr_t)d_src % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
+}
+
 // the fused kernels of the compiled codes (k_rs_bs_scrub, k_rs_bs_repair) serve
 bool fused_eligible(const rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, const void* d_src,
                     const void* d_parity, const unsigned char* coef)
 {
-    return (ctx->scrub_kernel == RSGPU_SCRUB_AUTO || ctx->scrub_kernel == RSGPU_SCRUB_FUSED) && !coef && rs_bitsliced_available(k, e) && len % 32 == 0 &&
-           len < (1ull << 32) && pitch % 16 == 0 && (uintptr_t)d_src % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
+    return (ctx->scrub_kernel == RSGPU_SCRUB_AUTO || ctx->scrub_kernel == RSGPU_SCRUB_FUSED) &&
+           fused_rows(k, e, len, pitch, d_src, d_parity, coef);
 }
 
 // Two-pass scratch (ctx->scrub): [rowtab 256 B | matrix e x k | pad to
@@ -393,6 +401,14 @@ int rsgpu_set_rebuild_kernel(rsgpu_ctx* ctx, int kernel)
     if (!ctx || kernel < RSGPU_REBUILD_AUTO || kernel > RSGPU_REBUILD_THREADED)
         return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_rebuild_kernel: unknown kernel");
     ctx->rebuild_kernel = kernel;
+    return RSGPU_OK;
+}
+
+int rsgpu_set_locate_kernel(rsgpu_ctx* ctx, int kernel)
+{
+    if (!ctx || kernel < RSGPU_LOCATE_AUTO || kernel > RSGPU_LOCATE_FUSED)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_locate_kernel: unknown kernel");
+    ctx->locate_kernel = kernel;
     return RSGPU_OK;
 }
 
@@ -799,17 +815,24 @@ int rsgpu_locate_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
     // (the TWO_PASS rule): encode, then span.  A block's area has one slot
     // per workgroup of the vector launch, then one per workgroup of the byte
     // launch; the workgroups per block are those of the largest slice.
+    // FUSED (rsgpu.h): per group one k_rs_bs_locate, which reads the rows as
+    // the FUSED scrub does and leaves a slot per dirty tile, the block's area
+    // holding one per tile; no scratch, no encode.
     const size_t per_block = (size_t)e * pitch;
+    const size_t tiles = (len + 2047) / 2048;
+    const bool fused = work && ctx->locate_kernel == RSGPU_LOCATE_FUSED &&
+                       fused_rows(k, e, len, pitch, d_src, d_parity, coef) &&
+                       tiles * kLocateSlotBytes <= kDegTabBytes;
     const bool vec = pitch % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
     const long long n16 = work && vec ? (long long)(len / 16) : 0;
     const long long rest = (long long)len - n16 * 16;  // byte columns
     unsigned gx_vec = 0, gx_bytes = 0;
-    if (work) {
+    if (work && !fused) {
         const long long most = (long long)parity_slice(std::min(blocks, kMaxGridBlocks), per_block);
         gx_vec = n16 > 0 ? columns_grid_x(n16, most, 256) : 0;
         gx_bytes = rest > 0 ? columns_grid_x(rest, most, 256) : 0;
     }
-    const int slots = (int)(gx_vec + gx_bytes);
+    const int slots = fused ? (int)tiles : (int)(gx_vec + gx_bytes);
     const size_t stride = (size_t)slots * kLocateSlotBytes;
     size_t group = std::max<size_t>(1, std::min({blocks, kMaxGridBlocks, kDegTabBytes / std::max<size_t>(1, stride)}));
     if (ctx->locate_group_max)
@@ -817,7 +840,7 @@ int rsgpu_locate_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
     if (work) {
         rc = ensure_device(ctx, ctx->locate, group * stride);
         // the scratch of the largest group now, so that no walk below grows it
-        if (!rc)
+        if (!rc && !fused)
             rc = grow_parity_scratch(ctx, group, per_block);
         // the matrix on the device (behind the update's tables)
         if (!rc)
@@ -856,9 +879,19 @@ int rsgpu_locate_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
                 };
                 return launch_head_and_tail(ctx, kLocateNames, nb, n16, (long long)len, launch);
             };
-            rc = two_pass(ctx, k, e, len, pitch, g0, ng, d_src, coef, nullptr, span);
-            if (rc)
-                return rc;
+            if (fused) {
+                // the claims are counted in the reports' status field, zero since the memset
+                a.claimed = 1;
+                KTimer kt(ctx, "k_rs_bs_locate", ng);
+                RS_HIP(ctx, launch_rs_bitsliced_locate(k, e, d_src + g0 * (size_t)k * pitch,
+                                                       d_parity + g0 * per_block, (long long)pitch, (long long)len,
+                                                       (long long)ng, reinterpret_cast<ScrubFold*>(d_report + g0),
+                                                       a.cand, stride, u, ctx->stream));
+            } else {
+                rc = two_pass(ctx, k, e, len, pitch, g0, ng, d_src, coef, nullptr, span);
+                if (rc)
+                    return rc;
+            }
         }
         KTimer kt(ctx, "k_locate_finish", ng);
         RS_HIP(ctx, launch_locate_finish(a, ctx->stream));

@@ -40,7 +40,7 @@ __all__ = [
     "REPAIR_COLUMNS", "REPAIR_CLEAN", "REPAIR_REPAIRED", "REPAIR_PARTIAL", "REPAIR_DAMAGED",
     "UPDATE_NONE", "UPDATE_DELTA", "LOST_NONE", "SCRUB_UNCHECKED", "SCRUB_BAD_MATRIX",
     "SCRUB_BAD_LIST", "REBUILD_CHECK", "REBUILD_MAX_LOST", "REBUILD_KERNELS", "SCRUB_ROWS",
-    "LOCATE_MAX_ROWS",
+    "LOCATE_MAX_ROWS", "LOCATE_KERNELS",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -88,6 +88,8 @@ REBUILD_KERNELS = {"auto": 0, "lanes": 1, "threaded": 2}
 # (include/rsgpu.h); lists and reports as the degraded scrub's
 SCRUB_ROWS = 4
 LOCATE_MAX_ROWS = 8
+# rsgpu_set_locate_kernel choices
+LOCATE_KERNELS = {"auto": 0, "two_pass": 1, "fused": 2}
 
 vp = C.c_void_p
 sz = C.c_size_t
@@ -144,6 +146,7 @@ _SIGS = {
     "rsgpu_repair_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp]),
     "rsgpu_set_scrub_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_set_rebuild_kernel": (C.c_int, [vp, C.c_int]),
+    "rsgpu_set_locate_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_update_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, C.c_int, vp, vp, vp, vp, vp,
                                       C.c_int, vp]),
     "rsgpu_host_alloc": (C.c_int, [vp, C.POINTER(vp), sz]),
@@ -457,6 +460,15 @@ class Context:
         rsgpu_set_rebuild_kernel); every choice writes the same bytes."""
         self.check(lib().rsgpu_set_rebuild_kernel(self._h, REBUILD_KERNELS[kernel]),
                    "rsgpu_set_rebuild_kernel")
+
+    def set_locate_kernel(self, kernel: str) -> None:
+        """Kernel of locate_blocks (and of GpuEncoder.locate and heal): auto |
+        two_pass | fused (include/rsgpu.h rsgpu_set_locate_kernel); every
+        choice writes the same reports and lists.  fused: the compiled codes'
+        fused scrub with the span of a dirty tile's syndromes as its cold
+        path; opt-in, auto runs two_pass."""
+        self.check(lib().rsgpu_set_locate_kernel(self._h, LOCATE_KERNELS[kernel]),
+                   "rsgpu_set_locate_kernel")
 
     def scrub_blocks(self, k, e, length, pitch, blocks, d_src, d_par, d_report, coef=None,
                      locate: bool = True) -> None:

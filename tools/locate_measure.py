@@ -21,7 +21,16 @@ Besides the statistics per kind the summary holds locate_clean / scrub_clean
 over the mirrored pairs (same round, same half), to be read against the two
 kinds' own run-to-run spread.
 
+With --kernel fused (profiles/locate_fused/README.md; two_pass is the default
+and measures what is described above) the same process measures both forms:
+`fused_scrub_clean` (rsgpu_scrub_blocks, FUSED, LOCATE) and `fused_locate_clean`,
+`fused_locate_one`, `fused_locate_two`, `fused_locate_whole` (rsgpu_set_locate_kernel
+FUSED), then the four TWO_PASS locate kinds on the same damage, then the copy.
+The summary then holds fused_locate_clean / fused_scrub_clean over the mirrored
+pairs and every fused locate kind over its TWO_PASS twin.
+
     python tools/locate_measure.py out.json [--k 64 --e 32 --len 1000000 --blocks 1024 --rounds 12]
+                                            [--kernel {two_pass,fused}]
 """
 import numpy as np
 import torch
@@ -34,7 +43,10 @@ U = rsgpu.LOCATE_MAX_ROWS
 
 
 def main():
-    a = ml.shape_parser().parse_args()
+    ap = ml.shape_parser()
+    ap.add_argument("--kernel", choices=["two_pass", "fused"], default="two_pass")
+    a = ap.parse_args()
+    both = a.kernel == "fused"
     k, e, L, B = a.k, a.e, a.len, a.blocks
     ctx, enc = ml.setup(a)
     ctx.set_scrub_kernel("two_pass")
@@ -75,8 +87,12 @@ def main():
         """One timed run: (ms, {kernel name: ms})."""
         if kind == "copy":
             return copy()
+        form = "fused" if kind.startswith("fused_") else "two_pass"
+        kind = kind.removeprefix("fused_")
         if kind == "scrub_clean":
+            ctx.set_scrub_kernel(form)
             return ml.timed(ctx, lambda: ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, rep))
+        ctx.set_locate_kernel(form)
         flip = damage.get(kind)
         if flip:
             flip()
@@ -88,7 +104,11 @@ def main():
                 flip()
                 torch.cuda.synchronize()
 
-    kinds = ["scrub_clean", "locate_clean", "locate_one", "locate_two", "locate_whole", "copy"]
+    locates = ["locate_clean", "locate_one", "locate_two", "locate_whole"]
+    if both:
+        kinds = ["fused_scrub_clean", *("fused_" + n for n in locates), *locates, "copy"]
+    else:
+        kinds = ["scrub_clean", *locates, "copy"]
     h1, h2 = r1.cpu().numpy(), r2.cpu().numpy()
     lo, hi = np.minimum(h1, h2), np.maximum(h1, h2)
     kernels_seen = {}
@@ -99,6 +119,9 @@ def main():
         kernels_seen[kind] = sorted(by)
         if kind == "copy":
             continue
+        if kind.startswith("fused_"):  # no silent fall-back to TWO_PASS
+            assert ("k_rs_bs_scrub" if "scrub" in kind else "k_rs_bs_locate") in by, (kind, sorted(by))
+            kind = kind.removeprefix("fused_")
         r = rep.cpu().numpy().view(DT)
         got = lists.cpu().numpy().reshape(B, U)
         if kind.endswith("clean"):
@@ -109,6 +132,7 @@ def main():
         else:
             assert (r["status"] == rsgpu.SCRUB_ROWS).all() and (r["row"] == lo).all(), kind
             assert (got[:, 0] == lo).all() and (got[:, 1] == hi).all() and (got[:, 2:] == 255).all(), kind
+    ctx.set_scrub_kernel("two_pass")
     ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, rep)
     torch.cuda.synchronize()
     assert ml.all_clean(rep), "the blocks after the damage was taken out again"
@@ -119,13 +143,17 @@ def main():
     summ["copy"]["tb_per_s"] = 2 * copy_bytes / (summ["copy"]["median"] * 1e-3) / 1e12
     half = len(kinds)
     at = {(r["round"], r["pos"] >= half, r["kind"]): r["ms"] for r in out["runs"]}
-    ratios = [at[(rnd, h, "locate_clean")] / at[(rnd, h, "scrub_clean")] for rnd in range(a.rounds)
+    pre = "fused_" if both else ""
+    ratios = [at[(rnd, h, pre + "locate_clean")] / at[(rnd, h, pre + "scrub_clean")] for rnd in range(a.rounds)
               for h in (False, True)]
-    summ["locate_clean"]["over_scrub_in_pairs"] = ml.stats(ratios)
+    summ[pre + "locate_clean"]["over_scrub_in_pairs"] = ml.stats(ratios)
     for kind in kinds[1:-1]:
-        summ[kind]["over_scrub"] = summ[kind]["median"] / summ["scrub_clean"]["median"]
+        summ[kind]["over_scrub"] = summ[kind]["median"] / summ[pre + "scrub_clean"]["median"]
+    for kind in locates if both else []:
+        summ["fused_" + kind]["over_two_pass"] = summ["fused_" + kind]["median"] / summ[kind]["median"]
     ml.finish(a.out, out, summ)
     ctx.set_scrub_kernel("auto")
+    ctx.set_locate_kernel("auto")
     ctx.close()
 
 
