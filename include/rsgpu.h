@@ -338,7 +338,9 @@ int rsgpu_scrub_locatable(int k, int e, const unsigned char *coef);
  *             memory pool; no parity scratch, a clean tile writes nothing.
  *             Opt-in: AUTO never takes it.  rsgpu_repair_blocks and
  *             rsgpu_scrub_degraded_blocks do not use it: under GENERATED the
- *             repair runs its TWO_PASS form.
+ *             repair runs its TWO_PASS form.  rsgpu_locate_blocks does, under
+ *             rsgpu_set_locate_kernel's FUSED (below): the two settings
+ *             together select the generated locate.
  *             Measured on an MI355X, 1 MB rows, 1.5 GB of rows per call, clean
  *             data, kernel times, medians of 24 runs: (10,4) 0.37 ms against
  *             0.49 ms TWO_PASS (gf_gen_rs_matrix and Cauchy alike), (6,3) 0.40
@@ -646,7 +648,7 @@ int rsgpu_set_rebuild_kernel(rsgpu_ctx *ctx, int kernel);
  * costs about 1.5 ns over the device.  Blocks damaged in most of their columns
  * are the worst case, every column taking the cooperative path: two whole
  * rows bad per block 175.6 ms, 5 x the scrub.  The form fused into the
- * compiled encode is rsgpu_set_locate_kernel's FUSED, below.  Not built:
+ * encode, compiled or generated, is rsgpu_set_locate_kernel's FUSED, below.  Not built:
  * e > 64; u > 8; per-column decoding of blocks that end DAMAGED. */
 #define RSGPU_SCRUB_ROWS 4        /* the damage lies in exactly the 2..u listed rows */
 #define RSGPU_LOCATE_MAX_ROWS 8
@@ -660,7 +662,9 @@ int rsgpu_locate_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, 
  *   AUTO      TWO_PASS
  *   TWO_PASS  the encode of a slice into the context's scratch, then
  *             k_locate_span, as described above; any geometry
- *   FUSED     k_rs_bs_locate: the FUSED scrub's kernel (the compiled encode
+ *   FUSED     fused into the encode program of the call's matrix.  Where the
+ *             compiled form applies it runs, and takes precedence:
+ *             k_rs_bs_locate, the FUSED scrub's kernel (the compiled encode
  *             programs with the stored parity read and compared in registers)
  *             whose cold path reduces a dirty tile's syndrome columns to a
  *             basis of at most u vectors, as k_locate_span does of its
@@ -681,9 +685,41 @@ int rsgpu_locate_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, 
  *             row per block bad in 1 % of the columns 24.98 ms (TWO_PASS
  *             50.64), two rows 28.84 ms (56.45), two whole rows bad per block
  *             133.8 ms (175.9), still the worst case.
- * A choice that does not apply falls back to TWO_PASS.  Not built: the same
- * cold path in the generated scrub for matrices known at run time
- * (k_rs_jit_scrub). */
+ *             Otherwise, when the context's scrub kernel is
+ *             RSGPU_SCRUB_GENERATED (rsgpu_set_scrub_kernel: the family's
+ *             opt-in to generated programs), the generated form:
+ *             k_rs_jit_locate / k_rs_jitw_locate, the GENERATED scrub's kernels
+ *             on the matrix's shared program (the one the GENERATED encode and
+ *             scrub of that matrix run; built on first use, cached per
+ *             context) with the same cold path, one claimed slot per dirty
+ *             workgroup, and the same k_locate_finish.  Any matrix, with or
+ *             without `coef`; 1 <= e <= 64, pitch % 16 == 0, 16-byte aligned
+ *             d_src and d_parity, len % 32 == 0, len < 4 GiB, a device with an
+ *             executable memory pool, and one block's candidate area within
+ *             64 MiB.  No parity scratch, no encode launch, and the scrub's
+ *             locate tables are not uploaded.
+ *             Measured at 1 MB rows, about 1.5 GB of rows per call, one
+ *             MI355X, one process, medians of 24 runs (profiles/locate_generated,
+ *             DESIGN.md 3.9; generated locate / TWO_PASS locate, ms):
+ *                                        (10,4) Cauchy  (6,3) Cauchy   (14,32)
+ *               clean                    0.378 / 0.510  0.414 / 0.545  0.298 / 0.881
+ *               one row bad in 1 %       1.59 / 1.19    1.96 / 1.25    1.51 / 1.56
+ *               two rows bad in 1 % each 2.50 / 1.53    3.20 / 1.73    1.68 / 1.92
+ *               two whole rows bad       47.0 / 8.3     72.2 / 13.6    6.19 / 5.91
+ *             Clean blocks cost what the GENERATED scrub with
+ *             RSGPU_SCRUB_LOCATE costs in the same process (0.374, 0.409, 0.295
+ *             ms; ratio over 24 mirrored pairs 1.005, 1.009, 1.018, stdev 0.010
+ *             - 0.019, inside the pair's run-to-run spread), 0.74, 0.76 and
+ *             0.34 of TWO_PASS.  On damaged blocks the generated form LOSES to
+ *             TWO_PASS wherever e is small: every dirty workgroup runs the
+ *             GENERATED scrub's cold path, eight passes that load the stored
+ *             rows again dword by dword, each load waited for, on one or two
+ *             waves, before its columns are reduced.  Advice: take the
+ *             combination for scrubbing, where nearly every block is clean;
+ *             a caller who expects damage in most blocks of a call with e <=
+ *             16 is served better by TWO_PASS (at (14,32) the two forms are
+ *             within 13 % of each other on every damaged kind).
+ * A choice that does not apply falls back to TWO_PASS, silently. */
 #define RSGPU_LOCATE_AUTO 0
 #define RSGPU_LOCATE_TWO_PASS 1
 #define RSGPU_LOCATE_FUSED 2

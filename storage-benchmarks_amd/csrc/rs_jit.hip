@@ -31,6 +31,7 @@
 #include "rs_jit.h"
 #include "rs_kernels.h"
 #include "rs_lane.h"
+#include "rs_span.h"
 #include "tc_handlers.inc"
 
 namespace rsgpu {
@@ -156,13 +157,59 @@ alignas(16) __device__ const GfTables kGfJit = make_gf_tables();
 constexpr int kScrubMaskBytes = 2048;  // >= 4 NV TPW 64: at most 6 waves
 
 struct JitScrub {
+    static constexpr bool kSpan = false;  // the cold path names one row per column
     ScrubFold* fold;
     const uint8_t* tab;
     int locate;
 };
 
-template <class SL, int NV, int TPW>
-__device__ __forceinline__ void scrub_slots(const JitScrub& s, int k, int e, uint8_t* const* dsts, int b, int r0,
+// The locate of several rows (rsgpu_locate_blocks under FUSED + GENERATED;
+// k_rs_jit_locate, k_rs_jitw_locate): the same epilogue with the cold path of
+// span_tile (rs_bitsliced.hip) for a matrix known at run time.  The eight
+// passes lay the syndromes into LDS as above, at a row stride of kLocRow = 260
+// bytes: lane p of a wave reads syndrome p of one column, byte p kLocRow + c.
+// A byte or dword read is served in two groups of 32 lanes over 32 banks of 4
+// bytes; at 256 bytes = 64 dwords every lane of a group would meet the same
+// bank, a 32-way conflict.  260 = 65 dwords puts lane p on bank (p + c / 4)
+// mod 32, every lane of a group on its own, and keeps the passes' dword writes
+// (consecutive dwords of a row, no conflict either) aligned.  After a pass's
+// barrier the NV waves of a tile divide the tile lanes that have a bad byte in
+// it (`tm`, the tile's masks: bit 8 q + w is byte 4 w + q, so pass p owns bits
+// 8 q + p and column 4 lane + q of the pass); each wave visits its columns one after the other, all
+// 64 lanes on each, under wave-uniform control, and reduces them against its
+// own basis of at most u vectors (rs_span.h).  After the last pass's barrier
+// wave 0 of the workgroup merges the NV TPW bases -- every tile the workgroup
+// owns; an idle tile past the row end has an empty one -- and writes them to
+// the next free slot of the block's candidate area, claimed with an atomicAdd
+// on the fold's hi1, which the locate uses for nothing else.  A block has a
+// slot per 2048-byte tile and a workgroup covers at least one tile, so the
+// claim is always below `slots`.  The order of the claims is that of the
+// workgroups' arrival; W, the span of all the block's syndrome columns, does
+// not depend on the order in which its vectors are met, and k_locate_finish
+// derives every byte of its output from W and the count.
+// LDS, in the chunk buffers: masks 2 KiB | syn [TPW][N NV][260] | GF tables
+// 768 B | NV TPW bases of 552 B (LocLds; N NV: the most rows the layout takes).
+struct JitLocate {
+    static constexpr bool kSpan = true;  // the cold path keeps the span of the columns
+    static constexpr int locate = 1;
+    ScrubFold* fold;  // hi1 counts the block's claimed slots
+    uint8_t* cand;
+    size_t cand_stride;
+    int slots, u;
+};
+
+constexpr int kLocRow = 260;
+template <int N, int NV, int TPW>
+struct LocLds {
+    static constexpr int kGfAt = kScrubMaskBytes + TPW * N * NV * kLocRow;
+    static constexpr int kBasesAt = kGfAt + (int)sizeof(GfTables);
+    static constexpr int kBytes = kBasesAt + NV * TPW * (int)sizeof(SpanBasis);
+    static_assert(kLocRow % 4 == 0 && kGfAt % 8 == 0 && sizeof(GfTables) % 8 == 0, "dword writes, aligned bases");
+    static_assert(NV == 1 || NV == 2 || NV == 4, "the waves divide the tile's 64 lanes");
+};
+
+template <class SL, int NV, int TPW, class S>
+__device__ __forceinline__ void scrub_slots(const S& s, int k, int e, uint8_t* const* dsts, int b, int r0,
                                             int nrow, int wave, int tw, bool inb, uint32_t po, uint8_t* ldsb,
                                             uint32_t m4, uint32_t m2, uint32_t m1)
 {
@@ -231,12 +278,23 @@ __device__ __forceinline__ void scrub_slots(const JitScrub& s, int k, int e, uin
     // is no hard limit below 64 registers
     typedef __attribute__((address_space(3))) uint8_t lds_u8;
     typedef __attribute__((address_space(3))) uint32_t lds_u32;
-    lds_u8* syn = (lds_u8*)ldsb + kScrubMaskBytes + tw * e * 256;
-    unsigned hi1 = 0, lo1 = 0;
+    constexpr int kRow = S::kSpan ? kLocRow : 256;
+    lds_u8* syn = (lds_u8*)ldsb + kScrubMaskBytes + tw * e * kRow;
+    [[maybe_unused]] unsigned hi1 = 0, lo1 = 0;
+    using Lay = LocLds<SL::N, NV, TPW>;
+    [[maybe_unused]] GfTables& gf = *reinterpret_cast<GfTables*>(ldsb + Lay::kGfAt);
+    [[maybe_unused]] SpanBasis* sb = reinterpret_cast<SpanBasis*>(ldsb + Lay::kBasesAt);
+    if constexpr (S::kSpan) {
+        // read from the first pass's barrier on; the chunk buffers are free
+        // since the barrier before the masks
+        load_gf_rolled(gf, kGfJit, (tw * NV + wave) * 64 + lane, 64 * NV * TPW);
+        sb[tw * NV + wave].n = 0;
+        sb[tw * NV + wave].ovf = 0;
+    }
 #pragma unroll 1
     for (int pass = 0; pass < 8; ++pass) {
         // bytes 4 pass .. 4 pass + 3 of the lane's 32 of every row (zeros from an idle lane)
-        lds_u32* mine4 = (lds_u32*)(syn + r0 * 256 + lane * 4);
+        lds_u32* mine4 = (lds_u32*)(syn + r0 * kRow + lane * 4);
         const uint32_t po4 = po + 4 * pass;
         [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
             (
@@ -258,30 +316,67 @@ __device__ __forceinline__ void scrub_slots(const JitScrub& s, int k, int e, uin
 #pragma unroll
                         for (int q = 1; q < 8; ++q)
                             d = pass == q ? W[q] : d;
-                        mine4[Ss * 64] = inb ? d ^ st : 0u;
+                        mine4[Ss * (kRow / 4)] = inb ? d ^ st : 0u;
                         __builtin_amdgcn_sched_barrier(0);  // slot by slot
                     }
                 }(),
                 ...);
         }(std::make_integer_sequence<int, SL::N>{});
         __syncthreads();
-        for (int c = wave * 64 + lane; c < 256; c += 64 * NV) {
-            int nz = 0, p0 = 0;
-#pragma unroll 1
-            for (int p = 0; p < e; ++p) {
-                const bool on = syn[p * 256 + c] != 0;
-                nz += on;
-                p0 = on ? p : p0;
+        if constexpr (S::kSpan) {
+            // tile lanes wave, wave + NV, ... are this wave's
+            constexpr unsigned long long kShare =
+                NV == 1 ? ~0ull : NV == 2 ? 0x5555555555555555ull : 0x1111111111111111ull;
+            SpanBasis& mb = sb[tw * NV + wave];
+            unsigned pm = 0;  // bit q: column 4 lane + q of the pass is bad
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                pm |= ((tm >> (8 * q + pass)) & 1u) << q;
+            unsigned long long todo = __ballot(pm != 0) & (kShare << wave);
+            while (todo) {
+                const int from = __ffsll(todo) - 1;
+                todo &= todo - 1;
+                unsigned m = (unsigned)__builtin_amdgcn_readlane((int)pm, from);
+                while (m) {
+                    const int c = from * 4 + __ffs(m) - 1;
+                    m &= m - 1;
+                    const uint8_t v = lane < e ? syn[lane * kRow + c] : (uint8_t)0;
+                    span_append(mb, gf, lane, span_reduce(mb, gf, lane, v), s.u);
+                }
             }
-            if (!nz)
-                continue;
-            // locate: the matrix is locatable, so e >= 2
-            const int row = scrub_locate_row(k, e, s.tab, s.tab + 256, kGfJit, syn[c], syn[256 + c], nz, p0,
-                                             [&](int p) { return syn[p * 256 + c]; });
-            hi1 = max(hi1, row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
-            lo1 = max(lo1, row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
+        } else {
+            for (int c = wave * 64 + lane; c < 256; c += 64 * NV) {
+                int nz = 0, p0 = 0;
+#pragma unroll 1
+                for (int p = 0; p < e; ++p) {
+                    const bool on = syn[p * 256 + c] != 0;
+                    nz += on;
+                    p0 = on ? p : p0;
+                }
+                if (!nz)
+                    continue;
+                // locate: the matrix is locatable, so e >= 2
+                const int row = scrub_locate_row(k, e, s.tab, s.tab + 256, kGfJit, syn[c], syn[256 + c], nz, p0,
+                                                 [&](int p) { return syn[p * 256 + c]; });
+                hi1 = max(hi1, row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
+                lo1 = max(lo1, row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
+            }
         }
-        __syncthreads();  // the next pass overwrites syn
+        __syncthreads();  // the next pass overwrites syn; the last one: the bases are complete
+    }
+    if constexpr (S::kSpan) {
+        // one slot per dirty workgroup; any order of the claims gives the same
+        // span W of the block, and so the same output (above)
+        if (tw * NV + wave == 0) {
+            unsigned at = 0;
+            if (lane == 0)
+                at = atomicAdd(&f->hi1, 1u);
+            at = (unsigned)uni((int)at);
+            if (at < (unsigned)s.slots)  // always, with hi1 zero before the launch
+                span_publish_rolled(sb[0], sb, NV * TPW, gf, lane, s.u,
+                                    s.cand + (size_t)b * s.cand_stride + (size_t)at * kLocateSlotBytes);
+        }
+        return;
     }
     for (int o = 32; o > 0; o >>= 1) {
         hi1 = max(hi1, (unsigned)__shfl_down((int)hi1, o, 64));
@@ -319,18 +414,24 @@ struct JitStore {
     }
 };
 
-// The scrub: wave w's rows [8 w, 8 w + 8) against the stored ones
-struct JitScrub8 : JitScrub {
+// The scrub (S = JitScrub) and the locate (JitLocate): wave w's rows [8 w, 8 w
+// + 8) against the stored ones
+template <class S>
+struct JitEpi8 : S {
     template <int NW>
     __device__ __forceinline__ void run(const JitArgs& a, uint8_t* const* dsts, int b, int wave, int,
                                         long long off, uint4* lds, uint32_t m4, uint32_t m2, uint32_t m1) const
     {
         static_assert(kScrubMaskBytes + 32 * 256 <= 2 * C * 2 * 64 * 16, "rows <= 32: syn fits the chunk buffers");
+        static_assert(!S::kSpan || LocLds<8, NW, 1>::kBytes <= 2 * C * 2 * 64 * 16,
+                      "rows <= 8 NW: masks, syn, tables and bases fit the chunk buffers");
         const bool inb = off + 32 <= a.len;
-        scrub_slots<Slots8, NW, 1>(*this, a.k, a.rows, dsts, b, wave * 8, min(8, a.rows - wave * 8), wave, 0, inb,
+        scrub_slots<Slots8, NW, 1>(static_cast<const S&>(*this), a.k, a.rows, dsts, b, wave * 8, min(8, a.rows - wave * 8), wave, 0, inb,
                                    inb ? (uint32_t)off : 0u, reinterpret_cast<uint8_t*>(lds), m4, m2, m1);
     }
 };
+using JitScrub8 = JitEpi8<JitScrub>;
+using JitLocate8 = JitEpi8<JitLocate>;
 
 // `int B` and `long long TILE`: this workgroup's block and its tile
 // (k_rs_jitw: its index) within the block.  Workgroups are dealt round-robin
@@ -488,6 +589,19 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void 
     jit_run<NW, true, JitHooks>(s.j, lds, wave, lane, b, tile, JitScrub8{{s.fold, s.tab, s.locate}});
 }
 
+// The generated locate for e <= 16: k_rs_jit_scrub with the span cold path
+// (JitLocate above)
+template <int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void k_rs_jit_locate(JitLocateArgs s)
+{
+    __shared__ uint4 lds[2][C * 2 * 64];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(s.j, b, tile)
+    jit_run<NW, true, JitHooks>(s.j, lds, wave, lane, b, tile,
+                                JitLocate8{{s.fold, s.cand, s.cand_stride, s.slots, s.u}});
+}
+
 template <int S>
 __device__ __forceinline__ void read_slotw(uint32_t (&W)[8])
 {
@@ -587,20 +701,25 @@ struct JitwStore {
 // ... and the scrub: the wave's rows [wide_row0(e, wave), wide_row0(e, wave +
 // 1)) against the stored ones.  (tile index >= ntile with TPW > 1: off is
 // past the row end, so every lane of that tile is idle.)
-struct JitwScrub : JitScrub {
+template <class S>
+struct JitwEpi : S {
     template <class W, int TPW, int NV>
     __device__ __forceinline__ void run(const JitArgs& a, uint8_t* const* dsts, int b, int wave, int tw, int,
                                         long long off, uint4* lds) const
     {
         static_assert(kScrubMaskBytes + TPW * (NV == 4 ? 64 : 32) * 256 <= 2 * TPW * W::CS * 2 * 64 * 16,
                       "e <= 32 (two waves), e <= 64 (four): syn fits the chunk buffers");
+        static_assert(!S::kSpan || LocLds<W::R, NV, TPW>::kBytes <= 2 * TPW * W::CS * 2 * 64 * 16,
+                      "e <= R NV: masks, syn, tables and bases fit the chunk buffers");
         const uint32_t m4 = vconst(0x0F0F0F0Fu), m2 = vconst(0x33333333u), m1 = vconst(0x55555555u);
         const int r0 = jit::wide_row0(a.rows, wave), nrow = jit::wide_row0(a.rows, wave + 1) - r0;
         const bool inb = off + 32 <= a.len;
-        scrub_slots<SlotsW<W::R>, NV, TPW>(*this, a.k, a.rows, dsts, b, r0, nrow, wave, tw, inb,
+        scrub_slots<SlotsW<W::R>, NV, TPW>(static_cast<const S&>(*this), a.k, a.rows, dsts, b, r0, nrow, wave, tw, inb,
                                            inb ? (uint32_t)off : 0u, reinterpret_cast<uint8_t*>(lds), m4, m2, m1);
     }
 };
+using JitwScrub = JitwEpi<JitScrub>;
+using JitwLocate = JitwEpi<JitLocate>;
 
 // The same decode with R rows per wave (rs_jit.h Wide): 2 waves per column
 // tile; R = 16: 168 VGPRs (3 waves per SIMD), chunks of 6 sources (6
@@ -815,6 +934,21 @@ __global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40)))
     RSGPU_JIT_PLACE(s.j, b, wg)
     const long long tile = wg * TPW + tw;
     jitw_run<W, TPW, NV>(s.j, lds, wv, wave, tw, lane, b, wg, tile, JitwScrub{{s.fold, s.tab, s.locate}});
+}
+
+// The generated locate for 16 < e <= 64: k_rs_jitw_scrub with the span cold
+// path (JitLocate above)
+template <class W, int TPW, int NV>
+__global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40))) void k_rs_jitw_locate(JitLocateArgs s)
+{
+    __shared__ uint4 lds[2][TPW][W::CS * 2 * 64];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wv % NV, tw = wv / NV;
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(s.j, b, wg)
+    const long long tile = wg * TPW + tw;
+    jitw_run<W, TPW, NV>(s.j, lds, wv, wave, tw, lane, b, wg, tile,
+                         JitwLocate{{s.fold, s.cand, s.cand_stride, s.slots, s.u}});
 }
 
 // every 8-byte slot a return: a call that lands in code never written
@@ -1168,45 +1302,83 @@ hipError_t launch_rs_jit(const JitArgs& a, long long blocks, hipStream_t st)
 }
 
 // The grids and the kernel choice of launch_rs_jit (shared program) and
-// launch_rs_jitw, on the scrub kernels.
-hipError_t launch_rs_jit_scrub(const JitScrubArgs& s, long long blocks, hipStream_t st)
+// launch_rs_jitw, on the two kernel families that end in scrub_slots.
+namespace {
+
+struct ScrubFamily {
+    using Args = JitScrubArgs;
+    template <int NW>
+    static constexpr auto jit = &jitk::k_rs_jit_scrub<NW>;
+    template <class W, int TPW, int NV>
+    static constexpr auto wide = &jitk::k_rs_jitw_scrub<W, TPW, NV>;
+};
+struct LocateFamily {
+    using Args = JitLocateArgs;
+    template <int NW>
+    static constexpr auto jit = &jitk::k_rs_jit_locate<NW>;
+    template <class W, int TPW, int NV>
+    static constexpr auto wide = &jitk::k_rs_jitw_locate<W, TPW, NV>;
+};
+
+template <class F, class W>
+void launch_wide(const typename F::Args& s, int nv, int tpw, dim3 grid, dim3 blk, hipStream_t st)
+{
+    if (nv == 4)
+        hipLaunchKernelGGL((F::template wide<W, 1, 4>), grid, blk, 0, st, s);
+    else if (tpw == 3)
+        hipLaunchKernelGGL((F::template wide<W, 3, 2>), grid, blk, 0, st, s);
+    else if (tpw == 2)
+        hipLaunchKernelGGL((F::template wide<W, 2, 2>), grid, blk, 0, st, s);
+    else
+        hipLaunchKernelGGL((F::template wide<W, 1, 2>), grid, blk, 0, st, s);
+}
+
+template <class F>
+hipError_t launch_scrub_family(const typename F::Args& s, long long blocks, hipStream_t st)
 {
     const JitArgs& a = s.j;
     if (a.rows <= 0 || a.rows > 64 || a.dst_stride < a.rows || a.k <= 0 || !a.code || a.chunk_stride <= 0 ||
         a.block_stride != 0 || a.status || a.len <= 0 || a.len % 32 || a.len >= (1LL << 32) || blocks <= 0 ||
-        blocks > (long long)kMaxGridBlocks || !s.fold || (s.locate && !s.tab))
+        blocks > (long long)kMaxGridBlocks || !s.fold)
         return hipErrorInvalidValue;
     const long long ntile = (a.len + 2047) / 2048;
     if (!jitw_rows(a.rows)) {  // e <= 16
         dim3 grid((unsigned)ntile, (unsigned)blocks);
         if (a.rows <= 8)
-            hipLaunchKernelGGL((jitk::k_rs_jit_scrub<1>), grid, dim3(64), 0, st, s);
+            hipLaunchKernelGGL((F::template jit<1>), grid, dim3(64), 0, st, s);
         else
-            hipLaunchKernelGGL((jitk::k_rs_jit_scrub<2>), grid, dim3(128), 0, st, s);
+            hipLaunchKernelGGL((F::template jit<2>), grid, dim3(128), 0, st, s);
         return hipGetLastError();
     }
     const int nv = jit::wide_waves(a.rows);
     const int tpw = nv == 4 ? 1 : a.tiles_per_wg >= 3 ? 3 : a.tiles_per_wg == 2 ? 2 : 1;
     dim3 grid((unsigned)((ntile + tpw - 1) / tpw), (unsigned)blocks);
     dim3 blk(64 * nv * tpw);
-#define RSGPU_JW_LAUNCH(WT)                                                                              \
-    if (nv == 4)                                                                                         \
-        hipLaunchKernelGGL((jitk::k_rs_jitw_scrub<WT, 1, 4>), grid, blk, 0, st, s);                      \
-    else                                                                                                 \
-        switch (tpw) {                                                                                   \
-        case 3: hipLaunchKernelGGL((jitk::k_rs_jitw_scrub<WT, 3, 2>), grid, blk, 0, st, s); break;      \
-        case 2: hipLaunchKernelGGL((jitk::k_rs_jitw_scrub<WT, 2, 2>), grid, blk, 0, st, s); break;      \
-        default: hipLaunchKernelGGL((jitk::k_rs_jitw_scrub<WT, 1, 2>), grid, blk, 0, st, s); break;     \
-        }
-    if (jitw_rows(a.rows) == 16) {
-        RSGPU_JW_LAUNCH(jit::J16)
-    } else if (jitw_rows(a.rows) == 12) {
-        RSGPU_JW_LAUNCH(jit::J12)
-    } else {
-        RSGPU_JW_LAUNCH(jit::J10)
-    }
-#undef RSGPU_JW_LAUNCH
+    if (jitw_rows(a.rows) == 16)
+        launch_wide<F, jit::J16>(s, nv, tpw, grid, blk, st);
+    else if (jitw_rows(a.rows) == 12)
+        launch_wide<F, jit::J12>(s, nv, tpw, grid, blk, st);
+    else
+        launch_wide<F, jit::J10>(s, nv, tpw, grid, blk, st);
     return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_rs_jit_scrub(const JitScrubArgs& s, long long blocks, hipStream_t st)
+{
+    if (s.locate && !s.tab)
+        return hipErrorInvalidValue;
+    return launch_scrub_family<ScrubFamily>(s, blocks, st);
+}
+
+// a slot per tile: no workgroup's claim can pass the block's area
+hipError_t launch_rs_jit_locate(const JitLocateArgs& s, long long blocks, hipStream_t st)
+{
+    if (!s.cand || s.u < 1 || s.u > kLocMax || s.slots < (s.j.len + 2047) / 2048 ||
+        s.cand_stride < (size_t)s.slots * kLocateSlotBytes)
+        return hipErrorInvalidValue;
+    return launch_scrub_family<LocateFamily>(s, blocks, st);
 }
 
 }  // namespace rsgpu

@@ -248,6 +248,25 @@ struct JitScrubArgs {
     int locate;
 };
 hipError_t launch_rs_jit_scrub(const JitScrubArgs& a, long long blocks, hipStream_t st);
+// The generated locate (k_rs_jit_locate, k_rs_jitw_locate; rsgpu_locate_blocks
+// under FUSED with the scrub kernel GENERATED): the generated scrub up to the
+// count of bad columns, then k_rs_bs_locate's contract (below, at
+// launch_rs_bitsliced_locate) for any matrix: a workgroup with a bad column
+// reduces the syndrome columns of all its tiles to a basis of at most u
+// vectors and writes it to the slot it claims with an atomicAdd on fold[b].hi1
+// (zero before the launch).  A block's area holds `slots` slots, one per tile
+// of 2048 bytes; a workgroup covers at least one tile and claims at most one
+// slot.  k_locate_finish with `claimed` follows.  j as JitScrubArgs::j; 1 <= u
+// <= 8.
+struct JitLocateArgs {
+    JitArgs j;
+    ScrubFold* fold;     // [B]; hi1 counts the block's claimed slots
+    uint8_t* cand;       // [B] candidate areas at cand_stride
+    size_t cand_stride;
+    int slots;           // per block
+    int u;
+};
+hipError_t launch_rs_jit_locate(const JitLocateArgs& a, long long blocks, hipStream_t st);
 // small uploads through the kernel arguments (k_put_words): bytes % 8 == 0,
 // at most sizeof(PutArgs::w)
 struct PutArgs {

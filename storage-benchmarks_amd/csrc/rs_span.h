@@ -1,8 +1,8 @@
 // rs_span.h -- the wave-cooperative span arithmetic of the locate
 // (rsgpu_locate_blocks): an echelon basis of at most RSGPU_LOCATE_MAX_ROWS
 // vectors of GF(2^8)^64 in LDS, a lane per coordinate.  Shared by
-// rs_locate.hip (k_locate_span, k_locate_finish) and rs_bitsliced.hip
-// (k_rs_bs_locate): one copy of the basis, the slot format, the reduction and
+// rs_locate.hip (k_locate_span, k_locate_finish), rs_bitsliced.hip
+// (k_rs_bs_locate) and rs_jit.hip (k_rs_jit_locate, k_rs_jitw_locate): one copy of the basis, the slot format, the reduction and
 // the append.  The merge of a workgroup's bases into its slot (span_publish) is
 // k_rs_bs_locate's; k_locate_span has the same steps written out, which keeps
 // its instructions what they were.
@@ -101,8 +101,8 @@ __device__ __forceinline__ void span_append(SpanBasis& s, const GfTables& gf, in
 // Wave 0 of a workgroup, after the barrier behind the last append: the bases
 // sb[1 .. nw) merged into its own, s = sb[0] (ovf is sticky), and s written to
 // `slot` of a candidate area.
-__device__ __forceinline__ void span_publish(SpanBasis& s, const SpanBasis* sb, int nw, const GfTables& gf, int lane,
-                                             int cap, uint8_t* slot)
+__device__ __forceinline__ void span_merge(SpanBasis& s, const SpanBasis* sb, int nw, const GfTables& gf, int lane,
+                                           int cap)
 {
     for (int w = 1; w < nw; ++w) {
         const int n = uni(sb[w].n);
@@ -111,12 +111,50 @@ __device__ __forceinline__ void span_publish(SpanBasis& s, const SpanBasis* sb, 
         for (int i = 0; i < n; ++i)
             span_append(s, gf, lane, span_reduce(s, gf, lane, sb[w].v[i][lane]), cap);
     }
+}
+
+__device__ __forceinline__ void span_publish(SpanBasis& s, const SpanBasis* sb, int nw, const GfTables& gf, int lane,
+                                             int cap, uint8_t* slot)
+{
+    span_merge(s, sb, nw, gf, lane, cap);
     const int n = uni(s.n);
     if (lane == 0) {
         SlotHdr* hdr = reinterpret_cast<SlotHdr*>(slot);
         hdr->n = n;
         hdr->ovf = s.ovf;
     }
+    for (int i = 0; i < n; ++i)
+        slot[sizeof(SlotHdr) + i * 64 + lane] = s.v[i][lane];
+}
+
+// load_gf and span_publish for the generated kernels (rs_jit.hip k_rs_jit_locate,
+// k_rs_jitw_locate), whose compiler-allocated registers must end below the
+// accumulators: the same copies and the same slot, every loop rolled.  The
+// compiler unrolls the loops above eight and thirteen times with a 64-bit
+// address per iteration, which took k_rs_jitw_locate's allocation past v39.
+// Both tables are 4-byte aligned (the device copy alignas(16), the LDS copy
+// where the kernel puts it).
+__device__ __forceinline__ void load_gf_rolled(GfTables& gf, const GfTables& from, int t, int threads)
+{
+    static_assert(sizeof(GfTables) % 4 == 0, "copied as dwords");
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&from);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(&gf);
+#pragma unroll 1
+    for (int i = t; i < (int)(sizeof(GfTables) / 4); i += threads)
+        dst[i] = src[i];
+}
+
+__device__ __forceinline__ void span_publish_rolled(SpanBasis& s, const SpanBasis* sb, int nw, const GfTables& gf,
+                                                    int lane, int cap, uint8_t* slot)
+{
+    span_merge(s, sb, nw, gf, lane, cap);
+    const int n = uni(s.n);
+    if (lane == 0) {
+        SlotHdr* hdr = reinterpret_cast<SlotHdr*>(slot);
+        hdr->n = n;
+        hdr->ovf = s.ovf;
+    }
+#pragma unroll 1
     for (int i = 0; i < n; ++i)
         slot[sizeof(SlotHdr) + i * 64 + lane] = s.v[i][lane];
 }

@@ -83,6 +83,12 @@ int jit_probe(rsgpu_ctx* ctx);
 int shared_program_scrub(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long blocks,
                          const uint8_t* const* d_srcs, const uint8_t* const* d_par, ScrubFold* fold,
                          const uint8_t* tab, int locate, const char* name);
+// The generated locate on the same program with the same settings (rs_kernels.h
+// JitLocateArgs): the fold and the candidate areas of `blocks` blocks, `slots`
+// slots each.  Recorded as `name`.
+int shared_program_locate(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long blocks,
+                          const uint8_t* const* d_srcs, const uint8_t* const* d_par, ScrubFold* fold, uint8_t* cand,
+                          size_t cand_stride, int slots, int u, const char* name);
 
 // >= bytes of executable device memory at ctx->d_jit, a new generation when regrown
 int jit_ensure(rsgpu_ctx* ctx, size_t bytes);

@@ -817,12 +817,19 @@ int rsgpu_locate_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
     // launch; the workgroups per block are those of the largest slice.
     // FUSED (rsgpu.h): per group one k_rs_bs_locate, which reads the rows as
     // the FUSED scrub does and leaves a slot per dirty tile, the block's area
-    // holding one per tile; no scratch, no encode.
+    // holding one per tile; no scratch, no encode.  Where the compiled form
+    // does not apply and the context's scrub kernel is GENERATED, the
+    // generated form: per group one k_rs_jit_locate / k_rs_jitw_locate on the
+    // matrix's shared program, row pointers in the context's scratch as the
+    // GENERATED scrub builds them, the same slots and the same finish.
     const size_t per_block = (size_t)e * pitch;
     const size_t tiles = (len + 2047) / 2048;
-    const bool fused = work && ctx->locate_kernel == RSGPU_LOCATE_FUSED &&
-                       fused_rows(k, e, len, pitch, d_src, d_parity, coef) &&
-                       tiles * kLocateSlotBytes <= kDegTabBytes;
+    const bool want_fused = work && ctx->locate_kernel == RSGPU_LOCATE_FUSED &&
+                            tiles * kLocateSlotBytes <= kDegTabBytes;
+    const bool compiled = want_fused && fused_rows(k, e, len, pitch, d_src, d_parity, coef);
+    const bool generated = want_fused && !compiled && ctx->scrub_kernel == RSGPU_SCRUB_GENERATED &&
+                           rows_aligned(len, pitch, d_src, d_parity) && len < (1ull << 32) && jit_probe(ctx) == 1;
+    const bool fused = compiled || generated;
     const bool vec = pitch % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
     const long long n16 = work && vec ? (long long)(len / 16) : 0;
     const long long rest = (long long)len - n16 * 16;  // byte columns
@@ -837,11 +844,17 @@ int rsgpu_locate_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
     size_t group = std::max<size_t>(1, std::min({blocks, kMaxGridBlocks, kDegTabBytes / std::max<size_t>(1, stride)}));
     if (ctx->locate_group_max)
         group = std::min(group, ctx->locate_group_max);
+    // the generated form's row pointers of a group: [group][k] then [group][e]
+    const size_t src_ptr_bytes = align_up(sizeof(void*) * (size_t)k * group, 256);
+    const size_t par_ptr_bytes = align_up(sizeof(void*) * (size_t)e * group, 256);
+    const std::vector<uint8_t> matrix = generated ? parity_matrix(k, e, coef) : std::vector<uint8_t>();
     if (work) {
         rc = ensure_device(ctx, ctx->locate, group * stride);
         // the scratch of the largest group now, so that no walk below grows it
         if (!rc && !fused)
             rc = grow_parity_scratch(ctx, group, per_block);
+        if (!rc && generated)
+            rc = ensure_scratch(ctx, src_ptr_bytes + par_ptr_bytes);
         // the matrix on the device (behind the update's tables)
         if (!rc)
             rc = update_tables(ctx, k, e, coef);
@@ -879,9 +892,21 @@ int rsgpu_locate_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
                 };
                 return launch_head_and_tail(ctx, kLocateNames, nb, n16, (long long)len, launch);
             };
-            if (fused) {
-                // the claims are counted in the reports' status field, zero since the memset
-                a.claimed = 1;
+            // fused: the claims are counted in the reports' status field, zero since the memset
+            a.claimed = fused ? 1 : 0;
+            if (generated) {
+                char* d = (char*)ctx->scratch.p;
+                RS_HIP(ctx, launch_row_ptrs(d_src + g0 * (size_t)k * pitch, (long long)pitch, k, (long long)ng,
+                                            (const uint8_t**)d, ctx->stream));
+                RS_HIP(ctx, launch_row_ptrs(d_parity + g0 * per_block, (long long)pitch, e, (long long)ng,
+                                            (const uint8_t**)(d + src_ptr_bytes), ctx->stream));
+                rc = shared_program_locate(ctx, matrix.data(), k, e, (long long)len, (long long)ng,
+                                           (const uint8_t* const*)d, (const uint8_t* const*)(d + src_ptr_bytes),
+                                           reinterpret_cast<ScrubFold*>(d_report + g0), a.cand, stride, slots, u,
+                                           "k_rs_jit_locate");
+                if (rc)
+                    return rc;
+            } else if (compiled) {
                 KTimer kt(ctx, "k_rs_bs_locate", ng);
                 RS_HIP(ctx, launch_rs_bitsliced_locate(k, e, d_src + g0 * (size_t)k * pitch,
                                                        d_parity + g0 * per_block, (long long)pitch, (long long)len,

@@ -451,7 +451,9 @@ class Context:
         shared generated program with the stored parity compared in registers,
         for any matrix with e <= 64 on 16-byte aligned rows of len % 32 == 0;
         opt-in, auto never picks it.  repair_blocks runs its two-pass form
-        under it."""
+        under it.  Together with set_locate_kernel("fused") it also opts
+        locate_blocks into the generated locate for the matrices that have no
+        compiled kernel."""
         self.check(lib().rsgpu_set_scrub_kernel(self._h, SCRUB_KERNELS[kernel]),
                    "rsgpu_set_scrub_kernel")
 
@@ -464,9 +466,13 @@ class Context:
     def set_locate_kernel(self, kernel: str) -> None:
         """Kernel of locate_blocks (and of GpuEncoder.locate and heal): auto |
         two_pass | fused (include/rsgpu.h rsgpu_set_locate_kernel); every
-        choice writes the same reports and lists.  fused: the compiled codes'
-        fused scrub with the span of a dirty tile's syndromes as its cold
-        path; opt-in, auto runs two_pass."""
+        choice writes the same reports and lists.  fused: fused into the
+        encode program of the call's matrix, the span of a dirty tile's
+        syndromes as the scrub's cold path -- the compiled codes' kernel where
+        it applies; otherwise, with set_scrub_kernel("generated"), the
+        matrix's shared generated program (any matrix with e <= 64 on 16-byte
+        aligned rows of len % 32 == 0); otherwise two_pass.  Opt-in, auto
+        runs two_pass."""
         self.check(lib().rsgpu_set_locate_kernel(self._h, LOCATE_KERNELS[kernel]),
                    "rsgpu_set_locate_kernel")
 
@@ -585,18 +591,24 @@ class GpuEncoder:
 
     The constructor allocates k+e rows per block and fills the k source rows
     with the seeded synthetic stream (isa.cpp:43-58); ``encode_all`` is the
-    timed parity generation (isa.cpp:69-79).
+    timed parity generation (isa.cpp:69-79).  ``coef`` (e x k bytes) is the
+    parity matrix of every call this encoder makes (encode_all, scrub, locate,
+    heal, ...); None is the built-in gf_gen_rs_matrix code, the only one a
+    GpuDecoder decodes.
     """
 
     def __init__(self, symbols: int, symbol_size: int, encoded_symbols: int, blocks: int = 1,
                  seed: int = 1, ctx: Optional[Context] = None, device: int = 0,
-                 block0: int = 0, pitch: Optional[int] = None):
+                 block0: int = 0, pitch: Optional[int] = None, coef=None):
         import torch
         if not (0 < symbols and 0 <= encoded_symbols and symbols + encoded_symbols <= MAX_SOURCES):
             raise ValueError("symbols + encoded_symbols must be in (0, 250]")
         self.k, self.e, self.L, self.B = symbols, encoded_symbols, symbol_size, blocks
         self.pitch = pitch if pitch is not None else row_pitch(symbol_size)
         self.seed, self.block0 = seed, block0
+        self.coef = _coef(coef)
+        if self.coef is not None and self.coef.size != self.k * self.e:
+            raise ValueError("coef must hold encoded_symbols x symbols bytes")
         self.ctx = _context(ctx, device)
         dev = torch.device("cuda", self.ctx.device)
         self.src = torch.empty(max(1, self.B * self.k * self.pitch), dtype=torch.uint8, device=dev)
@@ -607,7 +619,8 @@ class GpuEncoder:
         self.m_payload_count = self.e
 
     def encode_all(self) -> None:
-        self.ctx.encode_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par)
+        self.ctx.encode_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,
+                               coef=self.coef)
 
     def _report(self, dtype):
         """Device memory for one record of dtype per block, uninitialised."""
@@ -635,7 +648,7 @@ class GpuEncoder:
         Synchronises (the reports are copied to the host)."""
         rep = self._report(SCRUB_REPORT_DTYPE)
         self.ctx.scrub_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, rep,
-                              locate=locate)
+                              coef=self.coef, locate=locate)
         return self._read(rep, SCRUB_REPORT_DTYPE)
 
     def scrub_degraded(self, lost, locate: bool = True) -> np.ndarray:
@@ -648,7 +661,7 @@ class GpuEncoder:
         u, d_lost = self._lists("lost", lost)
         rep = self._report(SCRUB_REPORT_DTYPE)
         self.ctx.scrub_degraded_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,
-                                       u, d_lost, rep, locate=locate)
+                                       u, d_lost, rep, coef=self.coef, locate=locate)
         return self._read(rep, SCRUB_REPORT_DTYPE)
 
     def rebuild(self, lost, check: bool = True) -> np.ndarray:
@@ -661,7 +674,7 @@ class GpuEncoder:
         u, d_lost = self._lists("lost", lost)
         rep = self._report(SCRUB_REPORT_DTYPE)
         self.ctx.rebuild_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,
-                                u, d_lost, rep, check=check)
+                                u, d_lost, rep, coef=self.coef, check=check)
         return self._read(rep, SCRUB_REPORT_DTYPE)
 
     def _locate(self, u: int):
@@ -670,7 +683,7 @@ class GpuEncoder:
         rep = self._report(SCRUB_REPORT_DTYPE)
         rows = torch.empty(max(1, self.B) * u, dtype=torch.uint8, device=self.src.device)
         self.ctx.locate_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, u,
-                               rows, rep)
+                               rows, rep, coef=self.coef)
         return rep, rows
 
     def locate(self, u: int = LOCATE_MAX_ROWS):
@@ -679,7 +692,9 @@ class GpuEncoder:
         reports as a structured array (SCRUB_REPORT_DTYPE; CLEAN, ONE_ROW,
         SCRUB_ROWS or DAMAGED) and a (blocks, u) uint8 array of the located
         rows per block, ascending and padded with LOST_NONE, as rebuild takes
-        them.  Synchronises (both are copied to the host)."""
+        them.  Runs the kernel the context is set to (set_locate_kernel, and
+        with "fused" set_scrub_kernel).  Synchronises (both are copied to the
+        host)."""
         rep, rows = self._locate(u)
         reports = self._read(rep, SCRUB_REPORT_DTYPE)
         return reports, rows.cpu().numpy()[: self.B * u].reshape(self.B, u).copy()
@@ -688,12 +703,14 @@ class GpuEncoder:
         """locate, then rebuild (without the check) of the located rows in
         place, the lists staying on the device and both on the stream with no
         host decision in between; a block locate calls DAMAGED has an empty
-        list and is left as it is.  Returns (locate_reports, rebuild_reports).
-        Synchronises (the reports are copied to the host)."""
+        list and is left as it is.  The locate follows the context as
+        locate() does: under set_locate_kernel("fused") the compiled kernel,
+        or with set_scrub_kernel("generated") the generated one.  Returns
+        (locate_reports, rebuild_reports).  Synchronises (the reports are copied to the host)."""
         rep, rows = self._locate(u)
         rep2 = self._report(SCRUB_REPORT_DTYPE)
         self.ctx.rebuild_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,
-                                u, rows, rep2, check=False)
+                                u, rows, rep2, coef=self.coef, check=False)
         return self._read(rep, SCRUB_REPORT_DTYPE), self._read(rep2, SCRUB_REPORT_DTYPE)
 
     def repair(self, mode: str = "one_row") -> np.ndarray:
@@ -703,7 +720,7 @@ class GpuEncoder:
         Synchronises (the reports are copied to the host)."""
         rep = self._report(REPAIR_REPORT_DTYPE)
         self.ctx.repair_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, rep,
-                               mode=mode)
+                               coef=self.coef, mode=mode)
         return self._read(rep, REPAIR_REPORT_DTYPE)
 
     def update(self, cols, rows, delta: bool = False) -> np.ndarray:
@@ -719,7 +736,8 @@ class GpuEncoder:
             raise ValueError("rows must hold blocks x u rows at the encoder's pitch")
         status = self._report(np.int32)
         self.ctx.update_blocks(self.k, self.e, self.L, self.pitch, self.B, u, d_cols, rows,
-                               None if delta else self.src, self.par, status, delta=delta)
+                               None if delta else self.src, self.par, status, coef=self.coef,
+                               delta=delta)
         return self._read(status, np.int32)
 
     def block_size(self) -> int:

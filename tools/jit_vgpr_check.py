@@ -23,7 +23,7 @@ import tempfile
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kernel_isa_diff as kid  # noqa: E402
 
-KERNEL = re.compile(r"^(_ZN5rsgpu4jitk\d+k_rs_jit(w?)(?:_scrub)?I\S*):")
+KERNEL = re.compile(r"^(_ZN5rsgpu4jitk\d+k_rs_jit(w?)(?:_scrub|_locate)?I\S*):")
 WIDE_R = re.compile(r"WideILi(\d+)E")
 
 

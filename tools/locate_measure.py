@@ -29,8 +29,15 @@ FUSED), then the four TWO_PASS locate kinds on the same damage, then the copy.
 The summary then holds fused_locate_clean / fused_scrub_clean over the mirrored
 pairs and every fused locate kind over its TWO_PASS twin.
 
+With --kernel generated (profiles/locate_generated/README.md) the fused form
+measured is the generated one, for any matrix (--matrix rs | cauchy: the
+built-in gf_gen_rs_matrix code or the Cauchy matrix of the shape):
+`generated_scrub_clean` (rsgpu_scrub_blocks, GENERATED, LOCATE) and
+`generated_locate_*` (rsgpu_set_locate_kernel FUSED with the scrub kernel
+GENERATED), the TWO_PASS twins and the copy, summarised the same way.
+
     python tools/locate_measure.py out.json [--k 64 --e 32 --len 1000000 --blocks 1024 --rounds 12]
-                                            [--kernel {two_pass,fused}]
+                                            [--kernel {two_pass,fused,generated}] [--matrix {rs,cauchy}]
 """
 import numpy as np
 import torch
@@ -44,11 +51,16 @@ U = rsgpu.LOCATE_MAX_ROWS
 
 def main():
     ap = ml.shape_parser()
-    ap.add_argument("--kernel", choices=["two_pass", "fused"], default="two_pass")
+    ap.add_argument("--kernel", choices=["two_pass", "fused", "generated"], default="two_pass")
+    ap.add_argument("--matrix", choices=["rs", "cauchy"], default="rs")
     a = ap.parse_args()
-    both = a.kernel == "fused"
+    both = a.kernel != "two_pass"
+    pre = a.kernel + "_" if both else ""
+    # the kernel a fused kind must have run: no silent fall-back to TWO_PASS
+    ran = {"fused": ("k_rs_bs_scrub", "k_rs_bs_locate"), "generated": ("k_rs_jit_scrub", "k_rs_jit_locate")}
     k, e, L, B = a.k, a.e, a.len, a.blocks
-    ctx, enc = ml.setup(a)
+    coef = None if a.matrix == "rs" else rsgpu.gf_gen_cauchy1_matrix(k + e, k)[k:]
+    ctx, enc = ml.setup(a, coef)
     ctx.set_scrub_kernel("two_pass")
     dev, pitch = enc.src.device, enc.pitch
     rep = ml.reports(enc)
@@ -87,18 +99,19 @@ def main():
         """One timed run: (ms, {kernel name: ms})."""
         if kind == "copy":
             return copy()
-        form = "fused" if kind.startswith("fused_") else "two_pass"
-        kind = kind.removeprefix("fused_")
+        form = a.kernel if both and kind.startswith(pre) else "two_pass"
+        kind = kind.removeprefix(pre)
+        ctx.set_scrub_kernel(form)
         if kind == "scrub_clean":
-            ctx.set_scrub_kernel(form)
-            return ml.timed(ctx, lambda: ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, rep))
-        ctx.set_locate_kernel(form)
+            return ml.timed(ctx, lambda: ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, rep, coef=coef))
+        ctx.set_locate_kernel("fused" if form == "generated" else form)
         flip = damage.get(kind)
         if flip:
             flip()
             torch.cuda.synchronize()
         try:
-            return ml.timed(ctx, lambda: ctx.locate_blocks(k, e, L, pitch, B, enc.src, enc.par, U, lists, rep))
+            return ml.timed(ctx, lambda: ctx.locate_blocks(k, e, L, pitch, B, enc.src, enc.par, U, lists, rep,
+                                                          coef=coef))
         finally:
             if flip:
                 flip()
@@ -106,7 +119,7 @@ def main():
 
     locates = ["locate_clean", "locate_one", "locate_two", "locate_whole"]
     if both:
-        kinds = ["fused_scrub_clean", *("fused_" + n for n in locates), *locates, "copy"]
+        kinds = [pre + "scrub_clean", *(pre + n for n in locates), *locates, "copy"]
     else:
         kinds = ["scrub_clean", *locates, "copy"]
     h1, h2 = r1.cpu().numpy(), r2.cpu().numpy()
@@ -119,9 +132,10 @@ def main():
         kernels_seen[kind] = sorted(by)
         if kind == "copy":
             continue
-        if kind.startswith("fused_"):  # no silent fall-back to TWO_PASS
-            assert ("k_rs_bs_scrub" if "scrub" in kind else "k_rs_bs_locate") in by, (kind, sorted(by))
-            kind = kind.removeprefix("fused_")
+        if both and kind.startswith(pre):
+            assert ran[a.kernel]["locate" in kind] in by and not any(n.startswith("k_locate_span") for n in by), \
+                (kind, sorted(by))
+            kind = kind.removeprefix(pre)
         r = rep.cpu().numpy().view(DT)
         got = lists.cpu().numpy().reshape(B, U)
         if kind.endswith("clean"):
@@ -133,24 +147,23 @@ def main():
             assert (r["status"] == rsgpu.SCRUB_ROWS).all() and (r["row"] == lo).all(), kind
             assert (got[:, 0] == lo).all() and (got[:, 1] == hi).all() and (got[:, 2:] == 255).all(), kind
     ctx.set_scrub_kernel("two_pass")
-    ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, rep)
+    ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, rep, coef=coef)
     torch.cuda.synchronize()
     assert ml.all_clean(rep), "the blocks after the damage was taken out again"
 
-    out = {**ml.header(enc), "kernels": kernels_seen, "bad_columns_per_row": int(len(c1)),
+    out = {**ml.header(enc), "matrix": a.matrix, "kernels": kernels_seen, "bad_columns_per_row": int(len(c1)),
            "runs": ml.mirrored_rounds(kinds, a.rounds, run)}
     summ = ml.summarise(out["runs"], kinds, kernel_medians=True)
     summ["copy"]["tb_per_s"] = 2 * copy_bytes / (summ["copy"]["median"] * 1e-3) / 1e12
     half = len(kinds)
     at = {(r["round"], r["pos"] >= half, r["kind"]): r["ms"] for r in out["runs"]}
-    pre = "fused_" if both else ""
     ratios = [at[(rnd, h, pre + "locate_clean")] / at[(rnd, h, pre + "scrub_clean")] for rnd in range(a.rounds)
               for h in (False, True)]
     summ[pre + "locate_clean"]["over_scrub_in_pairs"] = ml.stats(ratios)
     for kind in kinds[1:-1]:
         summ[kind]["over_scrub"] = summ[kind]["median"] / summ[pre + "scrub_clean"]["median"]
     for kind in locates if both else []:
-        summ["fused_" + kind]["over_two_pass"] = summ["fused_" + kind]["median"] / summ[kind]["median"]
+        summ[pre + kind]["over_two_pass"] = summ[pre + kind]["median"] / summ[kind]["median"]
     ml.finish(a.out, out, summ)
     ctx.set_scrub_kernel("auto")
     ctx.set_locate_kernel("auto")

@@ -30,11 +30,12 @@ def shape_parser():
     return ap
 
 
-def setup(a):
-    """(context on torch's stream, encoder of the shape with its parity encoded)."""
+def setup(a, coef=None):
+    """(context on torch's stream, encoder of the shape with its parity encoded;
+    coef: the encoder's parity matrix, None for the built-in code)."""
     ctx = rsgpu.Context(0)
     ctx.set_torch_stream()
-    enc = rsgpu.GpuEncoder(a.k, a.len, a.e, blocks=a.blocks, seed=5, ctx=ctx)
+    enc = rsgpu.GpuEncoder(a.k, a.len, a.e, blocks=a.blocks, seed=5, ctx=ctx, coef=coef)
     enc.encode_all()
     return ctx, enc
 
