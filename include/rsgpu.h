@@ -145,7 +145,8 @@ int rsgpu_encode_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, 
  *              {(16,4) (16,8) (64,32) (64,16) (5,4) (20,7)}, no `coef`),
  *              otherwise GENERATED (aligned rows, len % 32 == 0; (100,20),
  *              compiled too, runs GENERATED: its compiled waves own 5 rows),
- *              otherwise the v_perm kernel
+ *              otherwise the v_perm kernel; (64, 32) calls of at least
+ *              480000 (2 KB column tile, block) pairs run KARATSUBA
  *   COMPILED   k_rs_bs: the matrix compiled into the kernel (codes above
  *              and (100,20))
  *   GENERATED  code built on the host for the matrix, once, shared by every
@@ -158,11 +159,17 @@ int rsgpu_encode_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, 
  *              used out), so a caller cycling through matrices builds each
  *              once
  *   THREADED   k_rs_tc: 256 generated handlers, one dispatch per coefficient
+ *   KARATSUBA  the (64, 32) gf_gen_rs_matrix code through a generated program
+ *              split by one Karatsuba level: three waves per column tile,
+ *              each one 16 x 32 product, combined once per tile (k_rs_kara;
+ *              aligned rows, len % 32 == 0); where it does not apply the
+ *              choice behaves as AUTO
  * A choice that does not apply falls back in that order. */
 #define RSGPU_ENCODE_AUTO 0
 #define RSGPU_ENCODE_COMPILED 1
 #define RSGPU_ENCODE_GENERATED 2
 #define RSGPU_ENCODE_THREADED 3
+#define RSGPU_ENCODE_KARATSUBA 4
 int rsgpu_set_encode_kernel(rsgpu_ctx *ctx, int kernel);
 
 /* Device workspace needed by rsgpu_decode_blocks for this geometry (any

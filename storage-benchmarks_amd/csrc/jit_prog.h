@@ -77,5 +77,39 @@ std::vector<uint8_t> build_matrix_code_wide_passes(const uint8_t* c, int k, int 
                                                    std::vector<std::pair<size_t, int>>* passes,
                                                    int max_ops = kMaxComposites);
 
+// ---- the Karatsuba-split program of the (64, 32) gf_gen_rs_matrix code ------
+//
+// V[r][j] = 2^(r j) = D1[r] h(r + j) d[j] with h(n) = 2^C(n, 2), d[j] =
+// 2^-C(j, 2), D1[r] = 2^-C(r, 2) (tools/karatsuba_price.py).  One Karatsuba
+// level on both 32-source halves (base = 0, 32; q, r < 16; s = 16 (base / 32)
+// + q names the source pair x[base + q], x[base + 16 + q]) gives three 16 x 32
+// products, one per role wave of a column tile (k_rs_kara, rs_jit.hip):
+//   P   over the virtual sources v_s = x[base + q] ^ rho[s] x[base + 16 + q]
+//   Q1  over x[base + q],   Q2 over x[base + 16 + q]
+//   y[r] = P[r] ^ Q1[r],    y[16 + r] = sigma[r] P[r] ^ Q2[r]
+// Code: role w (0 = P, 1 = Q1, 2 = Q2), chunk ch at (w kKaraChunks + ch)
+// chunk_stride, in the Wide<16, .> register contract (rs_jit.h).  Chunks 0 ..
+// kKaraSrcChunks - 1 hold kKaraPairs source pairs each, pair i of a chunk at
+// LDS positions 2 i (x[base + q]) and 2 i + 1 (x[base + 16 + q]); P loads
+// both, the second into v18..v25, XORs rho's program (temporaries from v26)
+// into v10..v17 and goes on as any source.  Chunk kKaraSrcChunks is the
+// combine, run once per tile after the last source chunk: its 16 sources are
+// P's rows as planes in LDS (row r at position r), added into slot r through
+// the identity (Q1) or sigma[r]'s XOR program (Q2); P's is a bare return.
+// (kKaraPairs, kKaraSrcChunks, kKaraChunks, kara_source: rs_jit.h, shared
+// with the kernel.)
+struct KaraProgram {
+    std::vector<uint8_t> code;
+    int chunk_stride = 0;
+    uint8_t cP[16 * 32], cQ1[16 * 32], cQ2[16 * 32];  // [r][s]
+    uint8_t rho[32], sigma[16];
+};
+
+// Builds the program for the 32 x 64 matrix c (row-major), which must be the
+// gf_gen_rs_matrix parity rows: every coefficient of c is checked against the
+// split, and false comes back (nothing built) when one differs or a scaling
+// program needs more temporaries than the contract has.
+bool build_karatsuba_code(const uint8_t* c, KaraProgram* out);
+
 }  // namespace jit
 }  // namespace rsgpu

@@ -288,6 +288,21 @@ using J16 = Wide<16, 6>;
 using J12 = Wide<12, 6>;
 using J10 = Wide<10, 5>;
 
+// ---- the Karatsuba-split (64, 32) encode (k_rs_kara; program: jit_prog.h) ----
+// Three role waves per column tile (P, Q1, Q2), each in the Wide<16, .>
+// register contract above.  A source chunk holds kKaraPairs source pairs
+// (x[base + q], x[base + 16 + q]) at LDS positions 2 i, 2 i + 1; one more
+// chunk per role, the combine, runs once per tile on P's rows in LDS.
+constexpr int kKaraPairs = 4;                    // source pairs per chunk: 8 sources, 16 KB
+constexpr int kKaraSrcChunks = 32 / kKaraPairs;  // 8
+constexpr int kKaraChunks = kKaraSrcChunks + 1;  // + the combine chunk
+// the real source at LDS position t (< 2 kKaraPairs) of source chunk ch
+RJ_HD constexpr int kara_source(int ch, int t)
+{
+    const int s = kKaraPairs * ch + t / 2;
+    return 32 * (s / 16) + (s % 16) + 16 * (t & 1);
+}
+
 // Word tables of the device emitter k_jitw_emit (the register contract, and
 // so every table, is the same for all R): the base word (mac_base) of
 // coefficient c for output plane b at [8 c + b], and the 14 preamble words

@@ -922,6 +922,140 @@ __global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40)))
     RSGPU_DIAG_END();
 }
 
+// The (64, 32) encode through the Karatsuba-split program (jit_prog.h
+// build_karatsuba_code): one column tile per workgroup of three role waves
+// (wave 0 = P, 1 = Q1, 2 = Q2), each in k_rs_jitw's 16-row register contract
+// (168 VGPRs, 3 waves per SIMD), each accumulating one pure 16 x 32 product
+// over all 8 chunks of 4 source pairs (8 real sources, 16 KB per buffer;
+// double-buffered LDS-DMA, the in-place transposes, the priority window and
+// the start-time chunk rotation as jitw_run).  Of a chunk's 8 transposes P
+// takes 2 (positions 2, 5: it also forms the virtual sources), Q1 and Q2 3
+// each (0 3 6 / 1 4 7); a wave transposes what it loaded.  After the last
+// chunk P writes its 16 rows as planes over the two chunk buffers (2 x 16 KB,
+// contiguous), and Q1 / Q2 run their combine chunk on them (y[r] = P[r] ^
+// Q1[r], y[16 + r] = sigma_r P[r] ^ Q2[r]) and store rows 0-15 / 16-31 with
+// k_rs_jitw's epilogue.
+// One tile per workgroup (32 KB of LDS, four workgroups per CU, 3 waves per
+// SIMD): the tiles of a CU start and end independently, so one's first loads
+// and last stores run beside the others' code, and a barrier waits for three
+// waves.  Measured at C3 in one process (profiles/karatsuba3/): 20.85 ms,
+// against 23.10 ms for four tiles per workgroup (12 waves, 128 KB, one
+// workgroup per CU) and 29.87 ms for two (six-wave workgroups spread unevenly
+// over the SIMDs, as DESIGN 4 records for the decode).
+__global__ __launch_bounds__(64 * 3) __attribute__((amdgpu_num_vgpr(40))) void k_rs_kara(JitArgs a)
+{
+    constexpr int CS = 2 * jit::kKaraPairs, NCH = jit::kKaraSrcChunks, K = 64;
+    __shared__ uint4 lds[2][CS * 2 * 64];
+    const int role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(a, b, tile)
+    const uint8_t* const* srcs = a.srcs + (size_t)b * K;
+    uint8_t* const* dsts = a.dsts + (size_t)b * a.dst_stride;
+    const uint8_t* code = a.code + (size_t)role * jit::kKaraChunks * a.chunk_stride;
+    const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint4*)&lds[0][0];
+    constexpr uint32_t kBuf = CS * 2 * 64 * 16;  // bytes between the two chunk buffers
+    const long long off = tile * 2048 + lane * 32;
+    const uint32_t loff = off + 32 <= a.len ? (uint32_t)off : 0u;  // past the row end: its head, never stored
+    if (role == 0)
+        asm volatile("s_icache_inv\n s_nop 15\n s_nop 15" ::: "memory");
+    typedef const uint8_t* const __attribute__((address_space(4)))* CPtrs;
+    const CPtrs csrcs = (CPtrs)srcs;
+    const int first = role == 0 ? 2 : role - 1;  // this wave's positions of a chunk: first, first + 3, ...
+    constexpr int PW = 3;
+    auto ptrs = [&](int ch, const uint8_t* (&p)[PW]) {
+#pragma unroll
+        for (int i = 0; i < PW; ++i)
+            p[i] = csrcs[jit::kara_source(ch, min(first + 3 * i, CS - 1))];  // in bounds, unconditional
+    };
+    // NOTE: the first word of chunk buffer 1 carries the chunk rotation until
+    // every wave has read it, before the first chunk barrier: no LDS-DMA may
+    // target buffer 1 before that barrier.
+    auto issue = [&](int par, const uint8_t* const (&p)[PW]) {
+        const uint32_t base = lds0 + (uint32_t)(par * kBuf);
+#pragma unroll
+        for (int i = 0; i < PW; ++i) {
+            const int t = first + 3 * i;
+            if (t < CS)
+                glds32(p[i], loff, base + (uint32_t)(t * 2 * 64 * 16));
+        }
+    };
+    asm volatile(RSGPU_J16_ZERO ::: RSGPU_J16_ACC_CLOBBERS);
+    int rot = 0;
+    if (a.chunk_rot_ticks > 0) {
+        volatile int& s_rot = *(volatile int*)&lds[1][0];
+        if (threadIdx.x == 0) {
+            unsigned long long t;
+            asm volatile("s_memrealtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
+            const unsigned long long p = (unsigned long long)a.chunk_rot_ticks;
+            s_rot = (int)(((t + p / 2) / p) % (unsigned long long)NCH);
+        }
+        __syncthreads();
+        rot = __builtin_amdgcn_readfirstlane(s_rot);
+    }
+    auto chunk_of = [&](int i) { return i + rot >= NCH ? i + rot - NCH : i + rot; };
+    const uint8_t* pc[PW];
+    const uint8_t* pn[PW];
+    ptrs(chunk_of(0), pc);
+    issue(0, pc);
+    ptrs(chunk_of(1), pn);
+    for (int i = 0; i < NCH; ++i) {
+        const int ch = chunk_of(i), par = i & 1;  // the chunk, its LDS buffer
+        uint4* buf = lds[par];
+        wait_vm(0);
+        if (a.prio)
+            asm volatile("s_setprio 2" ::: "memory");
+        {
+            const uint32_t m4 = vconst(0x0F0F0F0Fu), m2 = vconst(0x33333333u), m1 = vconst(0x55555555u);
+            for (int t = first; t < CS; t += 3) {
+                uint4 u = buf[(t * 2 + 0) * 64 + lane], v = buf[(t * 2 + 1) * 64 + lane];
+                uint32_t Wd[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+                tr8(Wd, m4, m2, m1);
+                buf[(t * 2 + 0) * 64 + lane] = make_uint4(Wd[0], Wd[1], Wd[2], Wd[3]);
+                buf[(t * 2 + 1) * 64 + lane] = make_uint4(Wd[4], Wd[5], Wd[6], Wd[7]);
+            }
+        }
+        barrier_lds();
+        if (a.prio)
+            asm volatile("s_setprio 0" ::: "memory");
+        if (i + 1 < NCH)
+            issue(par ^ 1, pn);
+        ptrs(chunk_of(min(i + 2, NCH - 1)), pn);  // in flight during this chunk's code
+        const uint32_t la = lds0 + (uint32_t)(par * kBuf) + lane * 16;
+        const uint8_t* fn = code + (size_t)ch * a.chunk_stride;
+        asm volatile("s_swappc_b64 s[82:83], %[fn]"
+                     :
+                     : [fn] "s"(fn), "{v9}"(la)
+                     : RSGPU_JW_CALL_CLOBBERS, "s82", "s83", "scc", "memory", RSGPU_J16_ACC_CLOBBERS);
+    }
+    // the combine, once per tile: every wave is past the last chunk's planes,
+    // P's rows replace them, Q1 and Q2 add them to their own
+    barrier_lds();
+    if (role == 0) {
+        uint4* tb = &lds[0][0];
+        [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
+            (
+                [&] {
+                    uint32_t Wd[8];
+                    read_slotw<Ss>(Wd);
+                    tb[(Ss * 2 + 0) * 64 + lane] = make_uint4(Wd[0], Wd[1], Wd[2], Wd[3]);
+                    tb[(Ss * 2 + 1) * 64 + lane] = make_uint4(Wd[4], Wd[5], Wd[6], Wd[7]);
+                }(),
+                ...);
+        }(std::make_integer_sequence<int, 16>{});
+    }
+    barrier_lds();
+    if (role != 0) {
+        const uint32_t la = lds0 + lane * 16;
+        const uint8_t* fn = code + (size_t)NCH * a.chunk_stride;
+        asm volatile("s_swappc_b64 s[82:83], %[fn]"
+                     :
+                     : [fn] "s"(fn), "{v9}"(la)
+                     : RSGPU_JW_CALL_CLOBBERS, "s82", "s83", "scc", "memory", RSGPU_J16_ACC_CLOBBERS);
+        const int half = role - 1;  // rows 16 half .. 16 half + 15 (wide_row0(32, half))
+        JitwStore{}.run<jit::J16, 1, 2>(a, dsts, b, half, 0, lane, off, nullptr);
+    }
+}
+
 // The generated scrub for 16 < e <= 64: k_rs_jitw's accumulation on the
 // matrix's shared program, then the scrub epilogue (scrub_slots)
 template <class W, int TPW, int NV>
@@ -1217,6 +1351,16 @@ hipError_t launch_rs_jitw(const JitArgs& a, long long blocks, hipStream_t st)
         RSGPU_JW_LAUNCH(jit::J10)
     }
 #undef RSGPU_JW_LAUNCH
+    return hipGetLastError();
+}
+
+hipError_t launch_rs_kara(const JitArgs& a, long long blocks, hipStream_t st)
+{
+    if (a.k != 64 || a.rows != 32 || a.dst_stride < 32 || !a.code || a.chunk_stride <= 0 || a.len <= 0 ||
+        a.len % 32 || blocks <= 0 || blocks > (long long)kMaxGridBlocks)
+        return hipErrorInvalidValue;
+    const long long ntile = (a.len + 2047) / 2048;
+    hipLaunchKernelGGL(jitk::k_rs_kara, dim3((unsigned)ntile, (unsigned)blocks), dim3(64 * 3), 0, st, a);
     return hipGetLastError();
 }
 

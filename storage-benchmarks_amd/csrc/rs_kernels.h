@@ -235,6 +235,11 @@ size_t jitw_pass_offset(int k, int e, int p);
 hipError_t launch_jitw_emit(int k, int e, long long blocks, const uint8_t* coef, const int* status,
                             uint8_t* code, hipStream_t st);
 hipError_t launch_rs_jitw(const JitArgs& a, long long blocks, hipStream_t st);
+// The (64, 32) gf_gen_rs_matrix encode through the Karatsuba-split program
+// (jit_prog.h build_karatsuba_code; k_rs_kara): a.code / a.chunk_stride the
+// program, a.k = 64, a.rows = 32, one column tile per workgroup, chunk_rot_ticks
+// and prio as k_rs_jitw.
+hipError_t launch_rs_kara(const JitArgs& a, long long blocks, hipStream_t st);
 // The generated scrub (k_rs_jit_scrub, k_rs_jitw_scrub): the shared program's
 // accumulation exactly as the encode runs it, then the stored parity rows read
 // through j.dsts (never written) and compared in registers.  j.rows = e <= 64

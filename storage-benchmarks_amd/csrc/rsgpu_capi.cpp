@@ -10,6 +10,7 @@
 #include <hsa/hsa_ext_amd.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -103,14 +104,17 @@ hsa_status_t pick_coarse_pool(hsa_amd_memory_pool_t p, void* out)
 constexpr size_t kProgCacheEntries = 64;
 constexpr size_t kProgCacheBytes = 256u << 20;
 
-const rsgpu_ctx::SharedProg* shared_program(rsgpu_ctx* ctx, const uint8_t* coef, int k, int rows, int* rc_out)
+// kara: the Karatsuba-split program of the (64, 32) gf_gen_rs_matrix code
+// (jit_prog.h build_karatsuba_code; k_rs_kara) instead, cached the same way.
+const rsgpu_ctx::SharedProg* shared_program(rsgpu_ctx* ctx, const uint8_t* coef, int k, int rows, int* rc_out,
+                                            bool kara = false)
 {
     *rc_out = RSGPU_OK;
     const bool wide = jitw_layout(rows);
     std::vector<uint8_t> key(9 + (size_t)k * rows);
     std::memcpy(key.data(), &k, 4);
     std::memcpy(key.data() + 4, &rows, 4);
-    key[8] = wide ? 1 : 0;
+    key[8] = kara ? 2 : wide ? 1 : 0;
     std::memcpy(key.data() + 9, coef, (size_t)k * rows);
     for (auto& pr : ctx->progs)
         if (pr.key == key) {
@@ -126,7 +130,13 @@ const rsgpu_ctx::SharedProg* shared_program(rsgpu_ctx* ctx, const uint8_t* coef,
     int stride = 0;
     std::vector<uint8_t> code;
     std::vector<std::pair<size_t, int>> passes;
-    if (wide) {
+    if (kara) {
+        jit::KaraProgram kp;
+        if (k != 64 || rows != 32 || !jit::build_karatsuba_code(coef, &kp))
+            return err(RSGPU_ERR_UNSUPPORTED, "Karatsuba program: not the (64, 32) gf_gen_rs_matrix code");
+        code = std::move(kp.code);
+        stride = kp.chunk_stride;
+    } else if (wide) {
         code = jit::build_matrix_code_wide_passes(coef, k, rows, &passes);
         if (code.empty())
             return err(RSGPU_ERR_UNSUPPORTED, "shared program: rows exceed the layout");
@@ -349,14 +359,79 @@ size_t dot_table_bytes(int k, int rows)
                     (size_t)k * rows_pad_for(rows) * (sizeof(uint4) + sizeof(uint32_t)));
 }
 
+// AUTO's threshold for the Karatsuba-split (64, 32) encode, in (tile, block)
+// pairs per call (profiles/karatsuba3/): the program runs 20 % fewer
+// VALU instructions at a lower issue rate, which pays only where the compiled
+// kernel runs long enough to sit at the power limit.  C3 (489 x 1024 = 500736
+// pairs, a 21 ms encode): step -0.49 ms in every one of 12 ABBA pairs; C4's
+// batch (16 x 16384 = 262144, 10.7 ms): level; from 65536 pairs down the
+// compiled kernel is 4-30 % faster.
+constexpr long long kKaraMinWork = 480000;
+// k_rs_kara's chunk rotation period: a chunk is 4 sources of 16 rows per wave
+// against k_rs_jitw's 6 (jitw_rot_ticks: 600)
+constexpr int kKaraRotTicks = 400;
+
+// The (64, 32) gf_gen_rs_matrix encode through the Karatsuba-split program.
+// *unavailable: the program cannot be built in this context (nothing was
+// launched, no error is left behind); the context remembers it
+// (kara_state) and the caller goes on with the kernels AUTO has otherwise.
+int karatsuba_launch(rsgpu_ctx* ctx, long long len, size_t pitch, size_t blocks, const unsigned char* d_src,
+                     unsigned char* d_parity, bool* unavailable)
+{
+    const int k = 64, e = 32;
+    *unavailable = false;
+    const std::vector<uint8_t> c = parity_matrix(k, e, nullptr);
+    const size_t src_ptr_bytes = align_up(sizeof(void*) * (size_t)k * blocks, 256);
+    const size_t dst_ptr_bytes = align_up(sizeof(void*) * (size_t)e * blocks, 256);
+    int rc = ensure_scratch(ctx, src_ptr_bytes + dst_ptr_bytes);
+    if (rc)
+        return rc;
+    const std::string err_before = ctx->err;
+    const rsgpu_ctx::SharedProg* pg = shared_program(ctx, c.data(), k, e, &rc, true);
+    if (!pg && rc == RSGPU_ERR_UNSUPPORTED) {
+        ctx->kara_state = -1;
+        ctx->err = err_before;
+        *unavailable = true;
+        return RSGPU_OK;
+    }
+    if (!pg)
+        return rc;
+    char* d = (char*)ctx->scratch.p;
+    RS_HIP(ctx, launch_row_ptrs(d_src, (long long)pitch, k, (long long)blocks, (const uint8_t**)d, ctx->stream));
+    RS_HIP(ctx, launch_row_ptrs(d_parity, (long long)pitch, e, (long long)blocks,
+                                (const uint8_t**)(d + src_ptr_bytes), ctx->stream));
+    JitArgs j = jit_args((const uint8_t* const*)d, (uint8_t* const*)(d + src_ptr_bytes), pg->code, pg->chunk_stride,
+                         0, k, e, e, len, nullptr);
+    j.chunk_rot_ticks = ctx->jitw_rot >= 0 ? ctx->jitw_rot : kKaraRotTicks;
+    j.prio = ctx->jitw_prio;
+    KTimer kt(ctx, "k_rs_jit(encode)", blocks);
+    RS_HIP(ctx, launch_rs_kara(j, (long long)blocks, ctx->stream));
+    return RSGPU_OK;
+}
+
 // rsgpu_encode_blocks on at most kMaxGridBlocks blocks, e > 0 and len > 0
 int encode_slice(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks, const unsigned char* d_src,
                  unsigned char* d_parity, const unsigned char* coef)
 {
     const bool aligned = ptrs_aligned(pitch, d_src, d_parity);
+    // The Karatsuba-split generated program of the (64, 32) code (k_rs_kara):
+    // KARATSUBA's path wherever it applies, AUTO's from kKaraMinWork (tile,
+    // block) pairs; everywhere else KARATSUBA chooses as AUTO.
+    const bool kara_wanted = ctx->encode_kernel == RSGPU_ENCODE_KARATSUBA ||
+                             (ctx->encode_kernel == RSGPU_ENCODE_AUTO &&
+                              (long long)(tiles(len) * blocks) >=
+                                  (ctx->kara_min_work >= 0 ? ctx->kara_min_work : kKaraMinWork));
+    if (kara_wanted && ctx->kara_state >= 0 && !coef && k == 64 && e == 32 && aligned && len % 32 == 0 &&
+        jit_probe(ctx) == 1) {
+        bool unavailable;
+        const int rc = karatsuba_launch(ctx, (long long)len, pitch, blocks, d_src, d_parity, &unavailable);
+        if (!unavailable)
+            return rc;
+    }
     // Fast paths: the gf_gen_rs_matrix code with compile-time coefficients,
     // bit-sliced (len % 32 == 0) or nibble-table (len % 4 == 0).
-    const bool compiled_ok = ctx->encode_kernel == RSGPU_ENCODE_AUTO || ctx->encode_kernel == RSGPU_ENCODE_COMPILED;
+    const bool compiled_ok = ctx->encode_kernel == RSGPU_ENCODE_AUTO || ctx->encode_kernel == RSGPU_ENCODE_COMPILED ||
+                             ctx->encode_kernel == RSGPU_ENCODE_KARATSUBA;
     if (compiled_ok && !coef && aligned && len % 32 == 0 && rs_bitsliced_split_available(k, e) &&
         (long long)(tiles(len) * blocks) < kTcSplitMaxWork) {
         KTimer kt(ctx, "k_rs_bs_split(encode)", blocks);
@@ -1026,7 +1101,7 @@ int rsgpu_encode_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
 
 int rsgpu_set_encode_kernel(rsgpu_ctx* ctx, int kernel)
 {
-    if (!ctx || kernel < RSGPU_ENCODE_AUTO || kernel > RSGPU_ENCODE_THREADED)
+    if (!ctx || kernel < RSGPU_ENCODE_AUTO || kernel > RSGPU_ENCODE_KARATSUBA)
         return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_encode_kernel: unknown kernel");
     ctx->encode_kernel = kernel;
     return RSGPU_OK;

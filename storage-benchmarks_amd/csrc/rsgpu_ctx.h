@@ -26,6 +26,8 @@ struct rsgpu_ctx {
     int tc_state = 0;
     int decode_kernel = RSGPU_DECODE_AUTO;
     int jitw_tpw = 0;  // k_rs_jitw column tiles per workgroup (0: by geometry)
+    long long kara_min_work = -1;  // AUTO's threshold for k_rs_kara, (tile, block) pairs (-1: the library's)
+    int kara_state = 0;  // -1: the Karatsuba program cannot be built here, its callers choose as without it
     int jitw_prefetch = -1;  // k_rs_jitw code prefetch into L2 (-1: by geometry)
     int jitw_rot = -1;       // k_rs_jitw chunk rotation period, ticks (-1: by geometry, 0: off)
     // wave priority of k_rs_bs / k_rs_jitw / k_rs_jit from a chunk's transposes

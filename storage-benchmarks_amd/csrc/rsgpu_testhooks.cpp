@@ -284,6 +284,53 @@ long long rsgpu_internal_jitw_matrix_code(int k, int e, const unsigned char* coe
     return (long long)code.size();
 }
 
+// Test hook (not in include/rsgpu.h): the Karatsuba-split program of the
+// (64, 32) code with parity matrix coef [32][64] (jit_prog.h
+// build_karatsuba_code), as shared_program builds it: the code (role w, chunk
+// ch at (w 9 + ch) *chunk_stride), and the role matrices cP / cQ1 / cQ2
+// [16][32], rho [32] and sigma [16] into mats (1584 bytes, in that order).
+// Returns the code bytes, or -1 (coef is not the gf_gen_rs_matrix code).
+long long rsgpu_internal_jit_karatsuba_code(const unsigned char* coef, unsigned char* out, size_t out_bytes,
+                                            int* chunk_stride, unsigned char* mats)
+{
+    jit::KaraProgram kp;
+    if (!coef || !chunk_stride || !jit::build_karatsuba_code(coef, &kp))
+        return -1;
+    *chunk_stride = kp.chunk_stride;
+    if (mats) {
+        std::memcpy(mats, kp.cP, 512);
+        std::memcpy(mats + 512, kp.cQ1, 512);
+        std::memcpy(mats + 1024, kp.cQ2, 512);
+        std::memcpy(mats + 1536, kp.rho, 32);
+        std::memcpy(mats + 1568, kp.sigma, 16);
+    }
+    if (out && out_bytes >= kp.code.size())
+        std::memcpy(out, kp.code.data(), kp.code.size());
+    return (long long)kp.code.size();
+}
+
+// Test / A-B hook (not part of include/rsgpu.h): the (tile, block) pairs from
+// which AUTO encodes (64, 32) through the Karatsuba program (-1 = the
+// library's threshold).
+int rsgpu_internal_set_kara_min_work(rsgpu_ctx* ctx, long long pairs)
+{
+    if (!ctx || pairs < -1)
+        return RSGPU_ERR_ARG;
+    ctx->kara_min_work = pairs;
+    return RSGPU_OK;
+}
+
+// Test hook (not part of include/rsgpu.h): mark the Karatsuba program as
+// not buildable in this context (-1), as a failed build leaves it, or clear
+// that (0).
+int rsgpu_internal_set_kara_state(rsgpu_ctx* ctx, int state)
+{
+    if (!ctx || (state != 0 && state != -1))
+        return RSGPU_ERR_ARG;
+    ctx->kara_state = state;
+    return RSGPU_OK;
+}
+
 // Test hook (not part of include/rsgpu.h): the DEVICE emitter k_jitw_emit
 // for `blocks` blocks of decode rows coef [blocks][e][k] (host memory), its
 // code copied back into out (blocks x the bytes rsgpu_internal_jitw_emit

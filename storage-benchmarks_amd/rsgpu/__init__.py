@@ -56,7 +56,7 @@ MAX_SOURCES = 250  # TEST_SOURCES, isa.cpp:25-27
 DECODE_KERNELS = {"auto": 0, "one_matrix": 1, "general": 3, "generated": 4,
                   "fused": 2}  # deprecated alias of one_matrix (rsgpu.h RSGPU_DECODE_FUSED)
 # rsgpu_set_encode_kernel choices (include/rsgpu.h)
-ENCODE_KERNELS = {"auto": 0, "compiled": 1, "generated": 2, "threaded": 3}
+ENCODE_KERNELS = {"auto": 0, "compiled": 1, "generated": 2, "threaded": 3, "karatsuba": 4}
 # rsgpu_set_scrub_kernel choices, rsgpu_scrub_blocks' flag and report
 # (include/rsgpu.h rsgpu_scrub_report)
 SCRUB_KERNELS = {"auto": 0, "fused": 1, "two_pass": 2, "generated": 3}
@@ -327,7 +327,8 @@ class Context:
 
     def set_encode_kernel(self, kernel: str) -> None:
         """Encode kernel of encode_blocks / ec_encode_data: auto | compiled |
-        generated | threaded (include/rsgpu.h rsgpu_set_encode_kernel)."""
+        generated | threaded | karatsuba (include/rsgpu.h
+        rsgpu_set_encode_kernel)."""
         self.check(lib().rsgpu_set_encode_kernel(self._h, ENCODE_KERNELS[kernel]),
                    "rsgpu_set_encode_kernel")
 

@@ -15,7 +15,9 @@ differences.
 
 `--knob` names a librsgpu_testhooks.so setter (ctx, int); `--encode-kernel`
 / `--decode-kernel` values switch the public kernel choice instead
-(--knob encode_kernel --values compiled,generated).
+(--knob encode_kernel --values compiled,generated).  A value written
+LABEL=VALUE is reported under LABEL, so one value can run against itself
+(--values A=compiled,B=compiled: the pair-to-pair spread of the step).
 """
 from __future__ import annotations
 
@@ -54,11 +56,13 @@ def main() -> int:
     ctx.set_torch_stream()
     enc = rsgpu.GpuEncoder(k, L, e, blocks=B, seed=1, ctx=ctx)
     dec = rsgpu.GpuDecoder(k, L, e, blocks=B, seed=1, ctx=ctx)
-    vals = args.values.split(",")
+    setting = dict(v.split("=", 1) if "=" in v else (v, v) for v in args.values.split(","))
+    vals = list(setting)
     if args.encode_kernel:
         ctx.set_encode_kernel(args.encode_kernel)
 
     def apply(v):
+        v = setting[v]
         if args.knob == "encode_kernel":
             ctx.set_encode_kernel(v)
         elif args.knob == "decode_kernel":
