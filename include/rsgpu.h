@@ -656,7 +656,8 @@ int rsgpu_set_rebuild_kernel(rsgpu_ctx *ctx, int kernel);
  * are the worst case, every column taking the cooperative path: two whole
  * rows bad per block 175.6 ms, 5 x the scrub.  The form fused into the
  * encode, compiled or generated, is rsgpu_set_locate_kernel's FUSED, below.  Not built:
- * e > 64; u > 8; per-column decoding of blocks that end DAMAGED. */
+ * e > 64; u > 8.  Blocks that end DAMAGED with at most two damaged rows in any
+ * one byte column: rsgpu_correct_blocks, below. */
 #define RSGPU_SCRUB_ROWS 4        /* the damage lies in exactly the 2..u listed rows */
 #define RSGPU_LOCATE_MAX_ROWS 8
 int rsgpu_locate_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
@@ -795,6 +796,106 @@ typedef struct rsgpu_repair_report {
 int rsgpu_repair_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                         unsigned char *d_src, unsigned char *d_parity,
                         const unsigned char *coef, int mode, rsgpu_repair_report *d_report);
+
+/* ---- correction per byte column of up to two damaged rows ------------------ */
+
+/* rsgpu_repair_blocks in RSGPU_REPAIR_COLUMNS mode corrects a byte column that
+ * one row explains; rsgpu_locate_blocks names several rows, but only from the
+ * span of all the block's columns and at most min(8, e - 1) of them.  Damage
+ * scattered over many rows of a long stripe (bad sectors, torn writes), no
+ * column holding more than two bad rows, ends there as PARTIAL or DAMAGED.
+ * This call decodes every byte column on its own, with up to t unknown
+ * positions.  With s the syndrome column and h_r as rsgpu_locate_blocks
+ * defines them (column r of the matrix for a data row, the unit vector of p
+ * for parity row k + p), per bad byte column i:
+ *
+ *   E1 = { r : s = x h_r for some x != 0 }
+ *   E2 = { {a, b}, a != b : s = x h_a + y h_b with x != 0 and y != 0 }
+ *
+ *   |E1| = 1                  corrected in that row, exactly as
+ *                             RSGPU_REPAIR_COLUMNS does it
+ *   else, when t = 2, E1 is   corrected in both rows: a data row r gets
+ *   empty and |E2| = 1        src[r][i] ^= x_r, a parity row k + p gets
+ *                             parity[p][i] ^= x_{k+p}; afterwards all syndromes
+ *                             of the column are zero
+ *   otherwise                 the column stays byte for byte as it was
+ *
+ * The verdict is that of the definition, per column, for any matrix the call
+ * takes: the search covers all (k + e)(k + e - 1) / 2 pairs, and two matching
+ * pairs leave the column alone.  With t = 1 the rows written and the report
+ * equal those of rsgpu_repair_blocks with RSGPU_REPAIR_COLUMNS
+ * (corrected_columns = its repaired_columns, two_row_columns = 0); with t = 2
+ * every column COLUMNS corrects is corrected identically, and columns it
+ * leaves may be corrected in two rows.  As there, a correction is the
+ * explanation with the fewest rows, not a proof: three or more damaged rows
+ * in one column can imitate two (or one) and are then "corrected" into a
+ * consistent but wrong column.  A matrix whose every e columns of [C | I] are
+ * independent (gf_gen_cauchy1_matrix always) has distance e + 1: with e >= 5
+ * three damaged rows of a column never look like two or fewer, and such a
+ * column is left alone.
+ *
+ * Report per block, overwritten by every call: status CLEAN, REPAIRED (every
+ * bad column corrected), DAMAGED (none corrected) or PARTIAL; `row` is the
+ * common row when every corrected column was a one-row correction in the
+ * same row, otherwise -1.  Never written: bytes in [len, pitch), any byte of
+ * a column that is not bad, any byte of a row that the column's verdict does
+ * not name.
+ *
+ * Layout, `coef` and accepted geometries as rsgpu_repair_blocks: any len, any
+ * pitch >= len, any alignment, a custom e x k matrix or NULL.  d_report
+ * [blocks] is DEVICE memory, 8-byte aligned.  t is 1 or 2, anything else
+ * RSGPU_ERR_ARG.  The matrix must be locatable (rsgpu_scrub_locatable); t = 1
+ * needs e >= 3 (COLUMNS' rule); t = 2 needs 5 <= e <= 64: correcting two
+ * errors per column while still detecting three takes distance e + 1 >= 2 * 2
+ * + 2 = 6, and a lane of the wave holds one syndrome, as in the locate.
+ * Otherwise RSGPU_ERR_UNSUPPORTED.  On either error, on null rows or a null or
+ * misaligned report, nothing is enqueued and the report is untouched.  e == 0
+ * or len == 0: every block CLEAN.  Enqueued on the context's stream, no
+ * synchronisation and no host decision between finding and writing; more
+ * than 65535 blocks run as consecutive slices.
+ *
+ * The two-pass form only: the encode of a slice into the context's scratch
+ * (the TWO_PASS scrub's slices, at most 128 MiB of parity), then
+ * k_correct_compare, which is k_repair_compare -- a thread ORs the syndromes
+ * of 16 columns per 16-byte load, a clean group costs nothing more, a bad
+ * column first gets the one-row test -- whose waves take the columns that
+ * test leaves one at a time: lane p holds s_p, two parity rows are read off
+ * the non-zero syndromes, a data row with a parity row takes one lane per data
+ * row, and the k (k - 1) / 2 pairs of data rows are solved from syndromes 0
+ * and 1 (the determinant is non-zero for a locatable matrix) and rejected at
+ * syndrome 2, 255 of 256 of them, with four reads of an exp table at sums of
+ * logarithms laid out per row before the search.  The tables
+ * lie in LDS, 4164 bytes per wave, filled by a wave when it meets its first
+ * such column.
+ * Cost, measured at (64, 32), 1 MB rows, 1024 blocks on one MI355X, one
+ * process, medians of 24 runs (profiles/correct): clean blocks
+ * with t = 2 34.60 ms, COLUMNS under the TWO_PASS scrub kernel 34.62 ms (ratio
+ * over 24 mirrored pairs 0.958 - 1.009, mean 0.999, stdev 0.010: inside the
+ * pair's run-to-run spread; the compare kernels 11.82 and 11.80 ms).  One row
+ * per block bad in 1 % of the columns: 172.8 ms with t = 2, 173.0 ms with
+ * t = 1, all of it COLUMNS' own walk of bad columns, 13.5 ns per bad column
+ * over the device.  A column that goes to the pair search costs 10.1 ns over
+ * the device, whichever pair explains it: two rows bad in the same 1 % of
+ * the columns 276.8 ms, 12 rows with two per column 276.8 ms.  Blocks damaged
+ * in most of their columns are the worst case: two whole rows bad 7575 ms.
+ * rsgpu_locate_blocks followed by rsgpu_rebuild_blocks took 62.4, 64.5 and
+ * 189.1 ms on the one-row, two-row and whole-row damage.  Advice: scrub
+ * first; where the damage lies in whole rows, locate and rebuild; take this
+ * call for the blocks they give up as DAMAGED, whose damage is scattered.
+ * Not built: a form fused into the compiled or generated encode
+ * (rsgpu_set_scrub_kernel has no influence on this call); t > 2; e > 64;
+ * host-resident blocks. */
+typedef struct rsgpu_correct_report {
+    unsigned long long bad_columns;       /* before the call */
+    unsigned long long corrected_columns; /* columns written, one- and two-row together */
+    unsigned long long two_row_columns;   /* of those, columns corrected in two rows */
+    int status;                           /* RSGPU_REPAIR_CLEAN / _REPAIRED / _PARTIAL / _DAMAGED */
+    int row; /* the one row every corrected column lay in, each a one-row correction; else -1 */
+} rsgpu_correct_report;                   /* 32 bytes */
+
+int rsgpu_correct_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                         unsigned char *d_src, unsigned char *d_parity,
+                         const unsigned char *coef, int t, rsgpu_correct_report *d_report);
 
 /* ---- partial-stripe update: parity follows a few overwritten rows -------- */
 

@@ -547,4 +547,33 @@ hipError_t launch_rs_bitsliced_locate(int k, int e, const uint8_t* src, const ui
                                       long long len, long long blocks, ScrubFold* fold, uint8_t* cand,
                                       size_t cand_stride, int u, hipStream_t st);
 
+// Correction per byte column of up to t rows (rsgpu_correct_blocks,
+// rs_correct.hip): k_repair_compare in its COLUMNS mode whose waves, with t ==
+// 2, search the row pairs for every bad column no single row explains.  A
+// block's 32-byte report holds its fold while a call is in flight (zeroed by
+// one memset, as the repair's):
+//   bytes 0-7    bad columns (atomicAdd)
+//   bytes 8-15   corrected columns, one- and two-row together (atomicAdd)
+//   bytes 16-23  of those, the columns corrected in two rows (atomicAdd)
+//   bytes 24-27  max of row + 1          over the corrected columns, a two-row
+//   bytes 28-31  max of kScrubBias - row   correction counting as kScrubNoRow
+// k_correct_finalise turns it into the report.
+struct CorrectFold {
+    unsigned long long bad, rep, two;
+    unsigned hi1, lo1;
+};
+struct CorrectCmpArgs {
+    const uint8_t* calc;  // [B][e] rows: the parity of the sources, recomputed
+    uint8_t* src;         // [B][k] rows
+    uint8_t* par;         // [B][e] rows: the stored parity
+    long long pitch, len, blocks;
+    int k, e;
+    const uint8_t* rowtab;  // as ScrubCmpArgs'
+    const uint8_t* coef;
+    CorrectFold* fold;  // [B]
+    int t;              // 1: e >= 3; 2: 5 <= e <= 64
+};
+hipError_t launch_correct_compare(const CorrectCmpArgs& a, hipStream_t st);
+hipError_t launch_correct_finalise(void* report, long long blocks, hipStream_t st);
+
 }  // namespace rsgpu

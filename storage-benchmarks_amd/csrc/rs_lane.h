@@ -1,5 +1,5 @@
 // rs_lane.h -- what the kernels of the scrub family share (rs_kernels.hip's
-// scrub and repair, rs_update.hip, rs_degraded.hip, rs_rebuild.hip, rs_locate.hip): the lane's building
+// scrub and repair, rs_update.hip, rs_degraded.hip, rs_rebuild.hip, rs_locate.hip, rs_correct.hip): the lane's building
 // blocks (v_perm multiply, three-way XOR, the 3-3-2 selector split of a dword
 // and the table multiply on it, a column of one row), the fold of a wave's bad
 // columns into a block's report, the verdict on a finished fold, and the
@@ -92,8 +92,8 @@ __device__ __forceinline__ void col_store(uint8_t* row, long long c, const Col<W
 // must equal c[p][r] x; a column whose only non-zero syndrome is s_p0 is
 // parity row k + p0.  nz: the column's non-zero syndromes (>= 1), p0: the
 // last of them, syn(p): syndrome p of the column.  coef: the e x k matrix.
-// One copy for k_scrub_compare, k_repair_compare (rs_kernels.hip) and the
-// generated scrub's cold path (rs_jit.hip).
+// One copy for k_scrub_compare, k_repair_compare (rs_kernels.hip), the
+// generated scrub's cold path (rs_jit.hip) and k_correct_compare (rs_correct.hip).
 template <class Syn>
 __host__ __device__ __forceinline__ int scrub_locate_row(int k, int e, const uint8_t* rowtab, const uint8_t* coef,
                                                          const GfTables& gf, uint8_t s0, uint8_t s1, int nz, int p0,

@@ -1,7 +1,8 @@
 // rs_span.h -- the wave-cooperative span arithmetic of the locate
 // (rsgpu_locate_blocks): an echelon basis of at most RSGPU_LOCATE_MAX_ROWS
 // vectors of GF(2^8)^64 in LDS, a lane per coordinate.  Shared by
-// rs_locate.hip (k_locate_span, k_locate_finish), rs_bitsliced.hip
+// rs_locate.hip (k_locate_span, k_locate_finish; rs_correct.hip takes the
+// lane helpers), rs_bitsliced.hip
 // (k_rs_bs_locate) and rs_jit.hip (k_rs_jit_locate, k_rs_jitw_locate): one copy of the basis, the slot format, the reduction and
 // the append.  The merge of a workgroup's bases into its slot (span_publish) is
 // k_rs_bs_locate's; k_locate_span has the same steps written out, which keeps
@@ -42,6 +43,12 @@ __device__ __forceinline__ uint8_t lane_byte(uint8_t v, int l)
 __device__ __forceinline__ uint8_t loc_mul(const GfTables& gf, uint8_t a, uint8_t b)
 {
     return a && b ? gf.exp[gf.log[a] + gf.log[b]] : 0;
+}
+
+// a / b, b != 0
+__device__ __forceinline__ uint8_t loc_div(const GfTables& gf, uint8_t a, uint8_t b)
+{
+    return a ? gf.exp[gf.log[a] + 255 - gf.log[b]] : 0;
 }
 
 // the tables `from` (device memory) into the workgroup's LDS copy

@@ -1,8 +1,9 @@
 // rsgpu_scrub.cpp -- the scrub family of the C ABI (include/rsgpu.h): parity
 // scrub, repair in place, partial-stripe update, degraded scrub, rebuild in
-// place and the locate of several rows.  Argument checks and launch sequences;
-// the kernels are rs_kernels.hip (two-pass compare, finalise), rs_bitsliced.hip
-// (fused), rs_update.hip, rs_degraded.hip, rs_rebuild.hip, rs_locate.hip.  The
+// place, the locate of several rows and the correction per column.  Argument
+// checks and launch sequences; the kernels are rs_kernels.hip (two-pass
+// compare, finalise), rs_bitsliced.hip (fused), rs_update.hip, rs_degraded.hip,
+// rs_rebuild.hip, rs_locate.hip, rs_correct.hip.  The
 // encode and the decode are rsgpu_capi.cpp and rsgpu_decode.cpp.
 #include <hip/hip_runtime.h>
 
@@ -576,6 +577,52 @@ int rsgpu_repair_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
                                                    fold + b0, kRepairGated, ctx->stream));
         }
     }
+    return RSGPU_OK;
+}
+
+int rsgpu_correct_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
+                         unsigned char* d_src, unsigned char* d_parity, const unsigned char* coef, int t,
+                         rsgpu_correct_report* d_report)
+{
+    int rc = check_geom(ctx, k, e, len, pitch, blocks);
+    if (rc)
+        return rc;
+    if (!d_report || (uintptr_t)d_report % 8 != 0 || (t != 1 && t != 2))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_correct_blocks: bad report pointer or t");
+    const bool work = e > 0 && len > 0;
+    if (work && (!d_src || !d_parity))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_correct_blocks: null rows");
+    Locator loc;
+    if (e > 0) {  // e == 0: no parity, nothing can be bad
+        rc = locator(ctx, k, e, coef, "rsgpu_correct_blocks: needs a locatable matrix (rsgpu_scrub_locatable)", loc);
+        if (rc)
+            return rc;
+        if (t == 1 && e < 3)
+            return fail(ctx, RSGPU_ERR_UNSUPPORTED, "rsgpu_correct_blocks: t == 1 needs e >= 3");
+        if (t == 2 && (e < 5 || e > 64))
+            return fail(ctx, RSGPU_ERR_UNSUPPORTED, "rsgpu_correct_blocks: t == 2 needs 5 <= e <= 64");
+    }
+    CorrectFold* fold = reinterpret_cast<CorrectFold*>(d_report);
+    RS_HIP(ctx, hipMemsetAsync(d_report, 0, blocks * sizeof(rsgpu_correct_report), ctx->stream));
+    // the two-pass form only: per slice of the scratch the encode, then the
+    // correcting compare while the slice's computed parity is still there
+    auto compare = [&](size_t b0, size_t nb, const uint8_t* calc) -> int {
+        CorrectCmpArgs a =
+            cmp_args<CorrectCmpArgs>(ctx, k, e, len, pitch, nb, calc, d_parity + b0 * e * pitch, fold + b0);
+        a.src = d_src + b0 * k * pitch;
+        a.t = t;
+        KTimer kt(ctx, "k_correct_compare", nb);
+        RS_HIP(ctx, launch_correct_compare(a, ctx->stream));
+        return RSGPU_OK;
+    };
+    // block index in grid.y: larger batches as consecutive slices
+    for (size_t b0 = 0; work && b0 < blocks; b0 += kMaxGridBlocks) {
+        rc = two_pass(ctx, k, e, len, pitch, b0, std::min(kMaxGridBlocks, blocks - b0), d_src, coef, &loc, compare);
+        if (rc)
+            return rc;
+    }
+    KTimer kt(ctx, "k_correct_finalise", blocks);
+    RS_HIP(ctx, launch_correct_finalise(d_report, (long long)blocks, ctx->stream));
     return RSGPU_OK;
 }
 

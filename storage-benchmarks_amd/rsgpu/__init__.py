@@ -40,7 +40,7 @@ __all__ = [
     "REPAIR_COLUMNS", "REPAIR_CLEAN", "REPAIR_REPAIRED", "REPAIR_PARTIAL", "REPAIR_DAMAGED",
     "UPDATE_NONE", "UPDATE_DELTA", "LOST_NONE", "SCRUB_UNCHECKED", "SCRUB_BAD_MATRIX",
     "SCRUB_BAD_LIST", "REBUILD_CHECK", "REBUILD_MAX_LOST", "REBUILD_KERNELS", "SCRUB_ROWS",
-    "LOCATE_MAX_ROWS", "LOCATE_KERNELS",
+    "LOCATE_MAX_ROWS", "LOCATE_KERNELS", "CORRECT_REPORT_DTYPE",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -70,6 +70,10 @@ REPAIR_MODES = {"one_row": REPAIR_ONE_ROW, "columns": REPAIR_COLUMNS}
 REPAIR_CLEAN, REPAIR_REPAIRED, REPAIR_PARTIAL, REPAIR_DAMAGED = 0, 1, 2, 3
 REPAIR_REPORT_DTYPE = np.dtype([("bad_columns", "<u8"), ("repaired_columns", "<u8"),
                                 ("status", "<i4"), ("row", "<i4")])
+# rsgpu_correct_blocks' report (include/rsgpu.h rsgpu_correct_report); the
+# statuses are the repair's
+CORRECT_REPORT_DTYPE = np.dtype([("bad_columns", "<u8"), ("corrected_columns", "<u8"),
+                                 ("two_row_columns", "<u8"), ("status", "<i4"), ("row", "<i4")])
 # rsgpu_update_blocks' list padding and flag (include/rsgpu.h)
 UPDATE_NONE = 255
 UPDATE_DELTA = 1
@@ -144,6 +148,7 @@ _SIGS = {
                                        vp]),
     "rsgpu_locate_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp, vp]),
     "rsgpu_repair_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp]),
+    "rsgpu_correct_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, vp, vp, vp, C.c_int, vp]),
     "rsgpu_set_scrub_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_set_rebuild_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_set_locate_kernel": (C.c_int, [vp, C.c_int]),
@@ -542,6 +547,18 @@ class Context:
                                              _ptr(d_par), _ptr(coef), REPAIR_MODES[mode],
                                              _ptr(d_report)), "rsgpu_repair_blocks")
 
+    def correct_blocks(self, k, e, length, pitch, blocks, d_src, d_par, d_report, coef=None,
+                       t: int = 2) -> None:
+        """Correction per byte column of up to t damaged rows, in place
+        (include/rsgpu.h rsgpu_correct_blocks): t is 1 (repair_blocks' columns
+        mode) or 2 (needs 5 <= e <= 64); d_report is device memory of blocks x
+        32 bytes, 8-byte aligned, read back as CORRECT_REPORT_DTYPE.  Enqueued
+        on the context's stream."""
+        coef = _coef(coef)
+        self.check(lib().rsgpu_correct_blocks(self._h, k, e, length, pitch, blocks, _ptr(d_src),
+                                              _ptr(d_par), _ptr(coef), t, _ptr(d_report)),
+                   "rsgpu_correct_blocks")
+
     def update_blocks(self, k, e, length, pitch, blocks, u, d_cols, d_upd, d_src, d_par, d_status,
                       coef=None, delta: bool = False) -> None:
         """Partial-stripe update (include/rsgpu.h rsgpu_update_blocks): the
@@ -723,6 +740,17 @@ class GpuEncoder:
         self.ctx.repair_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, rep,
                                coef=self.coef, mode=mode)
         return self._read(rep, REPAIR_REPORT_DTYPE)
+
+    def correct(self, t: int = 2) -> np.ndarray:
+        """Corrects every byte column of this encoder's blocks that one row
+        or, with t = 2, one pair of rows explains, in place (include/rsgpu.h
+        rsgpu_correct_blocks); the per-block reports as a structured array
+        (CORRECT_REPORT_DTYPE).  Synchronises (the reports are copied to the
+        host)."""
+        rep = self._report(CORRECT_REPORT_DTYPE)
+        self.ctx.correct_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, rep,
+                                coef=self.coef, t=t)
+        return self._read(rep, CORRECT_REPORT_DTYPE)
 
     def update(self, cols, rows, delta: bool = False) -> np.ndarray:
         """Overwrites source rows of this encoder's blocks and brings the

@@ -1,0 +1,164 @@
+#!/usr/bin/env python3
+"""The measurement of the correction per column (profiles/correct/README.md):
+rsgpu_correct_blocks against rsgpu_repair_blocks in COLUMNS mode under the
+TWO_PASS scrub kernel on the same blocks, clean and with four kinds of damage,
+and the TWO_PASS locate followed by the rebuild on three of them, at one shape,
+in one process on the same buffers.
+
+Kinds: `columns_clean` (rsgpu_repair_blocks, COLUMNS, TWO_PASS) and
+`correct_clean` (t = 2) on consistent blocks; `correct1_one` and `correct_one`
+(t = 1 and t = 2; one data row per block, b mod k, bad in 1 % of the byte
+columns); `correct_two` (a second data row bad in the same columns);
+`correct_whole` (two whole data rows per block bad: every column takes the
+pair search); `correct_scattered` (12 data rows per block, each pair of them
+bad in a sixth of those 1 % of the columns: at most two rows per column);
+`heal_one`, `heal_two`, `heal_whole`: rsgpu_locate_blocks (TWO_PASS) and
+rsgpu_rebuild_blocks of its lists on the damage of the first three.  Damage is
+XORed into the rows before every run, outside the timed part; every kind
+brings the rows back, which an untimed, checked run of each kind and a scrub at
+the end confirm.  Then `rounds` mirrored rounds, every kind twice per round.  A
+run's time is the sum of its kernels' HIP-event times from rsgpu_timing_read.
+
+Besides the statistics per kind the summary holds correct_clean /
+columns_clean over the mirrored pairs (same round, same half), to be read
+against the two kinds' own run-to-run spread.
+
+    python tools/correct_measure.py out.json [--k 64 --e 32 --len 1000000 --blocks 1024 --rounds 12]
+                                             [--skip kind,kind]
+"""
+import sys
+
+import numpy as np
+import torch
+
+import measure_lib as ml  # puts the engine's directory on the path
+import rsgpu  # noqa: E402
+
+DT = rsgpu.CORRECT_REPORT_DTYPE
+U = rsgpu.LOCATE_MAX_ROWS
+SCATTER = 12
+
+
+def main():
+    ap = ml.shape_parser()
+    ap.add_argument("--skip", default="", help="kinds to leave out, comma separated")
+    a = ap.parse_args()
+    k, e, L, B = a.k, a.e, a.len, a.blocks
+    assert k >= SCATTER and 5 <= e <= 64
+    ctx, enc = ml.setup(a)
+    ctx.set_scrub_kernel("two_pass")
+    ctx.set_locate_kernel("two_pass")
+    dev, pitch = enc.src.device, enc.pitch
+    crep, rrep, srep = ml.reports(enc, DT), ml.reports(enc, rsgpu.REPAIR_REPORT_DTYPE), ml.reports(enc)
+    srep2 = ml.reports(enc)
+    lists = torch.empty(B * U, dtype=torch.uint8, device=dev)
+    vs = enc.src.view(B, k, pitch)
+    rng = np.random.default_rng(9)
+    blk = torch.arange(B, device=dev)
+    r1 = torch.arange(B, device=dev) % k
+    r2 = (r1 + 1 + torch.from_numpy(rng.integers(0, k - 1, B)).to(dev)) % k  # != r1
+    ncols = max(SCATTER // 2, L // 100 // (SCATTER // 2) * (SCATTER // 2))
+    c1 = torch.from_numpy(np.sort(rng.choice(L, ncols, replace=False))).to(dev)
+    x1 = torch.from_numpy(rng.integers(1, 256, (B, ncols), dtype=np.uint8)).to(dev)
+    x2 = torch.from_numpy(rng.integers(1, 256, (B, ncols), dtype=np.uint8)).to(dev)
+    w1 = torch.from_numpy(rng.integers(1, 256, L, dtype=np.uint8)).to(dev)
+    w2 = torch.from_numpy(rng.integers(1, 256, L, dtype=np.uint8)).to(dev)
+    # scattered: rows r1 + j (k // 12), j < 12, distinct; the columns in six
+    # parts, part m damaged in rows 2 m and 2 m + 1
+    part = ncols // (SCATTER // 2)
+    srows = [(r1 + j * (k // SCATTER)) % k for j in range(SCATTER)]
+
+    def sparse(rows, c, x):
+        vs[blk[:, None], rows[:, None], c[None, :]] ^= x
+
+    def whole(rows, w):
+        vs[blk, rows, :L] ^= w[None, :]
+
+    def scattered():
+        for j in range(SCATTER):
+            m = j // 2
+            sel = slice(m * part, (m + 1) * part)
+            sparse(srows[j], c1[sel], (x1 if j % 2 == 0 else x2)[:, sel])
+
+    one = lambda: sparse(r1, c1, x1)  # noqa: E731
+    two = lambda: (sparse(r1, c1, x1), sparse(r2, c1, x2))  # noqa: E731
+    both = lambda: (whole(r1, w1), whole(r2, w2))  # noqa: E731
+    damage = {"correct1_one": one, "correct_one": one, "correct_two": two, "correct_whole": both,
+              "correct_scattered": scattered, "heal_one": one, "heal_two": two, "heal_whole": both}
+    torch.cuda.synchronize()
+
+    def run(kind):
+        """One timed run: (ms, {kernel name: ms})."""
+        if kind in damage:
+            damage[kind]()
+            torch.cuda.synchronize()
+        if kind == "columns_clean":
+            return ml.timed(ctx, lambda: ctx.repair_blocks(k, e, L, pitch, B, enc.src, enc.par, rrep, mode="columns"))
+        if kind.startswith("heal"):
+            def heal():
+                ctx.locate_blocks(k, e, L, pitch, B, enc.src, enc.par, U, lists, srep)
+                ctx.rebuild_blocks(k, e, L, pitch, B, enc.src, enc.par, U, lists, srep2, check=False)
+            return ml.timed(ctx, heal)
+        t = 1 if kind.startswith("correct1") else 2
+        return ml.timed(ctx, lambda: ctx.correct_blocks(k, e, L, pitch, B, enc.src, enc.par, crep, t=t))
+
+    skip = set(filter(None, a.skip.split(",")))
+    kinds = [kd for kd in ["columns_clean", "correct_clean", "correct1_one", "correct_one", "correct_two",
+                           "correct_whole", "correct_scattered", "heal_one", "heal_two", "heal_whole"]
+             if kd not in skip]
+    bad = {"correct1_one": (ncols, 0), "correct_one": (ncols, 0), "correct_two": (ncols, ncols),
+           "correct_whole": (L, L), "correct_scattered": (part * (SCATTER // 2), part * (SCATTER // 2))}
+    kernels_seen = {}
+    for kind in kinds:  # untimed and checked
+        crep.fill_(0xA5)
+        ms, by = run(kind)
+        print(f"checked {kind}: {ms:.2f} ms", file=sys.stderr, flush=True)
+        kernels_seen[kind] = sorted(by)
+        if kind == "columns_clean":
+            r = rrep.cpu().numpy().view(rsgpu.REPAIR_REPORT_DTYPE)
+            assert (r["status"] == rsgpu.REPAIR_CLEAN).all() and "k_repair_compare" in by, kind
+        elif kind.startswith("heal"):
+            r = srep.cpu().numpy().view(rsgpu.SCRUB_REPORT_DTYPE)
+            assert (r["status"] == (rsgpu.SCRUB_ONE_ROW if kind == "heal_one" else rsgpu.SCRUB_ROWS)).all(), kind
+        else:
+            r = crep.cpu().numpy().view(DT)
+            assert "k_correct_compare" in by, kind
+            if kind == "correct_clean":
+                assert (r["status"] == rsgpu.REPAIR_CLEAN).all() and (r["bad_columns"] == 0).all(), kind
+            else:
+                n, n2 = bad[kind]
+                assert (r["status"] == rsgpu.REPAIR_REPAIRED).all() and (r["bad_columns"] == n).all(), kind
+                assert (r["corrected_columns"] == n).all() and (r["two_row_columns"] == n2).all(), kind
+        ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, srep)
+        torch.cuda.synchronize()
+        assert ml.all_clean(srep), "the blocks after " + kind
+
+    def progress(kind):
+        out = run(kind)
+        print(f"{kind} {out[0]:.2f}", file=sys.stderr, flush=True)
+        return out
+
+    out = {**ml.header(enc), "kernels": kernels_seen, "bad_columns": {kd: v[0] for kd, v in bad.items()},
+           "runs": ml.mirrored_rounds(kinds, a.rounds, progress)}
+    ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, srep)
+    torch.cuda.synchronize()
+    assert ml.all_clean(srep), "the blocks after the last run"
+    summ = ml.summarise(out["runs"], kinds, kernel_medians=True)
+    half = len(kinds)
+    at = {(r["round"], r["pos"] >= half, r["kind"]): r["ms"] for r in out["runs"]}
+    if "columns_clean" in kinds and "correct_clean" in kinds:
+        ratios = [at[(rnd, h, "correct_clean")] / at[(rnd, h, "columns_clean")] for rnd in range(a.rounds)
+                  for h in (False, True)]
+        summ["correct_clean"]["over_columns_in_pairs"] = ml.stats(ratios)
+        summ["correct_clean"]["over_columns_in_pairs"]["mean"] = float(np.mean(ratios))
+        cmp_ratios = [r["kernels"]["k_correct_compare"] for r in out["runs"] if r["kind"] == "correct_clean"]
+        rep_ratios = [r["kernels"]["k_repair_compare"] for r in out["runs"] if r["kind"] == "columns_clean"]
+        summ["correct_clean"]["compare_kernel_over_columns"] = float(np.median(cmp_ratios) / np.median(rep_ratios))
+    ml.finish(a.out, out, summ)
+    ctx.set_scrub_kernel("auto")
+    ctx.set_locate_kernel("auto")
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -1,5 +1,6 @@
 """What the scrub family's measuring tools share (tools/repair_measure.py,
-update_measure.py, degraded_measure.py, rebuild_measure.py, locate_measure.py; a tool, not the
+update_measure.py, degraded_measure.py, rebuild_measure.py, locate_measure.py,
+correct_measure.py; a tool, not the
 product): the shape arguments, the context and encoder at that shape, the
 timing of one call from rsgpu_timing_read, the torch copy that is the
 yardstick for "memory-bound", the check that every report is CLEAN, the
