@@ -4,13 +4,24 @@ Not a test module.
 
 plan(k, e, L, block) is what one block gets: [(kind, column, [(row, x)])].
 The columns are chosen for k_correct_compare's walk: a thread owns a 16-byte
-group of 16-byte aligned rows (a byte of unaligned ones), a wave 64 of them."""
+group of 16-byte aligned rows (a byte of unaligned ones), a wave 64 of them.
+
+The shapes with more than 64 data rows, (65, 6) (129, 7) (245, 5) Cauchy and
+(100, 20) (213, 37) RS, are there for the loops of the wave over the data
+rows (the per-row tables, the data-plus-parity search, the data-pair search
+in bands of 64 rows): band_pairs(k, e) damages pairs of rows inside a band,
+across two bands and on both sides of every band's edge."""
 import numpy as np
 
 # (k, e, matrix): Cauchy for the MDS property; gf_gen_rs_matrix shapes that the
 # model corrects in every planned one- and two-row column (test_correct.py);
-# k + e > 64 rows; a lane per syndrome used up (e = 64)
-SHAPES = [(6, 5, "cauchy"), (12, 6, "cauchy"), (16, 8, "rs"), (20, 7, "rs"), (64, 32, "rs"), (8, 64, "cauchy")]
+# k + e > 64 rows; a lane per syndrome used up (e = 64); k > 64, where the
+# wave's loops over the data rows take a second trip: one lane on it (65),
+# the C5 code (100, 20), three trips (129), k + e = 250 (245, 5)
+SHAPES = [(6, 5, "cauchy"), (12, 6, "cauchy"), (16, 8, "rs"), (20, 7, "rs"), (64, 32, "rs"), (8, 64, "cauchy"),
+          (65, 6, "cauchy"), (100, 20, "rs"), (129, 7, "cauchy"), (245, 5, "cauchy")]
+# the shapes of band_pairs: SHAPES' k > 64 and the scrub's large RS shape
+BAND_SHAPES = SHAPES[6:] + [(213, 37, "rs")]
 # (len, gpu_family.pitch_of mode): len % 32 == 0 under a longer pitch, whose
 # bytes in [len, pitch) are sentinels; a 16-byte body with a byte tail; rows one
 # byte off the allocation's alignment, every column on the byte path
@@ -63,6 +74,33 @@ def scattered(k, e, L, rows=12):
             for n in range(rows)]
 
 
+def band_pairs(k, e):
+    """k > 64: one bad column per pair of rows around the edges of the 64-row
+    bands of the data rows, [(column, [(ra, x), (rb, y)])] with ra < rb: data
+    pairs inside a band, across neighbouring bands and across distant ones,
+    pairs of a data and a parity row, and past 128 and 192 rows the same
+    around those edges.  Some pairs coincide at small k; each keeps its
+    column."""
+    last = (k - 1) // 64 * 64
+    pairs = [(0, 64), (63, 64), (64, 65), (1, k - 1), (last - 1, last), (k - 2, k - 1),
+             (64, k), (k - 1, k), (k - 1, k + 1), (last, k + e - 1), (65, k + 2)]
+    if k > 128:
+        pairs += [(127, 128), (128, 129), (70, 130)]
+    if k > 192:
+        pairs += [(191, 192), (5, 200), (130, k - 1)]
+    assert all(0 <= a < b < k + e for a, b in pairs)
+    rng = np.random.default_rng(31 * k + e)
+    return [(7 + 233 * n, [(a, int(rng.integers(1, 256))), (b, int(rng.integers(1, 256)))])
+            for n, (a, b) in enumerate(pairs)]
+
+
+def three_bands(k):
+    """(245, 5): a column damaged in three data rows of three different bands,
+    which no row and no pair explains (the code's distance is 6), and beside
+    it a column damaged in the last data row alone: [(column, [(row, x)])]."""
+    return [(2050, [(10, 0x1D), (100, 0x72), (200, 0xE3)]), (2051, [(k - 1, 0x4C)])]
+
+
 def dependent_matrix():
     """A locatable (12, 6) matrix that is not MDS, made from the Cauchy one:
     h_3 = h_0 + 2 h_1 + 3 h_2, so that h_0 + 2 h_1 is also h_3 + 3 h_2, and
@@ -77,6 +115,40 @@ def dependent_matrix():
     assert sm.locatable(c)
     return c
 
+
+def dependent_wide_matrix():
+    """The same at (129, 7), for the data-pair search's walk over the bands of
+    64 rows (WIDE_DEPENDENCIES): h_3 in the plane of h_0, h_1, h_2 (both pairs
+    in the first band, so the walk stops after it), h_100 in that of h_5, h_6,
+    h_70 (a pair in the first band and one in the second, found by two lanes
+    on different trips) and h_128 in that of h_64, h_65, h_127 (the second
+    band and the third, which has one row)."""
+    import scrub_model as sm
+    c = sm.cauchy_matrix(129, 7).copy()
+    for d, r0, r1, r2, f, g in WIDE_DEPENDENCIES:
+        c[:, d] = c[:, r0] ^ sm.MUL[c[:, r1], f] ^ sm.MUL[c[:, r2], g]
+    assert sm.locatable(c)
+    return c
+
+
+# h_d = h_r0 + f h_r1 + g h_r2 as (d, r0, r1, r2, f, g); f and g are the first
+# factors from 2 on with which every entry of the matrix stays non-zero and
+# the matrix locatable, one dependency after the other
+WIDE_DEPENDENCIES = [(3, 0, 1, 2, 2, 5), (100, 5, 6, 70, 2, 4), (128, 64, 65, 127, 2, 4)]
+
+
+def _mul(a, b):
+    import scrub_model as sm
+    return int(sm.MUL[a, b])
+
+
+# columns of dependent_wide_matrix() that two pairs explain, each from either
+# side (x h_r0 + f x h_r1 is also x h_d + g x h_r2), and two beside them that
+# only their own pair explains
+AMBIGUOUS_WIDE = [(50 + 2 * n + side, sorted([(r0, x), (r1, _mul(f, x))] if side == 0 else [(d, x), (r2, _mul(g, x))]))
+                  for n, (d, r0, r1, r2, f, g) in enumerate(WIDE_DEPENDENCIES)
+                  for side, x in ((0, 1 + 6 * n), (1, 0x35 + n))]
+UNIQUE_WIDE = [(80, [(0, 1), (1, 1)]), (2049, [(70, 1), (127, 1)])]
 
 # columns of dependent_matrix() that two pairs explain, each from either side,
 # and one beside them that only its own pair explains: (column, [(row, x)])

@@ -176,6 +176,69 @@ def mixed_lists(k, e, u, B, seed=5):
     return lost
 
 
+def band_members(k, e):
+    """The rows around the 64-row bands of a wave's strided loops that a
+    (k, e) block has: both sides of every band's edge, the last data row, the
+    first parity row, the parity rows 63 and 64, the last row."""
+    want = (63, 64, 65, 127, 128, 129, 191, 192, k - 1, k, k + 63, k + 64, k + e - 1)
+    return sorted({r for r in want if 0 <= r < k + e})
+
+
+def band_lists(k, e, u, B):
+    """The lists of blocks 2..5 of a wide case, (4, u): each min(u, e) - 1 of
+    band_members (all of them where there are fewer), ascending, dealt out so
+    that a list has rows of several bands and the four hold every member."""
+    assert B >= 6
+    have = band_members(k, e)
+    n = min(min(u, e) - 1, len(have))
+    assert 1 <= n and 4 * n >= len(have)
+    out = np.full((4, u), dm.NONE, np.uint8)
+    for i in range(4):
+        rows = have[i::4]
+        rows += [r for r in have[i + 1:] + have[:i] if r not in rows]
+        out[i] = dm.pad(sorted(rows[:n]), u)
+    assert {int(r) for r in out.ravel()} - {dm.NONE} == set(have)
+    return out
+
+
+def wide_lists(k, e, u, B):
+    """mixed_lists with band_lists in blocks 2..5."""
+    lost = mixed_lists(k, e, u, B)
+    lost[2:6] = band_lists(k, e, u, B)
+    return lost
+
+
+def wide_row(k, e):
+    """The row of a wide case's deliberate ONE_ROW block: the last data row
+    where k > 64, the last parity row where only e is."""
+    return max(64, k - 1) if k > 64 else k + e - 1
+
+
+def wide_plan(lost, k, e, L):
+    """The deliberate damage of a wide case, [(block, row, column, x)], and
+    its two blocks, both among the blocks 0..4 that damage() leaves alone: one
+    byte of wide_row in the first of 2, 3, 4, 0 whose list does not hold it
+    (ONE_ROW; block 0 lists the first rows), and in another one a byte of its
+    first and of its last survivor, in different columns (DAMAGED)."""
+    row = wide_row(k, e)
+    one = next(b for b in (2, 3, 4, 0) if row not in dm.list_rows(lost[b], k, e))
+    two = next(b for b in range(2, 5) if b != one)
+    surv = [r for r in range(k + e) if r not in dm.list_rows(lost[two], k, e)]
+    return [(one, row, L // 2, 0x5A), (two, surv[0], 1, 0x21), (two, surv[-1], L - 1, 0x84)], one, two
+
+
+def wide_damage(st, seed=9):
+    """damage(), whose kind is 0 in blocks 0..4 (min(u, e) >= 4), then
+    wide_plan; returns wide_plan's two blocks."""
+    assert min(st.u, st.e) >= 4
+    damage(st, seed)
+    hits, one, two = wide_plan(st.lost, st.k, st.e, st.L)
+    for b, row, col, x in hits:
+        st.xor(b, row, col, x)
+    torch.cuda.synchronize()
+    return one, two
+
+
 def damage(st, seed=9):
     """Block b gets damage kind (b // (min(u, e) + 1)) mod 7, so that every
     kind meets every n: none; one byte of a survivor; one survivor in several
@@ -217,7 +280,9 @@ def damage(st, seed=9):
 
 # codes (5, 4) (16, 4) (20, 7) (64, 32) RS and Cauchy (10, 4); len in {1, 31,
 # 32, 2080, 4176} and 4099 (a 16-byte body with a 3-byte tail); the three
-# pitches; blocks in {1, 67}; u in {1, 2, 4, 8}
+# pitches; blocks in {1, 67}; u in {1, 2, 4, 8}.  WIDE_CASES below: more than
+# 64 source rows, (65, 6) (129, 9) (245, 5) Cauchy and (100, 20) (213, 37) RS,
+# and more than 64 parity rows, (9, 70) RS
 CASES = [
     (5, 4, "rs", 4176, 67, 4, "plus48"),
     (5, 4, "rs", 1, 67, 1, "eq"),
@@ -234,4 +299,16 @@ CASES = [
     (10, 4, "cauchy", 2080, 67, 4, "plus48"),
     (10, 4, "cauchy", 4176, 1, 8, "eq"),
     (10, 4, "cauchy", 1, 1, 1, "mis1"),
+]
+
+# more rows than a wave has lanes, where the strided loops of the prepare
+# kernels (for r = lane; r < k; r += 64) take a second, ragged trip; lists
+# from wide_lists, damage from wide_damage
+WIDE_CASES = [
+    (65, 6, "cauchy", 2080, 67, 4, "plus48"),  # one lane on the second trip
+    (100, 20, "rs", 2080, 67, 8, "eq"),        # the C5 code
+    (129, 9, "cauchy", 4099, 23, 8, "tail"),   # three trips, the last with one lane; byte tail
+    (213, 37, "rs", 2080, 23, 8, "mis1"),      # the scrub's and the repair's large shape, byte kernels
+    (245, 5, "cauchy", 2080, 23, 4, "eq"),     # k + e = 250 = RSGPU_MAX_SOURCES
+    (9, 70, "rs", 2080, 23, 8, "plus48"),      # e > 64: more than 64 rest rows in the degraded prepare
 ]

@@ -118,7 +118,7 @@ def test_one_row_corrections_in_one_row_name_it():
 
 def test_scattered_damage_is_corrected():
     """The case the call exists for: damage in 12 rows, two per column."""
-    for k, e, kind in [(12, 6, "cauchy"), (20, 7, "rs"), (64, 32, "rs")]:
+    for k, e, kind in [(12, 6, "cauchy"), (20, 7, "rs"), (64, 32, "rs"), (245, 5, "cauchy"), (100, 20, "rs")]:
         c = matrix(k, e, kind)
         src, par = codeword(c, 256, 8)
         s1, p1 = src.copy(), par.copy()
@@ -127,6 +127,50 @@ def test_scattered_damage_is_corrected():
                 hit(s1, p1, row, col, x)
         s2, p2, verdict = cm.correct(c, s1, p1, 2)
         assert verdict == (12, 12, 12, cm.REPAIRED, -1) and (s2 == src).all() and (p2 == par).all()
+
+
+@pytest.mark.parametrize("k,e,kind", cc.BAND_SHAPES, ids=str)
+def test_pairs_across_bands_are_two_row_corrections(k, e, kind):
+    """What tests/test_gpu_correct.py test_pairs_across_bands relies on: every
+    column of band_pairs is a two-row correction of exactly its pair and the
+    block comes back as the codeword; t = 1 leaves every byte; a second pass
+    finds nothing."""
+    c = matrix(k, e, kind)
+    src, par = codeword(c, 4128, 2)
+    s1, p1 = src.copy(), par.copy()
+    todo = cc.band_pairs(k, e)
+    assert len(todo) == (17 if k > 192 else 14 if k > 128 else 11)
+    assert any(a < k and b < k and a // 64 != b // 64 for _, ((a, _), (b, _)) in todo)
+    for col, hits in todo:
+        for row, x in hits:
+            hit(s1, p1, row, col, x)
+    syn = sm.syndromes(c, s1, p1)
+    for col, hits in todo:
+        assert cm.verdict(c, syn[:, col], 2) == hits, (col, hits)
+    s2, p2, verdict = cm.correct(c, s1, p1, 2)
+    assert verdict == (len(todo), len(todo), len(todo), cm.REPAIRED, -1)
+    assert (s2 == src).all() and (p2 == par).all()
+    s3, p3, verdict = cm.correct(c, s1, p1, 1)
+    assert verdict == (len(todo), 0, 0, cm.DAMAGED, -1) and (s3 == s1).all() and (p3 == p1).all()
+    assert cm.correct(c, s2, p2, 2)[2] == (0, 0, 0, cm.CLEAN, -1)
+
+
+def test_three_rows_of_three_bands_are_left_alone():
+    """(245, 5) Cauchy, distance 6: the column damaged in rows of three
+    different bands stays byte for byte, the one beside it in row 244 alone
+    is corrected."""
+    k, e = 245, 5
+    c = sm.cauchy_matrix(k, e)
+    src, par = codeword(c, 4128, 3)
+    s1, p1 = src.copy(), par.copy()
+    (col3, hits3), (col1, hits1) = cc.three_bands(k)
+    assert len({r // 64 for r, _ in hits3}) == 3 and hits1[0][0] == 244
+    for col, hits in ((col3, hits3), (col1, hits1)):
+        for row, x in hits:
+            hit(s1, p1, row, col, x)
+    s2, p2, verdict = cm.correct(c, s1, p1, 2)
+    assert verdict == (2, 1, 0, cm.PARTIAL, 244)
+    assert (s2[:, col3] == s1[:, col3]).all() and (s2[:, col1] == src[:, col1]).all() and (p2 == p1).all()
 
 
 def test_two_matching_pairs_leave_the_column_alone():
@@ -141,6 +185,32 @@ def test_two_matching_pairs_leave_the_column_alone():
     s2, p2, verdict = cm.correct(c, s1, p1, 2)
     assert verdict == (6, 1, 1, cm.PARTIAL, -1)
     for col, hits in cc.UNIQUE:
+        for row, x in hits:
+            hit(s1, p1, row, col, x)
+    assert (s2 == s1).all() and (p2 == p1).all()
+
+
+def test_two_matching_pairs_in_different_bands():
+    """The same at (129, 7) with the two pairs in one 64-row band, in two
+    neighbouring ones and in the last, one-row band: each ambiguous column has
+    exactly its two pairs and stays as it is, the two beside them come back."""
+    c = cc.dependent_wide_matrix()
+    src, par = codeword(c, 2100, 7)
+    s1, p1 = src.copy(), par.copy()
+    for col, hits in cc.AMBIGUOUS_WIDE + cc.UNIQUE_WIDE:
+        for row, x in hits:
+            hit(s1, p1, row, col, x)
+    syn = sm.syndromes(c, s1, p1)
+    bands = set()
+    for col, _ in cc.AMBIGUOUS_WIDE:
+        pairs = {(a, b) for a, b, _, _ in cm.explaining_pairs(c, syn[:, col])}
+        assert len(pairs) == 2 and not sm.explaining_rows(c, syn[:, col]), (col, pairs)
+        bands.add(tuple(sorted(b // 64 for _, b in pairs)))
+    assert bands == {(0, 0), (0, 1), (1, 2)}
+    s2, p2, verdict = cm.correct(c, s1, p1, 2)
+    n = len(cc.AMBIGUOUS_WIDE)
+    assert verdict == (n + 2, 2, 2, cm.PARTIAL, -1)
+    for col, hits in cc.UNIQUE_WIDE:
         for row, x in hits:
             hit(s1, p1, row, col, x)
     assert (s2 == s1).all() and (p2 == p1).all()

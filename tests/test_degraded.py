@@ -301,6 +301,46 @@ def test_the_hazard(orc):
     assert all((rec[i] == src[r]).all() for i, r in enumerate([0, flipped, 4]))
 
 
+def test_lists_and_damage_of_the_wide_cases():
+    """What the GPU suites take for granted at more than 64 source (or parity)
+    rows, tests/gpu_family.py WIDE_CASES: band_lists gives blocks 2..5 lists
+    of min(u, e) - 1 ascending rows around the edges of the 64-row bands which
+    between them hold every such row of the shape, and the model calls the two
+    deliberately damaged blocks of wide_plan ONE_ROW, in a row of the second
+    band or above (a parity row from k + 64 on at (9, 70)), and DAMAGED; with
+    the lists of the checked rebuild (u <= 7) as well."""
+    pytest.importorskip("torch")
+    import gpu_family as gf
+    assert [(k, e) for k, e, *_ in gf.WIDE_CASES] == [(65, 6), (100, 20), (129, 9), (213, 37), (245, 5), (9, 70)]
+    for k, e, kind, L, B, u, mode in gf.WIDE_CASES:
+        assert k + e <= 250 and max(k, e) > 64
+        pool = {63, 64, 65, 127, 128, 129, 191, 192, k - 1, k, k + 63, k + 64, k + e - 1}
+        have = {r for r in pool if r < k + e}
+        assert have == set(gf.band_members(k, e)) and max(have) == k + e - 1
+        c = gf.matrix(k, e, kind)
+        src, par = block(c, 64, seed=k)
+        for uu in {u, min(u, 7)}:
+            lists = gf.band_lists(k, e, uu, B)
+            rows = [dm.list_rows(lst, k, e) for lst in lists]
+            assert lists.shape == (4, uu) and all(r is not None for r in rows)
+            assert all(len(r) == min(min(uu, e) - 1, len(have)) and set(r) <= have for r in rows)
+            assert set().union(*rows) == have
+            lost = gf.wide_lists(k, e, uu, B)
+            assert (lost[2:6] == lists).all() and (lost[:2] == gf.mixed_lists(k, e, uu, B)[:2]).all()
+            hits, one, two = gf.wide_plan(lost, k, e, 64)
+            want = {one: (1, dm.ONE_ROW, gf.wide_row(k, e)), two: (2, dm.DAMAGED, -1)}
+            assert gf.wide_row(k, e) >= (k + 64 if k <= 64 else 64) and one != two and {one, two} <= {0, 2, 3, 4}
+            for b in (one, two):
+                s2, p2 = src.copy(), par.copy()
+                for blk, row, col, x in hits:
+                    if blk == b:
+                        assert row not in dm.list_rows(lost[b], k, e)
+                        xor_byte(s2, p2, row, col, x)
+                for r in dm.list_rows(lost[b], k, e):  # whatever the lost rows hold
+                    xor_byte(s2, p2, r, 5, 0x77)
+                assert dm.report(c, s2, p2, lost[b]) == want[b], (k, e, uu, b)
+
+
 def test_null_context_and_constants():
     L = rsgpu.lib()
     assert L.rsgpu_scrub_degraded_blocks(None, 16, 4, 4096, 4096, 1, None, None, None, 1, None, 1, None) == -1

@@ -113,7 +113,49 @@ def test_planned_damage(ctx, k, e, kind, L, mode):
     assert blk.equals(after1)
 
 
-@pytest.mark.parametrize("k,e,kind", [(12, 6, "cauchy"), (64, 32, "rs")], ids=str)
+@pytest.mark.parametrize("L,mode", [(4128, "plus48"), (4128, "mis1")], ids=str)
+@pytest.mark.parametrize("k,e,kind", cc.BAND_SHAPES, ids=str)
+def test_pairs_across_bands(ctx, k, e, kind, L, mode):
+    """k > 64, block 1 of 3 damaged in pairs of rows inside a 64-row band,
+    across bands and on both sides of every band's edge, a column each: all
+    of them two-row corrections, the block the original encode again; t = 1
+    leaves every byte; a second call finds the block clean."""
+    blk = Blocks(ctx, k, e, kind, L, mode, B=3)
+    todo = cc.band_pairs(k, e)
+    for col, hits in todo:
+        blk.hit(1, hits, col)
+    damaged = blk.snapshot()
+    n = len(todo)
+    want, after = blk.model(2, [1])
+    assert want == [CLEAN, (n, n, n, cm.REPAIRED, -1), CLEAN]
+    assert torch.equal(after[0], blk.pristine[0]) and torch.equal(after[1], blk.pristine[1])
+    want1, after1 = blk.model(1, [1])
+    assert want1 == [CLEAN, (n, 0, 0, cm.DAMAGED, -1), CLEAN]
+    assert torch.equal(after1[0], damaged[0]) and torch.equal(after1[1], damaged[1])
+    run(blk, 1, want1, damaged)
+    run(blk, 2, want, blk.pristine)
+    run(blk, 2, [CLEAN] * 3, blk.pristine, poison=None)
+
+
+@pytest.mark.parametrize("L,mode", [(4128, "plus48"), (4128, "mis1")], ids=str)
+def test_three_rows_of_three_bands_are_left_alone(ctx, L, mode):
+    """(245, 5) Cauchy: a column damaged in data rows of three different
+    bands stays byte for byte, the column beside it in row 244 alone is
+    corrected."""
+    k, e = 245, 5
+    blk = Blocks(ctx, k, e, "cauchy", L, mode, B=3)
+    (col3, hits3), (col1, hits1) = cc.three_bands(k)
+    blk.hit(1, hits3, col3)
+    want_after = blk.snapshot()  # what the call must leave: the three-row column alone
+    blk.hit(1, hits1, col1)
+    want, after = blk.model(2, [1])
+    assert want == [CLEAN, (2, 1, 0, cm.PARTIAL, 244), CLEAN]
+    assert torch.equal(after[0], want_after[0]) and torch.equal(after[1], want_after[1])
+    run(blk, 2, want, after)
+    run(blk, 2, [CLEAN, (1, 0, 0, cm.DAMAGED, -1), CLEAN], after, poison=None)
+
+
+@pytest.mark.parametrize("k,e,kind", [(12, 6, "cauchy"), (64, 32, "rs"), (245, 5, "cauchy"), (100, 20, "rs")], ids=str)
 def test_scattered_damage_that_locate_calls_damaged(ctx, k, e, kind):
     """What the call exists for: block 1 damaged in 12 distinct rows, two per
     column.  rsgpu_locate_blocks gives it up; every column comes back."""
@@ -149,6 +191,27 @@ def test_two_matching_pairs_leave_the_column_alone(ctx, L, mode):
     assert want == [CLEAN, (6, 1, 1, cm.PARTIAL, -1)]
     run(blk, 2, want, after)
     run(blk, 2, [CLEAN, (5, 0, 0, cm.DAMAGED, -1)], after, poison=None)
+
+
+@pytest.mark.parametrize("L,mode", [(4128, "plus48"), (4128, "mis1")], ids=str)
+def test_two_matching_pairs_in_different_bands(ctx, L, mode):
+    """(129, 7) with dependent columns of [C | I] in one 64-row band, in two
+    neighbouring ones and in the last, one-row band: the data-pair search
+    stops after the band that holds both pairs, or meets the second pair in a
+    lane of a later trip; either way the column stays byte for byte."""
+    c = cc.dependent_wide_matrix()
+    pitch, offset = gf.pitch_of(L, mode)
+    blk = Blocks.__new__(Blocks)
+    gf.DeviceBlocks.__init__(blk, ctx, 129, 7, L, 2, pitch, offset, "cauchy", c=c)
+    blk.rep = torch.empty(2 * DT.itemsize, dtype=torch.uint8, device=blk.dev)
+    torch.cuda.synchronize()
+    for col, hits in cc.AMBIGUOUS_WIDE + cc.UNIQUE_WIDE:
+        blk.hit(1, hits, col)
+    n = len(cc.AMBIGUOUS_WIDE)
+    want, after = blk.model(2)
+    assert want == [CLEAN, (n + 2, 2, 2, cm.PARTIAL, -1)]
+    run(blk, 2, want, after)
+    run(blk, 2, [CLEAN, (n, 0, 0, cm.DAMAGED, -1)], after, poison=None)
 
 
 def test_more_blocks_than_a_grid_holds(ctx):

@@ -56,6 +56,28 @@ def test_against_the_model(ctx, orc, k, e, kind, L, B, u, mode):
     assert again.tobytes() == got.tobytes(), "the lost rows' contents changed a report"
 
 
+@pytest.mark.parametrize("k,e,kind,L,B,u,mode", gf.WIDE_CASES, ids=str)
+def test_wide_against_the_model(ctx, orc, k, e, kind, L, B, u, mode):
+    """More than 64 source rows, or parity rows: the same comparison with
+    lists around the edges of the 64-row bands in blocks 2..5, one of them
+    damaged in the last data row (at (9, 70) the last parity row), which the
+    model must name, and one in two rows."""
+    st = Stripe(ctx, k, e, L, B, u, kind, mode)
+    st.lost = gf.wide_lists(k, e, u, B)
+    one, two = gf.wide_damage(st)
+    st.fill_lost(None)
+    want = st.model(orc)
+    assert {dm.CLEAN, dm.ONE_ROW, dm.DAMAGED} <= {w[1] for w in want}
+    assert want[one] == (1, dm.ONE_ROW, gf.wide_row(k, e)) and want[two] == (2, dm.DAMAGED, -1)
+    assert any(w[1] == dm.ONE_ROW and w[2] >= (k + 64 if k <= 64 else 64) for w in want)
+    got = st.scrub()
+    same(got, want)
+    same(st.scrub(locate=False), st.model(orc, locate=False))
+    st.fill_lost(77)
+    again = st.scrub()
+    assert again.tobytes() == got.tobytes(), "the lost rows' contents changed a report"
+
+
 @pytest.mark.parametrize("k,e,kind,L,B", [(16, 4, "rs", 4176, 67), (16, 4, "rs", 4160, 67),  # 4160: the fused scrub
                                           (10, 4, "cauchy", 2080, 67),
                                           (64, 32, "rs", 4099, 67), (20, 7, "rs", 31, 67)], ids=str)

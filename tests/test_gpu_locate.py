@@ -209,6 +209,77 @@ def test_eight_rows_of_64_32(ctx):
     assert all(w[1:] == (lm.DAMAGED, -1) for w in want)
 
 
+WIDE = [(100, 20, "rs"), (245, 5, "cauchy"), (213, 37, "rs")]
+
+
+def wide_rows(k, e):
+    """The damaged rows of the six blocks of a wide shape: none; one row past
+    the first 64-row band; two rows of different bands; min(8, e - 1) rows
+    that go round the 64-row bands of the k + e rows, the last of them the
+    first parity row (in the last band); a data row and the last parity row;
+    nine rows, more than any u takes."""
+    n = min(8, e - 1)
+    bands = (k + e + 63) // 64
+    spread = sorted((i % bands) * 64 + 1 + 2 * i for i in range(n - 1))
+    assert len(set(spread)) == n - 1 and spread[-1] < k
+    return [[], [k - 2], [5, 64 + (k - 64) // 2], spread + [k], [65, k + e - 1],
+            sorted({3, 40, 63, 64, 70, k - 1, k, k + 1, k + e - 1})]
+
+
+@pytest.mark.parametrize("k,e,kind", WIDE, ids=str)
+def test_more_rows_than_a_wave_has_lanes(ctx, k, e, kind):
+    """k > 64 under the TWO_PASS kernel: k_locate_finish walks the members of
+    all k + e rows against the basis k_locate_span left.  The model must name
+    exactly the planned rows of blocks 1..4."""
+    L, B = 2048, 6
+    st = Blocks(ctx, k, e, L, B, L, kind=kind)
+    rng = np.random.default_rng(k)
+    plan = wide_rows(k, e)
+    for b, rows in enumerate(plan):
+        for r in rows:
+            st.hit(rng, b, r, columns(rng, L, 12))
+    syn = st.syndromes()
+    ctx.set_locate_kernel("two_pass")
+    try:
+        for u in (8, 2):
+            want = [lm.report_syn(st.c, s, u) for s in syn]
+            for b in range(1, 5):
+                if len(plan[b]) <= u:
+                    assert want[b][0][1:] == (lm.ONE_ROW if len(plan[b]) == 1 else lm.ROWS, plan[b][0]), (u, b)
+                    assert list(want[b][1][: len(plan[b])]) == plan[b], (u, b)
+                else:
+                    assert want[b][0][1:] == (lm.DAMAGED, -1), (u, b)
+            assert want[0][0] == (0, lm.CLEAN, -1) and want[5][0][1:] == (lm.DAMAGED, -1)
+            assert st.check(u, syn) == [w[0] for w in want]
+    finally:
+        ctx.set_locate_kernel("auto")
+    assert plan[1][0] >= 64 and plan[2][0] // 64 != plan[2][1] // 64 and len(plan[3]) == min(8, e - 1)
+    assert {r // 64 for r in plan[3]} == set(range((k + e + 63) // 64)) and plan[3][-1] == k
+
+
+def test_heal_above_64_sources(ctx):
+    """GpuEncoder.heal at (100, 20): rows 70, 99 and the last parity row of
+    block 1 are located and rebuilt, the blocks are the original encode."""
+    k, e, L, B = 100, 20, 4096, 3
+    enc = rsgpu.GpuEncoder(k, L, e, blocks=B, seed=9, ctx=ctx)
+    enc.encode_all()
+    torch.cuda.synchronize()
+    orig = enc.src.clone(), enc.par.clone()
+    rng = np.random.default_rng(100)
+    rows = [70, 99, 100 + 19]
+    for r in rows:
+        t = enc.src.view(B, k, enc.pitch)[1, r] if r < k else enc.par.view(B, e, enc.pitch)[1, r - k]
+        cols = sorted({0, L - 1, *columns(rng, L, 20)})
+        x = torch.from_numpy(rng.integers(1, 256, len(cols)).astype(np.uint8)).to(t.device)
+        t[torch.from_numpy(np.asarray(cols, np.int64)).to(t.device)] ^= x
+    torch.cuda.synchronize()
+    assert not torch.equal(enc.src, orig[0]) and not torch.equal(enc.par, orig[1])
+    found, rebuilt = enc.heal()
+    assert [(int(r["status"]), int(r["row"])) for r in found] == [(lm.CLEAN, -1), (lm.ROWS, 70), (lm.CLEAN, -1)]
+    gf.same(rebuilt, [(0, dm.CLEAN, -1)] * B)
+    assert torch.equal(enc.src, orig[0]) and torch.equal(enc.par, orig[1])
+
+
 def test_edges_of_e_and_len(ctx):
     rng = np.random.default_rng(1)
     one = Blocks(ctx, 6, 1, 256, 2, 256)

@@ -95,13 +95,19 @@ class Stripe(gf.DegradedStripe):
 same = gf.same
 
 
-@pytest.mark.parametrize("k,e,kind,L,B,u,mode", gf.CASES, ids=str)
+def lists_of(k, e, u, B):
+    """mixed_lists; above 64 source or parity rows with the lists around the
+    edges of the 64-row bands in blocks 2..5 (gf.wide_lists)."""
+    return gf.wide_lists(k, e, u, B) if max(k, e) > 64 else gf.mixed_lists(k, e, u, B)
+
+
+@pytest.mark.parametrize("k,e,kind,L,B,u,mode", gf.CASES + gf.WIDE_CASES, ids=str)
 def test_unchecked_against_the_model(ctx, k, e, kind, L, B, u, mode):
     """Mixed lists, n from 0 to min(u, e), consistent survivors: every block
     is CLEAN, the allocations are what the model says, which is the original
     encode; other noise in the lost rows, the same bytes and reports."""
     st = Stripe(ctx, k, e, L, B, u, kind, mode)
-    st.lost = gf.mixed_lists(k, e, u, B)
+    st.lost = lists_of(k, e, u, B)
     if B > 1:
         ns = {len(dm.list_rows(lst, k, e)) for lst in st.lost}
         assert ns == set(range(min(u, e) + 1))
@@ -165,7 +171,7 @@ def checked(st, orc):
     return want, (es, ep)
 
 
-CHECKED = [(k, e, kind, L, B, min(u, 7), mode) for k, e, kind, L, B, u, mode in gf.CASES]
+CHECKED = [(k, e, kind, L, B, min(u, 7), mode) for k, e, kind, L, B, u, mode in gf.CASES + gf.WIDE_CASES]
 
 
 @pytest.mark.parametrize("k,e,kind,L,B,u,mode", CHECKED, ids=str)
@@ -174,9 +180,10 @@ def test_checked_against_the_models(ctx, orc, k, e, kind, L, B, u, mode):
     degraded model's (BAD_MATRIX judged on the list as it is rebuilt), CLEAN
     blocks and ONE_ROW blocks come back as the original encode, DAMAGED ones
     keep their bytes, UNCHECKED ones are the model's."""
+    wide = max(k, e) > 64
     st = Stripe(ctx, k, e, L, B, u, kind, mode)
-    st.lost = gf.mixed_lists(k, e, u, B)
-    gf.damage(st)
+    st.lost = lists_of(k, e, u, B)
+    one, two = gf.wide_damage(st) if wide else (gf.damage(st), None)
     st.noise(5)
     before = st.snapshot()
     want, after = checked(st, orc)
@@ -184,6 +191,10 @@ def test_checked_against_the_models(ctx, orc, k, e, kind, L, B, u, mode):
         statuses = {w[1] for w in want}
         assert {dm.CLEAN, dm.ONE_ROW, dm.DAMAGED} <= statuses
         assert (dm.UNCHECKED in statuses) == (u >= e)
+    if wide:  # a located row in the second 64-row band or above: it is rebuilt
+        assert want[one] == (1, dm.ONE_ROW, gf.wide_row(k, e)) and want[two] == (2, dm.DAMAGED, -1)
+        assert any(w[1] == dm.ONE_ROW and w[2] >= (k + 64 if k <= 64 else 64) for w in want)
+        assert st.is_original(one)
     # the same input with other noise: the same bytes and reports; a block
     # that is not written keeps the noise in its lost rows, whichever it was
     st.src_all.copy_(before[0])

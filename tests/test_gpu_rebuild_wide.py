@@ -149,7 +149,10 @@ def factors(c, k, lost):
 
 
 TABLE_CASES = [(20, 12, "cauchy", 4207, 12, "tail"), (20, 12, "custom", 4207, 12, "tail"),
-               (5, 12, "cauchy", 4208, 9, "plus48"), (64, 32, "rs", 32, 32, "eq"), (20, 12, "rs", 64, 9, "eq")]
+               (5, 12, "cauchy", 4208, 9, "plus48"), (64, 32, "rs", 32, 32, "eq"), (20, 12, "rs", 64, 9, "eq"),
+               # k > 64: the sources the prepare's lanes write on their second and later trips
+               (65, 17, "rs", 4207, 17, "tail"), (129, 12, "cauchy", 4208, 12, "plus48"),
+               (218, 32, "rs", 4207, 32, "tail"), (218, 32, "rs", 64, 24, "eq")]
 
 
 @pytest.mark.parametrize("k,e,kind,L,u,mode", TABLE_CASES, ids=str)
@@ -232,6 +235,11 @@ CASES = [
     (64, 32, "rs", 32, "eq", 17),
     (64, 32, "cauchy", 4208, "plus48", 24),
     (64, 32, "rs", 31, "eq", 16),
+    # k > 64
+    (65, 17, "rs", 4207, "tail", 17),
+    (129, 12, "cauchy", 4208, "plus48", 12),
+    (218, 32, "rs", 4207, "tail", 32),
+    (218, 32, "rs", 64, "eq", 24),
 ]
 
 
@@ -458,4 +466,26 @@ def test_groups_of_blocks(ctx, kernel):
     st.same_bytes(es, ep)
     assert names.count("k_rebuild_wide_prepare") == 3
     assert names.count("k_rs_tc(rebuild)") == (3 if kernel == "threaded" else 0)
+    assert names == wide_names(st, kernel) * 3
+
+
+@pytest.mark.parametrize("kernel", ["lanes", "threaded"])
+def test_groups_of_blocks_above_64_sources(ctx, kernel):
+    """The same cap at (218, 32) with 32 lost rows and a byte tail: every
+    group's prepare writes the tables of sources 64..217 at its own offset."""
+    k, e, L, u = 218, 32, 4207, 32
+    H = hooks()
+    st = stripe(ctx, k, e, "rs", L, 8, u, "tail")
+    st.lost = lists_of(k, e, u, "rs")
+    st.noise(5)
+    pre, host = st.snapshot(), st.hosts()
+    want, es, ep = st.expect(pre, host, check=False)
+    assert [w[1] for w in want].count(dm.CLEAN) >= 4
+    assert H.rsgpu_internal_set_rebuild_group(ctx.handle, 3) == 0
+    try:
+        got, names = run(st, kernel, pre, seed=5)
+    finally:
+        H.rsgpu_internal_set_rebuild_group(ctx.handle, 0)
+    same(got, want)
+    st.same_bytes(es, ep)
     assert names == wide_names(st, kernel) * 3
