@@ -434,8 +434,9 @@ int rsgpu_set_scrub_kernel(rsgpu_ctx *ctx, int kernel);
  * the TWO_PASS scrub of complete blocks takes (36.2 ms; FUSED 22.3 ms, the
  * encode alone 22.0 ms); 4 lost rows 38.8 ms, 8 lost rows 41.5 ms.  The
  * compare is memory-bound for up to 2 lost data rows per block and bound by
- * its arithmetic at 8 (0.79 of the device-to-device copy rate).  Not built: a
- * form fused into the compiled encode, and host-resident blocks. */
+ * its arithmetic at 8 (0.79 of the device-to-device copy rate).  A form fused
+ * into the compiled encode is rsgpu_set_degraded_kernel's FUSED, below.  Not
+ * built: host-resident blocks. */
 #define RSGPU_LOST_NONE 255         /* list padding */
 #define RSGPU_SCRUB_UNCHECKED 3     /* n == e: no spare row, nothing can be checked */
 #define RSGPU_SCRUB_BAD_MATRIX (-1) /* the lost data rows are not determined by the surviving parity */
@@ -445,6 +446,43 @@ int rsgpu_scrub_degraded_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t
                                 const unsigned char *d_parity, const unsigned char *coef,
                                 int u, const unsigned char *d_lost, int flags,
                                 rsgpu_scrub_report *d_report);
+
+/* Kernel of rsgpu_scrub_degraded_blocks, and with it of the check that
+ * rsgpu_rebuild_blocks runs under RSGPU_REBUILD_CHECK (per context; every
+ * choice writes the same reports):
+ *   AUTO      TWO_PASS
+ *   TWO_PASS  the encode into scratch, then k_degraded_compare (the cost
+ *             above); any geometry
+ *   FUSED     k_rs_bs_degraded, between k_degraded_prepare and
+ *             k_degraded_finalise in place of the encode and the compare: the
+ *             compiled encode programs with the stored parity read and the
+ *             syndromes reduced and compared in registers, as FUSED of
+ *             rsgpu_set_scrub_kernel and where it applies -- (16,4) (16,8)
+ *             (64,32) (64,16) (100,20) (5,4) (20,7), no `coef`, pitch % 16 == 0,
+ *             16-byte aligned d_src and d_parity, len % 32 == 0, len < 4 GiB.
+ *             No encode is launched and the parity scratch is neither touched
+ *             nor grown; a workgroup whose block the prepare has reported loads
+ *             nothing, a lost parity row is never read, a clean tile writes
+ *             nothing.  Any other call runs TWO_PASS, silently.  Opt-in: AUTO
+ *             does not take it yet.
+ * rsgpu_set_scrub_kernel has no influence on these calls.
+ * Measured at (64, 32), 1 MB rows, 1024 blocks on one MI355X, both choices in
+ * mirrored pairs in one process, medians of 24 runs, FUSED / TWO_PASS and the
+ * spread of the pairs' ratio (profiles/degraded_fused), clean
+ * survivors: all-NONE lists 21.9 / 36.0 ms (0.60 - 0.69; the FUSED
+ * rsgpu_scrub_blocks of the same blocks 22.5 ms); one lost data row 23.9 / 36.3
+ * (0.65 - 0.67); one lost parity row 21.8 / 35.5 (0.60 - 0.63); 4 lost rows
+ * 27.3 / 37.3 (0.72 - 0.74); 8 lost data rows 35.3 / 42.9 (0.81 - 0.83); lists
+ * of 0 to 8 rows mixed 27.4 / 37.5 (0.72 - 0.74).  One surviving row bad in 1 %
+ * of the columns, one lost data row: 141.6 / 174.8 ms (0.81), the cold path on
+ * both sides.  The checked rebuild at n = 1 / 4 / 7: 35.5 / 42.2 / 51.3 ms
+ * against 47.8 / 52.1 / 59.7.  A lost parity row costs nothing, a lost data row
+ * 1.6 - 2.0 ms (one more pivot in the reduction on planes); FUSED did not lose
+ * to TWO_PASS at any number of lost rows a list can hold. */
+#define RSGPU_DEGRADED_AUTO 0
+#define RSGPU_DEGRADED_TWO_PASS 1
+#define RSGPU_DEGRADED_FUSED 2
+int rsgpu_set_degraded_kernel(rsgpu_ctx *ctx, int kernel);
 
 /* ---- rebuild in place of known-lost rows, optionally checked -------------- */
 

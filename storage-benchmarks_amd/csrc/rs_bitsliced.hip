@@ -39,7 +39,9 @@
 // (k_rs_bs_repair) is that epilogue with the rows writable: a bad column's
 // byte is corrected where its row and error value are found.  The locate of
 // several rows (k_rs_bs_locate) is the scrub with another cold path: a dirty
-// tile leaves the span of its syndrome columns (span_tile).
+// tile leaves the span of its syndrome columns (span_tile).  The degraded scrub
+// (k_rs_bs_degraded) reduces the syndromes of a block with known-lost rows on
+// planes before the mask (degraded_tile).
 //
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -50,6 +52,7 @@
 #include "diag_clock.h"
 #include "gf256.h"
 #include "kernel_hooks.h"
+#include "plane_mul.h"
 #include "rs_kernels.h"
 #include "rs_span.h"
 
@@ -252,6 +255,7 @@ __device__ __forceinline__ void consume_part(uint32_t (&acc)[NR][8], uint32_t (&
 // workgroup reduces belongs to one block.
 struct ScrubArgs {
     static constexpr bool kScrub = true;
+    static constexpr bool kDegraded = false;
     static constexpr bool kRepair = false;  // scrub_tile only reads the rows
     static constexpr bool kSpan = false;    // its cold path names one row per column
     static constexpr int flat = 0;
@@ -268,6 +272,7 @@ struct ScrubArgs {
 // columns (rs_kernels.h launch_rs_bitsliced_locate).
 struct LocArgs {
     static constexpr bool kScrub = true;
+    static constexpr bool kDegraded = false;
     static constexpr bool kRepair = false;
     static constexpr bool kSpan = true;  // scrub_tile's cold path is span_tile
     static constexpr int flat = 0;
@@ -286,6 +291,7 @@ struct LocArgs {
 // with writable rows, the 24-byte fold and a mode (rs_kernels.h kRepair*).
 struct RepairArgs {
     static constexpr bool kScrub = true;
+    static constexpr bool kDegraded = false;
     static constexpr bool kRepair = true;  // scrub_tile corrects what it locates
     static constexpr bool kSpan = false;
     static constexpr int flat = 0;
@@ -296,6 +302,22 @@ struct RepairArgs {
     long long blocks;
     RepairFold* fold;  // [B]: zeroed (kRepairLocate, kRepairColumns) or the final reports (kRepairGated)
     int mode;
+};
+
+// The degraded scrub (rsgpu_scrub_degraded_blocks under FUSED,
+// k_rs_bs_degraded): the scrub's arguments and the tables k_degraded_prepare
+// wrote (rs_kernels.h DegradedHdr); the epilogue is degraded_tile.
+struct DegArgs {
+    static constexpr bool kScrub = true;
+    static constexpr bool kDegraded = true;
+    static constexpr int flat = 0;
+    const uint8_t* src;  // [B][K] rows, the lost ones as they lie in memory
+    const uint8_t* par;  // [B][E] rows, the stored parity; a lost row is never read
+    long long pitch, len;
+    long long blocks;
+    const uint8_t* tab;  // [B] tables at degraded_tab_stride(K, E)
+    ScrubFold* fold;  // [B]: the reports, zeroed by the prepare where the block runs
+    int locate;
 };
 
 // log / antilog tables of the cold paths (the scrub's row location, the
@@ -574,6 +596,205 @@ __device__ __forceinline__ void scrub_tile(const A& a, uint32_t (&acc)[NR][8], b
     }
 }
 
+// The degraded scrub's epilogue (DegArgs): scrub_tile for a block with
+// known-lost rows, on the tables k_degraded_prepare wrote for it (rs_kernels.h:
+// the pivot parity rows Q, the other surviving parity rows `rest`, R and, with
+// locate, every row's reduced column H).  One round trip fetches the header
+// and the rest list (lane l: rest[l]), a second one, over the pivot barrier, R
+// (lane l: the 8 factors of rest row l); what a parity row is -- pivot i, rest row pi, or lost -- is then a ballot
+// per row of the wave, so every test below is wave-uniform.
+//   syndromes  the stored row to planes and into the accumulators, as
+//              scrub_tile; a lost parity row is not loaded and counts nowhere
+//   pivots     the wave's pivot rows' planes go to slot i of the second part
+//              buffer (a slot: [2][64] uint4 = 2 KB, at most 8), a barrier
+//   reduction  t_p = s_p ^ XOR_i R[p][i] s_Q[i] for the wave's rest rows, the
+//              pivot's planes read once per i and multiplied by the uniform
+//              constant on planes (plane_mul.h); Q rows are zero by
+//              construction, neither reduced nor counted
+//   mask       the OR over the rest rows' planes; from there scrub_tile's
+//              logic: masks meet in LDS, a clean tile leaves, wave 0 counts
+// The cold path (a dirty tile with locate) lays t, as bytes, into LDS in four
+// passes as scrub_tile lays its syndromes (the first pass may overwrite the
+// pivot slots: every wave is past its reduction at the mask barrier), and the
+// threads walk the 512 columns of a pass with deg_locate's rule (rs_degraded.hip)
+// on the t bytes in LDS and H from the table: the first non-zero entry p*, a
+// screen on one other entry, then t_p h_r[p*] == t_p* h_r[p] for every rest row;
+// a row only when exactly one surviving row passes.  Small code, not fast code.
+// LDS: masks 1 KiB | t [E][512] | rest [E]; the slots from 16 KiB on.
+template <int K, int E, int NW, int G, int R0, int NR>
+__device__ __forceinline__ void degraded_tile(const DegArgs& a, uint32_t (&acc)[NR][8], bool inb, long long wo,
+                                              long long wb, long long blk, int lane, uint4* ldsv, uint32_t m4,
+                                              uint32_t m2, uint32_t m1)
+{
+    static_assert(E >= 2 && E <= 64 && 1024 + E * 512 + E <= 2 * S * 2 * 64 * 16, "degraded LDS fits the part buffers");
+    uint32_t* wmask = reinterpret_cast<uint32_t*>(ldsv);
+    uint8_t* syn = reinterpret_cast<uint8_t*>(ldsv) + 1024;
+    uint8_t* lrest = syn + E * 512;
+    uint4* piv = ldsv + S * 2 * 64;
+    const uint8_t* pb = a.par + (size_t)wb * E * a.pitch;
+    const uint8_t* tab = a.tab + (size_t)blk * degraded_tab_stride(K, E);
+    const uint8_t* t_rest = tab + sizeof(DegradedHdr);
+    const uint8_t* t_r = t_rest + degraded_rest_bytes(E);
+    // the block's table: every lane the header, lane l < E rest[l] and R[l]
+    const uint4 hd = *reinterpret_cast<const uint4*>(tab);
+    const int rv = lane < E ? t_rest[lane] : 0;
+    const int nq = __builtin_amdgcn_readfirstlane((int)(hd.y & 0xFFu));
+    const int nrest = __builtin_amdgcn_readfirstlane((int)((hd.y >> 8) & 0xFFu));
+    const int qv = (int)(((lane & 4 ? hd.w : hd.z) >> (8 * (lane & 3))) & 0xFFu);  // lane i < 8: Q[i]
+    const unsigned long long qlanes = (1ull << nq) - 1, rlanes = (1ull << nrest) - 1;  // nq <= 8, nrest <= E < 64
+    int slot[NR], pi[NR];  // wave-uniform: the row's pivot slot / index among the rest rows, or -1
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const unsigned long long qm = __ballot(qv == R0 + r) & qlanes;
+        const unsigned long long rm = __ballot(rv == R0 + r) & rlanes;
+        slot[r] = qm ? __ffsll(qm) - 1 : -1;
+        pi[r] = rm ? __ffsll(rm) - 1 : -1;
+    }
+    // the syndromes of the surviving parity rows, one stored row ahead as scrub_tile
+    uint32_t Pn[8];
+    const long long po = inb ? wo : 0;
+    auto live = [&](int r) { return slot[r < NR ? r : 0] >= 0 || pi[r < NR ? r : 0] >= 0; };  // not a lost row
+    load32(pb + (size_t)R0 * a.pitch, po, live(0), Pn);
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        uint32_t Pw[8];
+#pragma unroll
+        for (int q = 0; q < 8; ++q)
+            Pw[q] = Pn[q];
+        if (r + 1 < NR)
+            load32(pb + (size_t)(R0 + r + 1) * a.pitch, po, live(r + 1), Pn);
+        if (live(r)) {
+            tr8(Pw, m4, m2, m1);
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                acc[r][q] ^= Pw[q];
+        }
+        if (slot[r] >= 0) {
+            piv[(slot[r] * 2 + 0) * 64 + lane] = make_uint4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+            piv[(slot[r] * 2 + 1) * 64 + lane] = make_uint4(acc[r][4], acc[r][5], acc[r][6], acc[r][7]);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    // R arrives over the barrier (loaded here, not with the header: two more
+    // VGPRs across the loop above put (64, 32) into scratch)
+    const uint2 rr8 = lane < E ? *reinterpret_cast<const uint2*>(t_r + lane * 8) : make_uint2(0u, 0u);
+    __syncthreads();
+    unsigned long long fac[NR];  // R[pi]: byte i the factor of pivot i
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        const int l = pi[r] >= 0 ? pi[r] : 0;
+        fac[r] = (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rr8.x, l) |
+                 (unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)rr8.y, l) << 32;
+    }
+    for (int i = 0; i < nq; ++i) {
+        const uint4 u = piv[(i * 2 + 0) * 64 + lane], v = piv[(i * 2 + 1) * 64 + lane];
+        const uint32_t sq[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            const uint32_t c = (uint32_t)(fac[r] >> (8 * i)) & 0xFFu;
+            if (pi[r] >= 0 && c)
+                plane_mul_acc(acc[r], sq, c);
+        }
+    }
+    uint32_t mine = 0;
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+        if (pi[r] >= 0) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q)
+                mine |= acc[r][q];
+        }
+    wmask[G * 64 + lane] = inb ? mine : 0u;
+    __syncthreads();
+    uint32_t tm = 0;
+#pragma unroll
+    for (int g = 0; g < NW; ++g)
+        tm |= wmask[g * 64 + lane];
+    if (__ballot(tm != 0) == 0)
+        return;  // the same for every wave of the workgroup
+    ScrubFold* f = a.fold + blk;
+    if constexpr (G == 0) {
+        unsigned n = __builtin_popcount(tm);
+        for (int off = 32; off > 0; off >>= 1)
+            n += __shfl_down(n, off, 64);
+        if (lane == 0)
+            atomicAdd(&f->bad, (unsigned long long)n);
+    }
+    if (!a.locate)
+        return;
+    const uint8_t* t_h = t_r + (size_t)E * 8;
+    const int tid = G * 64 + lane;
+    unsigned hi1 = 0, lo1 = 0;
+    if (tid < nrest)
+        lrest[tid] = t_rest[tid];  // read from the first pass's barrier on
+#pragma unroll
+    for (int r = 0; r < NR; ++r)
+        tr8(acc[r], m4, m2, m1);  // planes -> bytes, in place (a Q or lost row: never read below)
+    for (int pass = 0; pass < 4; ++pass) {
+        // the lane's bytes 8 pass .. 8 pass + 7 of every row (zeros from an idle lane)
+        [&]<int... Ps>(std::integer_sequence<int, Ps...>) {
+            ((pass == Ps ? [&] {
+#pragma unroll
+                for (int r = 0; r < NR; ++r)
+                    *reinterpret_cast<uint2*>(syn + (R0 + r) * 512 + lane * 8) =
+                        inb ? make_uint2(acc[r][2 * Ps], acc[r][2 * Ps + 1]) : make_uint2(0u, 0u);
+            }()
+                         : void()),
+             ...);
+        }(std::make_integer_sequence<int, 4>{});
+        __syncthreads();
+        for (int c = tid; c < 512; c += 64 * NW) {
+            int ps = -1;
+            uint8_t ts = 0, t0 = 0, t2 = 0;
+            for (int p = 0; p < nrest; ++p) {
+                const uint8_t t = syn[lrest[p] * 512 + c];
+                if (p == 0)
+                    t0 = t;
+                if (ps < 0 && t) {
+                    ps = p;
+                    ts = t;
+                } else if (ps >= 0 && p == ps + 1) {
+                    t2 = t;
+                }
+            }
+            if (ps < 0)
+                continue;  // not a bad column
+            // the screen: entry 0 (zero) when p* > 0, else entry 1 when there is one
+            const int p2 = ps > 0 ? 0 : nrest > 1 ? 1 : -1;
+            if (ps > 0)
+                t2 = t0;
+            int found = 0, row = -1;
+            for (int r = 0; r < K + E && found < 2; ++r) {
+                const uint8_t* h = t_h + (size_t)r * E;
+                const uint8_t hs = h[ps];
+                if (!hs)
+                    continue;
+                if (p2 >= 0 && gf_mul_slow(t2, hs) != gf_mul_slow(ts, h[p2]))
+                    continue;
+                bool ok = true;
+                for (int p = 0; p < nrest && ok; ++p)
+                    ok = gf_mul_slow(syn[lrest[p] * 512 + c], hs) == gf_mul_slow(ts, h[p]);
+                if (ok) {
+                    ++found;
+                    row = r;
+                }
+            }
+            row = found == 1 ? row : -1;
+            hi1 = max(hi1, row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
+            lo1 = max(lo1, row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
+        }
+        __syncthreads();  // the next pass overwrites t
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+        hi1 = max(hi1, (unsigned)__shfl_down((int)hi1, off, 64));
+        lo1 = max(lo1, (unsigned)__shfl_down((int)lo1, off, 64));
+    }
+    if (lane == 0 && hi1) {
+        atomicMax(&f->hi1, hi1);
+        atomicMax(&f->lo1, lo1);
+    }
+}
+
 // One wave group: rows [R0, R0+NR).  The workgroup streams the sources
 // chunk by chunk (Horner order, last chunk first) through the LDS parts:
 // while part n is transposed in place and consumed, part n+1 is already in
@@ -679,7 +900,10 @@ __device__ __forceinline__ void run_group(const A& a, uint4 (*lds)[S * 2 * 64])
 
     if constexpr (A::kScrub) {
         // the part buffers are free: every wave is past the last step's barrier
-        scrub_tile<K, E, NW, G, R0, NR>(a, acc, inb, wo, wb, tp.b0, lane, &lds[0][0], m4, m2, m1);
+        if constexpr (A::kDegraded)
+            degraded_tile<K, E, NW, G, R0, NR>(a, acc, inb, wo, wb, tp.b0, lane, &lds[0][0], m4, m2, m1);
+        else
+            scrub_tile<K, E, NW, G, R0, NR>(a, acc, inb, wo, wb, tp.b0, lane, &lds[0][0], m4, m2, m1);
     } else {
         if (!inb)
             return;
@@ -779,6 +1003,33 @@ hipError_t launch_repair(const RepairArgs& a, hipStream_t st)
 {
     dim3 grid((unsigned)((a.len + 2047) / 2048), (unsigned)a.blocks);
     hipLaunchKernelGGL((k_rs_bs_repair<K, E, C, NW>), grid, dim3(64 * NW), 0, st, a);
+    return hipGetLastError();
+}
+
+// The degraded scrub: k_rs_bs_scrub with degraded_tile as the epilogue.  A
+// workgroup whose block the prepare has already reported (state != kDegRun:
+// a malformed list, n == e, a matrix that does not determine D) leaves before
+// it loads anything; the block index is uniform, the state a scalar load.
+template <int K, int E, int C, int NW>
+__global__ __launch_bounds__(64 * NW, (bs_waves_per_simd<E, NW>())) void k_rs_bs_degraded(DegArgs a)
+{
+    __shared__ uint4 lds[2][S * 2 * 64];
+    if (reinterpret_cast<const DegradedHdr*>(a.tab + (size_t)blockIdx.y * degraded_tab_stride(K, E))->state != kDegRun)
+        return;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // the first match ends the chain: with the siblings' `? :` fold hipcc keeps
+    // the lane and the tile offsets alive through the group that runs, for the
+    // groups after it, at (64, 32) and (100, 20) in scratch
+    [&]<int... Gs>(std::integer_sequence<int, Gs...>) {
+        (void)((wave == Gs && (run_group<K, E, C, NW, Gs, true, DegArgs>(a, lds), true)) || ...);
+    }(std::make_integer_sequence<int, NW>{});
+}
+
+template <int K, int E, int C, int NW>
+hipError_t launch_degraded(const DegArgs& a, hipStream_t st)
+{
+    dim3 grid((unsigned)((a.len + 2047) / 2048), (unsigned)a.blocks);
+    hipLaunchKernelGGL((k_rs_bs_degraded<K, E, C, NW>), grid, dim3(64 * NW), 0, st, a);
     return hipGetLastError();
 }
 
@@ -1197,6 +1448,24 @@ hipError_t launch_rs_bitsliced_locate(int k, int e, const uint8_t* src, const ui
     if (k == 100 && e == 20) return bs::launch_locate<100, 20, 20, 4>(a, st);
     if (k == 5 && e == 4) return bs::launch_locate<5, 4, 5, 1>(a, st);
     if (k == 20 && e == 7) return bs::launch_locate<20, 7, 20, 1>(a, st);
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_rs_bitsliced_degraded(int k, int e, const uint8_t* src, const uint8_t* par, long long pitch,
+                                        long long len, long long blocks, const uint8_t* tab, ScrubFold* fold,
+                                        int locate, hipStream_t st)
+{
+    if (blocks <= 0 || blocks > 65535 || len <= 0 || len % 32 != 0 || len >= (1ll << 32) || pitch < len ||
+        !src || !par || !tab || !fold || (uintptr_t)tab % 16 != 0)
+        return hipErrorInvalidValue;
+    const bs::DegArgs a{src, par, pitch, len, blocks, tab, fold, locate};
+    if (k == 16 && e == 4) return bs::launch_degraded<16, 4, 16, 1>(a, st);
+    if (k == 16 && e == 8) return bs::launch_degraded<16, 8, 16, 1>(a, st);
+    if (k == 64 && e == 32) return bs::launch_degraded<64, 32, 16, 4>(a, st);
+    if (k == 64 && e == 16) return bs::launch_degraded<64, 16, 16, 2>(a, st);
+    if (k == 100 && e == 20) return bs::launch_degraded<100, 20, 20, 4>(a, st);
+    if (k == 5 && e == 4) return bs::launch_degraded<5, 4, 5, 1>(a, st);
+    if (k == 20 && e == 7) return bs::launch_degraded<20, 7, 20, 1>(a, st);
     return hipErrorInvalidValue;
 }
 

@@ -395,14 +395,6 @@ bool args_ok(const DegradedArgs& a)
 
 }  // namespace
 
-size_t degraded_rest_bytes(int e) { return ((size_t)e + 15) / 16 * 16; }
-
-size_t degraded_tab_stride(int k, int e)
-{
-    const size_t n = sizeof(DegradedHdr) + degraded_rest_bytes(e) + (size_t)e * 8 + (size_t)(k + e) * e;
-    return (n + 15) / 16 * 16;
-}
-
 hipError_t launch_degraded_prepare(const DegradedArgs& a, hipStream_t st)
 {
     if (!args_ok(a) || (a.work && !a.coef))

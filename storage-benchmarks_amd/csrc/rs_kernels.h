@@ -422,14 +422,28 @@ struct DegradedArgs {
     const uint32_t* tabc;  // device [256]: perm_tables word 4
     ::rsgpu_scrub_report* report;  // [B]
 };
-size_t degraded_rest_bytes(int e);
-size_t degraded_tab_stride(int k, int e);
+// (constant expressions: k_rs_bs_degraded takes them from its template arguments)
+constexpr size_t degraded_rest_bytes(int e) { return ((size_t)e + 15) / 16 * 16; }
+constexpr size_t degraded_tab_stride(int k, int e)
+{
+    return (sizeof(DegradedHdr) + degraded_rest_bytes(e) + (size_t)e * 8 + (size_t)(k + e) * e + 15) / 16 * 16;
+}
 hipError_t launch_degraded_prepare(const DegradedArgs& a, hipStream_t st);
 // bytes == false: columns [col0, col1) are 16-byte units of 16-byte aligned
 // rows; bytes == true: byte columns, any alignment
 hipError_t launch_degraded_compare(const DegradedArgs& a, bool bytes, long long col0, long long col1,
                                    hipStream_t st);
 hipError_t launch_degraded_finalise(const DegradedArgs& a, hipStream_t st);
+// The degraded scrub fused into the compiled encode (rs_bitsliced.hip
+// k_rs_bs_degraded), between the prepare and the finalise in place of the
+// encode and the compare: the accumulation of k_rs_bs_scrub, then the
+// syndromes reduced with the block's table and compared in registers; `fold`
+// is the blocks' reports.  The fused scrub's geometry (len % 32 == 0, len <
+// 2^32, 16-byte aligned rows, blocks <= 65535); `tab`: the blocks' tables at
+// degraded_tab_stride(k, e), 16-byte aligned.  A lost parity row is never read.
+hipError_t launch_rs_bitsliced_degraded(int k, int e, const uint8_t* src, const uint8_t* par, long long pitch,
+                                        long long len, long long blocks, const uint8_t* tab, ScrubFold* fold,
+                                        int locate, hipStream_t st);
 
 // Rebuild in place (rsgpu_rebuild_blocks, rs_rebuild.hip): the listed rows of
 // a block, and with `check` the one row its degraded report names, written

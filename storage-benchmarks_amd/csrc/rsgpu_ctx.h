@@ -92,8 +92,10 @@ struct rsgpu_ctx {
     void* d_update = nullptr;
     std::vector<uint8_t> update_key;
     // degraded scrub (rsgpu_scrub_degraded_blocks): the per-block tables
-    // k_degraded_prepare writes for one slice
+    // k_degraded_prepare writes for one slice, and its kernel choice
+    // (rsgpu_set_degraded_kernel)
     DevBuf degraded;
+    int degraded_kernel = RSGPU_DEGRADED_AUTO;
     // rebuild in place (rsgpu_rebuild_blocks): the per-block tables
     // k_rebuild_prepare writes for one group of blocks
     DevBuf rebuild;

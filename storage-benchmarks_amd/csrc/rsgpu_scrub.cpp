@@ -413,6 +413,14 @@ int rsgpu_set_locate_kernel(rsgpu_ctx* ctx, int kernel)
     return RSGPU_OK;
 }
 
+int rsgpu_set_degraded_kernel(rsgpu_ctx* ctx, int kernel)
+{
+    if (!ctx || kernel < RSGPU_DEGRADED_AUTO || kernel > RSGPU_DEGRADED_FUSED)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_degraded_kernel: unknown kernel");
+    ctx->degraded_kernel = kernel;
+    return RSGPU_OK;
+}
+
 int rsgpu_scrub_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                        const unsigned char* d_src, const unsigned char* d_parity,
                        const unsigned char* coef, int flags, rsgpu_scrub_report* d_report)
@@ -689,15 +697,19 @@ int rsgpu_scrub_degraded_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t
     // Two nested slicings.  A group of blocks shares one prepare and one
     // finalise: its tables fit kDegTabBytes, its blocks fit a grid.  Inside it
     // a slice is what the scrub scratch holds of computed parity (the TWO_PASS
-    // rule): encode, then compare.
+    // rule): encode, then compare.  FUSED (rsgpu_set_degraded_kernel) on the
+    // rows the fused scrub takes: one k_rs_bs_degraded launch over the group
+    // in their place, no encode and no parity scratch.
     const size_t per_block = (size_t)e * pitch, stride = degraded_tab_stride(k, e);
     const size_t group = std::max<size_t>(1, std::min({blocks, kMaxGridBlocks, kDegTabBytes / stride}));
     rc = ensure_device(ctx, ctx->degraded, group * stride);
     if (rc)
         return rc;
+    const bool fused = work && ctx->degraded_kernel == RSGPU_DEGRADED_FUSED &&
+                       fused_rows(k, e, len, pitch, d_src, d_parity, coef);
     if (work) {
         // the scratch of the largest group now, so that no walk below grows it
-        rc = grow_parity_scratch(ctx, group, per_block);
+        rc = fused ? RSGPU_OK : grow_parity_scratch(ctx, group, per_block);
         if (rc)
             return rc;
         // the v_perm tables of every coefficient value and the matrix, on the device
@@ -745,9 +757,17 @@ int rsgpu_scrub_degraded_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t
             };
             return launch_head_and_tail(ctx, kDegradedNames, nb, n16, (long long)len, launch);
         };
-        rc = two_pass(ctx, k, e, len, pitch, g0, ng, d_src, coef, nullptr, compare);
-        if (rc)
-            return rc;
+        if (fused) {
+            KTimer kt(ctx, "k_rs_bs_degraded", ng);
+            RS_HIP(ctx, launch_rs_bitsliced_degraded(k, e, d_src + g0 * (size_t)k * pitch, d_parity + g0 * per_block,
+                                                     (long long)pitch, (long long)len, (long long)ng, a.tab,
+                                                     reinterpret_cast<ScrubFold*>(d_report + g0), a.locate,
+                                                     ctx->stream));
+        } else {
+            rc = two_pass(ctx, k, e, len, pitch, g0, ng, d_src, coef, nullptr, compare);
+            if (rc)
+                return rc;
+        }
         KTimer kt(ctx, "k_degraded_finalise", ng);
         RS_HIP(ctx, launch_degraded_finalise(a, ctx->stream));
     }

@@ -16,6 +16,7 @@
 
 #include "../../include/rsgpu.h"
 #include "jit_prog.h"
+#include "plane_mul.h"
 #include "rs_jit.h"
 #include "rs_kernels.h"
 #include "rs_lane.h"
@@ -380,6 +381,21 @@ int rsgpu_internal_scrub_locate_row(int k, int e, const unsigned char* rowtab, c
     if (!nz || e < 2)
         return -1;
     return scrub_locate_row(k, e, rowtab, coef, gf, syn[0], syn[1], nz, p0, [&](int p) { return syn[p]; });
+}
+
+// Test hook (not part of include/rsgpu.h): the constant-times-planes multiply
+// of k_rs_bs_degraded's reduction (plane_mul.h) on the host: t[0..7] ^= c * s
+// [0..7], plane a holding bit a of 32 bytes.
+int rsgpu_internal_plane_mul_acc(unsigned c, const uint32_t* s, uint32_t* t)
+{
+    if (c > 255 || !s || !t)
+        return RSGPU_ERR_ARG;
+    uint32_t sv[8], tv[8];
+    std::memcpy(sv, s, sizeof sv);
+    std::memcpy(tv, t, sizeof tv);
+    plane_mul_acc(tv, sv, c);
+    std::memcpy(t, tv, sizeof tv);
+    return RSGPU_OK;
 }
 
 }  // extern "C"

@@ -40,7 +40,7 @@ __all__ = [
     "REPAIR_COLUMNS", "REPAIR_CLEAN", "REPAIR_REPAIRED", "REPAIR_PARTIAL", "REPAIR_DAMAGED",
     "UPDATE_NONE", "UPDATE_DELTA", "LOST_NONE", "SCRUB_UNCHECKED", "SCRUB_BAD_MATRIX",
     "SCRUB_BAD_LIST", "REBUILD_CHECK", "REBUILD_MAX_LOST", "REBUILD_KERNELS", "SCRUB_ROWS",
-    "LOCATE_MAX_ROWS", "LOCATE_KERNELS", "CORRECT_REPORT_DTYPE",
+    "LOCATE_MAX_ROWS", "LOCATE_KERNELS", "CORRECT_REPORT_DTYPE", "DEGRADED_KERNELS",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -94,6 +94,8 @@ SCRUB_ROWS = 4
 LOCATE_MAX_ROWS = 8
 # rsgpu_set_locate_kernel choices
 LOCATE_KERNELS = {"auto": 0, "two_pass": 1, "fused": 2}
+# rsgpu_set_degraded_kernel choices
+DEGRADED_KERNELS = {"auto": 0, "two_pass": 1, "fused": 2}
 
 vp = C.c_void_p
 sz = C.c_size_t
@@ -152,6 +154,7 @@ _SIGS = {
     "rsgpu_set_scrub_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_set_rebuild_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_set_locate_kernel": (C.c_int, [vp, C.c_int]),
+    "rsgpu_set_degraded_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_update_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, C.c_int, vp, vp, vp, vp, vp,
                                       C.c_int, vp]),
     "rsgpu_host_alloc": (C.c_int, [vp, C.POINTER(vp), sz]),
@@ -481,6 +484,19 @@ class Context:
         runs two_pass."""
         self.check(lib().rsgpu_set_locate_kernel(self._h, LOCATE_KERNELS[kernel]),
                    "rsgpu_set_locate_kernel")
+
+    def set_degraded_kernel(self, kernel: str) -> None:
+        """Kernel of scrub_degraded_blocks and of the check of rebuild_blocks
+        (so of GpuEncoder.scrub_degraded and rebuild): auto | two_pass | fused
+        (include/rsgpu.h rsgpu_set_degraded_kernel); every choice writes the
+        same reports.  fused: between the prepare and the finalise one launch
+        of the compiled encode's program with the stored parity read and the
+        syndromes reduced in registers, where the fused scrub applies (the
+        compiled codes, no coef, 16-byte aligned rows, len % 32 == 0);
+        otherwise two_pass, silently.  Opt-in, auto runs two_pass;
+        set_scrub_kernel has no influence on these calls."""
+        self.check(lib().rsgpu_set_degraded_kernel(self._h, DEGRADED_KERNELS[kernel]),
+                   "rsgpu_set_degraded_kernel")
 
     def scrub_blocks(self, k, e, length, pitch, blocks, d_src, d_par, d_report, coef=None,
                      locate: bool = True) -> None:

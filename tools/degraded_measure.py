@@ -21,6 +21,18 @@ The byte model: the call costs the encode plus 2 (e - |P|) rows per block
 parity rows) at the copy's rate; `over_model` is measured / modelled.
 
     python tools/degraded_measure.py out.json [--k 64 --e 32 --len 1000000 --blocks 1024 --rounds 12]
+
+--kernel two_pass | fused runs the degraded kinds above under that choice of
+rsgpu_set_degraded_kernel.  --kernel both is the measurement of the fused form
+(profiles/degraded_fused/README.md) instead: every case under FUSED and under
+TWO_PASS in mirrored pairs in one process -- clean blocks with all-NONE lists
+(beside the FUSED rsgpu_scrub_blocks), one lost data row, one lost parity
+row, 4 lost rows, 8 lost data rows and mixed lists of 0 to 8 rows; one
+surviving row bad in 1 % of the columns with one lost data row; the checked
+rebuild at n = 1, 4, 7 with clean survivors -- after one untimed run of each
+whose reports must be equal byte for byte under both choices.  Per case:
+the medians, and min / median / max of the ratio FUSED / TWO_PASS over the
+pairs of a round's two halves.
 """
 import numpy as np
 import torch
@@ -28,11 +40,104 @@ import torch
 import measure_lib as ml  # puts the engine's directory on the path
 
 
+def both(a, ctx, enc):
+    """--kernel both: FUSED against TWO_PASS, case by case."""
+    k, e, L, B = a.k, a.e, a.len, a.blocks
+    dev, pitch = enc.src.device, enc.pitch
+    rep = ml.reports(enc)
+    rng = np.random.default_rng(9)
+    none = np.full((B, 1), 255, np.uint8)
+
+    def pad(rows, u):
+        return np.concatenate([np.sort(rows), np.full(u - len(rows), 255)]).astype(np.uint8)
+
+    lists = {
+        "none": none,
+        "data1": (np.arange(B) % k).astype(np.uint8).reshape(B, 1),
+        "parity1": (k + np.arange(B) % e).astype(np.uint8).reshape(B, 1),
+        "rows4": np.stack([pad(rng.choice(k + e, 4, replace=False), 4) for _ in range(B)]),
+        "data8": np.stack([pad(rng.choice(k, 8, replace=False), 8) for _ in range(B)]),
+        "mixed": np.stack([pad(rng.choice(k + e, b % 9, replace=False), 8) for b in range(B)]),
+    }
+    for n in (1, 4, 7):
+        lists[f"rebuild{n}"] = np.stack([pad(rng.choice(k + e, n, replace=False), n) for _ in range(B)])
+    lists["bad1pct"] = lists["data1"]
+    d_lists = {n: torch.from_numpy(v).to(dev) for n, v in lists.items()}
+    cases = list(lists)
+    # bad1pct: row (lost + 1) mod k of every block, bad in every 100th column; applied around its runs
+    cols = torch.arange(0, L, 100, device=dev)
+    bad_rows = torch.from_numpy((lists["data1"][:, 0].astype(np.int64) + 1) % k).to(dev)
+    src = enc.src.view(B, k, pitch)
+
+    def flip():
+        src[torch.arange(B, device=dev)[:, None], bad_rows[:, None], cols[None, :]] ^= 0x5A
+
+    def run(kind):
+        case, kernel = kind.rsplit("/", 1)
+        if case == "scrub_fused":
+            ctx.set_scrub_kernel("fused")
+            try:
+                return ml.timed(ctx, lambda: ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, rep))
+            finally:
+                ctx.set_scrub_kernel("auto")
+        ctx.set_degraded_kernel(kernel)
+        lst = d_lists[case]
+        u = lst.shape[1]
+        if case == "bad1pct":
+            flip()
+        try:
+            if case.startswith("rebuild"):
+                return ml.timed(ctx, lambda: ctx.rebuild_blocks(k, e, L, pitch, B, enc.src, enc.par, u, lst, rep,
+                                                                check=True))
+            return ml.timed(ctx, lambda: ctx.scrub_degraded_blocks(k, e, L, pitch, B, enc.src, enc.par, u, lst, rep))
+        finally:
+            ctx.set_degraded_kernel("auto")
+            if case == "bad1pct":
+                flip()
+
+    kinds = [f"{c}/{kern}" for c in cases for kern in ("fused", "two_pass")] + ["scrub_fused/-"]
+    kernels_seen, statuses = {}, {}
+    for c in cases:  # untimed and checked: the same reports under both choices
+        got = {}
+        for kern in ("fused", "two_pass"):
+            rep.fill_(0xA5)
+            _, by = run(f"{c}/{kern}")
+            kernels_seen[f"{c}/{kern}"] = sorted(by)
+            got[kern] = rep.cpu().numpy().tobytes()
+        assert got["fused"] == got["two_pass"], c
+        assert "k_rs_bs_degraded" in kernels_seen[f"{c}/fused"], kernels_seen
+        r = np.frombuffer(got["fused"], ml.rsgpu.SCRUB_REPORT_DTYPE)
+        statuses[c] = {int(v): int((r["status"] == v).sum()) for v in np.unique(r["status"])}
+        if c != "bad1pct":
+            assert (r["bad_columns"] == 0).all(), c
+    run("scrub_fused/-")
+    out = {**ml.header(enc), "kernels": kernels_seen, "statuses": statuses,
+           "runs": ml.mirrored_rounds(kinds, a.rounds, run)}
+    summ = ml.summarise(out["runs"], kinds, kernel_medians=True)
+    for c in cases:
+        ratios = []
+        for rnd in range(a.rounds):
+            mine = [r for r in out["runs"] if r["round"] == rnd]
+            for half in (mine[:len(kinds)], mine[len(kinds):]):
+                ms = {r["kind"]: r["ms"] for r in half}
+                ratios.append(ms[f"{c}/fused"] / ms[f"{c}/two_pass"])
+        summ[f"{c}/fused"]["pair_ratio_to_two_pass"] = {"min": float(min(ratios)), "median": float(np.median(ratios)),
+                                                        "max": float(max(ratios))}
+    ml.finish(a.out, out, summ)
+
+
 def main():
-    a = ml.shape_parser().parse_args()
+    ap = ml.shape_parser()
+    ap.add_argument("--kernel", choices=("auto", "two_pass", "fused", "both"), default="auto")
+    a = ap.parse_args()
     k, e, L, B = a.k, a.e, a.len, a.blocks
 
     ctx, enc = ml.setup(a)
+    if a.kernel == "both":
+        both(a, ctx, enc)
+        ctx.close()
+        return
+    ctx.set_degraded_kernel(a.kernel)
     dev, pitch = enc.src.device, enc.pitch
     rep = ml.reports(enc)
     rng = np.random.default_rng(9)
