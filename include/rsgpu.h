@@ -345,7 +345,9 @@ int rsgpu_scrub_locatable(int k, int e, const unsigned char *coef);
  *             memory pool; no parity scratch, a clean tile writes nothing.
  *             Opt-in: AUTO never takes it.  rsgpu_repair_blocks and
  *             rsgpu_scrub_degraded_blocks do not use it: under GENERATED the
- *             repair runs its TWO_PASS form.  rsgpu_locate_blocks does, under
+ *             repair runs its TWO_PASS form; its own generated form is
+ *             rsgpu_set_repair_kernel's GENERATED (below, at
+ *             rsgpu_repair_blocks).  rsgpu_locate_blocks does, under
  *             rsgpu_set_locate_kernel's FUSED (below): the two settings
  *             together select the generated locate.
  *             Measured on an MI355X, 1 MB rows, 1.5 GB of rows per call, clean
@@ -818,7 +820,8 @@ typedef struct rsgpu_repair_report {
 #define RSGPU_REPAIR_COLUMNS 1 /* mode: correct every bad column exactly one row explains */
 
 /* Scrubs `blocks` blocks as rsgpu_scrub_blocks with RSGPU_SCRUB_LOCATE does
- * (same layout, geometries, kernel choice by rsgpu_set_scrub_kernel) and
+ * (same layout, geometries, kernel choice by rsgpu_set_scrub_kernel and, on
+ * top of it, rsgpu_set_repair_kernel below) and
  * corrects d_src / d_parity in place on the device; d_report [blocks] is
  * DEVICE memory, 8-byte aligned.  Enqueued on the context's stream, no
  * synchronisation and no host decision between locating and writing.
@@ -834,6 +837,52 @@ typedef struct rsgpu_repair_report {
 int rsgpu_repair_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                         unsigned char *d_src, unsigned char *d_parity,
                         const unsigned char *coef, int mode, rsgpu_repair_report *d_report);
+
+/* Repair kernel of rsgpu_repair_blocks (per context; every choice writes the
+ * same rows and the same reports):
+ *   AUTO      what rsgpu_set_scrub_kernel decides: FUSED (k_rs_bs_repair)
+ *             where it applies, otherwise TWO_PASS (the encode of all k rows
+ *             into the parity scratch, then k_repair_compare)
+ *   GENERATED the generated scrub (RSGPU_SCRUB_GENERATED above) with a
+ *             correcting cold path (k_rs_jit_repair): the shared program of
+ *             the call's matrix, the stored parity compared in registers, and
+ *             the byte of a bad column corrected where the row is named, with
+ *             all e syndromes of the column at hand.  ONE_ROW runs it twice
+ *             around the finalise (locate, then the gated correction of the
+ *             blocks that are to be written), COLUMNS once.  Applies under the
+ *             generated scrub's conditions: any matrix, with or without
+ *             `coef`, 1 <= e <= 64 (the repair itself needs a locatable matrix,
+ *             and e >= 3 for COLUMNS), 16-byte aligned rows (pitch % 16 == 0),
+ *             len % 32 == 0 and len < 4 GiB, on a device with an executable
+ *             memory pool; no encode launch, and the parity scratch is neither
+ *             touched nor grown.  Where it applies it comes before FUSED;
+ *             where it does not, the call runs what AUTO runs, silently.
+ *             Opt-in: neither the default nor AUTO takes it, and
+ *             rsgpu_set_scrub_kernel(GENERATED) alone leaves the repair on its
+ *             TWO_PASS form.
+ *             Measured on an MI355X, 1 MB rows, 1.5 GB of rows per call, kernel
+ *             times, medians of 24 runs (profiles/repair_generated/).
+ *             Clean data: COLUMNS is the GENERATED scrub's time with LOCATE
+ *             (0.996 - 1.009 of it in mirrored pairs at (10,4), (6,3), (14,32)
+ *             and (64,32), inside the run-to-run spread; 1.04 at (13,20) and
+ *             (13,24)), ONE_ROW 1.02 - 1.07 of it; against TWO_PASS (10,4) 0.38
+ *             / 0.54 ms COLUMNS and 0.40 / 0.60 ONE_ROW, (6,3) 0.40 / 0.63 and
+ *             0.43 / 0.70, (14,32) 0.30 / 0.89 and 0.30 / 1.00.  One row of
+ *             every block bad in 1 % of the columns, or in all of them: with
+ *             e >= 20 0.31 - 0.61 of TWO_PASS in both modes; with e <= 4
+ *             COLUMNS 0.83 - 1.02, but ONE_ROW 1.05 - 1.53 (its second launch
+ *             runs the whole program again, TWO_PASS only its compare).
+ *             Against FUSED at (64,32): 1.29 clean, 2.1 - 2.8 damaged.
+ *             So: GENERATED for a matrix without a compiled kernel when most
+ *             blocks are clean (what a scrub finds), in COLUMNS mode at any
+ *             damage, and at e >= 20 in either mode; ONE_ROW at small e on
+ *             heavily damaged data is better left on TWO_PASS, and the
+ *             compiled codes on FUSED.
+ * All argument checks, the UNSUPPORTED cases and the e == 0 / len == 0 paths
+ * are the same under every choice.  rsgpu_correct_blocks does not use it. */
+#define RSGPU_REPAIR_KERNEL_AUTO 0
+#define RSGPU_REPAIR_KERNEL_GENERATED 1
+int rsgpu_set_repair_kernel(rsgpu_ctx *ctx, int kernel);
 
 /* ---- correction per byte column of up to two damaged rows ------------------ */
 

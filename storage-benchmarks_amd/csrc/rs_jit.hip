@@ -131,7 +131,8 @@ alignas(16) __device__ const GfTables kGfJit = make_gf_tables();
 // parity store: scrub_tile (rs_bitsliced.hip) for a matrix known at run time.
 // The wave holds rows [r0, r0 + nrow) of the computed parity as planes in its
 // slots (SL: Slots8, SlotsW); dsts names the block's STORED parity rows, which
-// are only read.  Wave `wave` of NV of tile `tw` of the workgroup's TPW.
+// are only read (the repair, JitRepair below, writes through bases of its own).
+// Wave `wave` of NV of tile `tw` of the workgroup's TPW.
 //
 // Per row: the lane's 32 stored bytes (one row's load in flight ahead, no
 // further), one tr8 on them -- the stored side: the slot's planes are then
@@ -158,6 +159,7 @@ constexpr int kScrubMaskBytes = 2048;  // >= 4 NV TPW 64: at most 6 waves
 
 struct JitScrub {
     static constexpr bool kSpan = false;  // the cold path names one row per column
+    static constexpr bool kRepair = false;  // scrub_slots only reads the rows
     ScrubFold* fold;
     const uint8_t* tab;
     int locate;
@@ -191,11 +193,52 @@ struct JitScrub {
 // 768 B | NV TPW bases of 552 B (LocLds; N NV: the most rows the layout takes).
 struct JitLocate {
     static constexpr bool kSpan = true;  // the cold path keeps the span of the columns
+    static constexpr bool kRepair = false;
     static constexpr int locate = 1;
     ScrubFold* fold;  // hi1 counts the block's claimed slots
     uint8_t* cand;
     size_t cand_stride;
     int slots, u;
+};
+
+// The repair (rsgpu_repair_blocks under RSGPU_REPAIR_KERNEL_GENERATED;
+// k_rs_jit_repair, k_rs_jitw_repair): JitScrub's epilogue with the cold path
+// correcting in its walk, as scrub_tile (rs_bitsliced.hip) does for the
+// compiled codes.  The thread at column c of pass `pass` of tile `tw` has the
+// row, and c is byte 4 pass + c % 4 of lane c / 4's 32 bytes of the tile, so
+// the column is byte tile0 + (c >> 2) 32 + 4 pass + (c & 3) of the row: it
+// XORs x = s_0 / c[0][r] into source row r (x from the tables at `tab`, the
+// quotient scrub_locate_row tests the other syndromes against), or s_p0 into
+// parity row k + p0.  One byte read and written per bad column, in the cold
+// path only; the address comes from base, pitch and row by selects (no load
+// from the row-pointer table, whose divergent 64-bit address the wide kernels
+// have no registers for), and the write is one divergent region: address and
+// value by selects, one `if` around the store, the fold by selects.
+// In place is safe: every wave of the workgroup has read all its sources
+// before the body's last barrier; a pass of the cold path reloads, per lane and
+// row, only the stored-parity dword that pass owns (bytes 4 pass .. 4 pass + 3
+// of the lane's 32), and a correction touches bytes of that dword alone, after
+// the pass's barrier, when every wave has laid its syndromes into LDS; tiles
+// are disjoint column ranges, so no other workgroup uses those bytes -- the
+// idle lanes of a row's tail tile do re-read the row head, which the head's
+// workgroup may be correcting, but what they read is discarded (`inb`).  An
+// idle lane's syndromes are zeros, so none of its columns is bad; the column is
+// checked against len all the same before a write.
+// The modes are rs_kernels.h's: kRepairLocate folds every bad column and writes
+// no row byte; kRepairColumns corrects, folds `row` over the corrected columns
+// only and counts them in rep, one atomic per wave; kRepairGated (after the
+// finalise; the kernel has left already where the block is not to be written)
+// corrects and touches no field of the report.
+struct JitRepair {
+    static constexpr bool kSpan = false;
+    static constexpr bool kRepair = true;  // scrub_slots corrects what it locates
+    static constexpr int locate = 1;
+    RepairFold* fold;  // [B]: zeroed (kRepairLocate, kRepairColumns) or the final reports (kRepairGated)
+    const uint8_t* tab;
+    int mode;
+    uint8_t* src;  // [B][k] rows of the slice
+    uint8_t* par;  // [B][e] rows of the slice, the stored parity
+    long long pitch, len;
 };
 
 constexpr int kLocRow = 260;
@@ -211,7 +254,8 @@ struct LocLds {
 template <class SL, int NV, int TPW, class S>
 __device__ __forceinline__ void scrub_slots(const S& s, int k, int e, uint8_t* const* dsts, int b, int r0,
                                             int nrow, int wave, int tw, bool inb, uint32_t po, uint8_t* ldsb,
-                                            uint32_t m4, uint32_t m2, uint32_t m1)
+                                            uint32_t m4, uint32_t m2, uint32_t m1,
+                                            [[maybe_unused]] long long tile0 = 0)  // the repair: the tile's first column
 {
     static_assert(4 * NV * TPW * 64 <= kScrubMaskBytes, "the masks fit their part");
     // the lane index afresh: the body's copy, kept live to the end of the cold
@@ -261,12 +305,15 @@ __device__ __forceinline__ void scrub_slots(const S& s, int k, int e, uint8_t* c
     }
     if (__ballot(any != 0) == 0)
         return;  // the same for every wave of the workgroup
-    ScrubFold* f = s.fold + b;
+    auto* f = s.fold + b;
     if (wave == 0) {
         unsigned n = __builtin_popcount(tm);
         for (int o = 32; o > 0; o >>= 1)
             n += __shfl_down(n, o, 64);
-        if (lane == 0 && n)
+        bool count = lane == 0 && n;
+        if constexpr (S::kRepair)
+            count = count && s.mode != kRepairGated;  // the block's report is final
+        if (count)
             atomicAdd(&f->bad, (unsigned long long)n);
     }
     if (!s.locate)
@@ -280,7 +327,7 @@ __device__ __forceinline__ void scrub_slots(const S& s, int k, int e, uint8_t* c
     typedef __attribute__((address_space(3))) uint32_t lds_u32;
     constexpr int kRow = S::kSpan ? kLocRow : 256;
     lds_u8* syn = (lds_u8*)ldsb + kScrubMaskBytes + tw * e * kRow;
-    [[maybe_unused]] unsigned hi1 = 0, lo1 = 0;
+    [[maybe_unused]] unsigned hi1 = 0, lo1 = 0, nrep = 0;
     using Lay = LocLds<SL::N, NV, TPW>;
     [[maybe_unused]] GfTables& gf = *reinterpret_cast<GfTables*>(ldsb + Lay::kGfAt);
     [[maybe_unused]] SpanBasis* sb = reinterpret_cast<SpanBasis*>(ldsb + Lay::kBasesAt);
@@ -358,6 +405,25 @@ __device__ __forceinline__ void scrub_slots(const S& s, int k, int e, uint8_t* c
                 // locate: the matrix is locatable, so e >= 2
                 const int row = scrub_locate_row(k, e, s.tab, s.tab + 256, kGfJit, syn[c], syn[256 + c], nz, p0,
                                                  [&](int p) { return syn[p * 256 + c]; });
+                if constexpr (S::kRepair) {
+                    const bool src_row = row < k;
+                    const long long col = tile0 + (c >> 2) * 32 + 4 * pass + (c & 3);
+                    g_u8* g = (g_u8*)(src_row ? s.src : s.par) +
+                              ((size_t)b * (src_row ? k : e) + (src_row ? row : row - k)) * s.pitch + col;
+                    // x = s_0 / c[0][r] (c[0][r] != 0: the matrix is locatable), or s_p0
+                    const int ls = kGfJit.log[syn[c]] + 255 - kGfJit.log[s.tab[256 + (row >= 0 && src_row ? row : 0)]];
+                    const uint8_t x = src_row ? kGfJit.exp[ls] : syn[(src_row ? 0 : row - k) * 256 + c];
+                    if (s.mode != kRepairLocate && row >= 0 && col < s.len) {
+                        *g ^= x;
+                        ++nrep;
+                    }
+                    // what folds into `row`: every bad column (kRepairLocate), the
+                    // corrected ones (kRepairColumns), none (kRepairGated)
+                    const bool folds = s.mode == kRepairLocate || (s.mode == kRepairColumns && row >= 0);
+                    hi1 = max(hi1, !folds ? 0u : row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
+                    lo1 = max(lo1, !folds ? 0u : row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
+                    continue;
+                }
                 hi1 = max(hi1, row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
                 lo1 = max(lo1, row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
             }
@@ -386,6 +452,23 @@ __device__ __forceinline__ void scrub_slots(const S& s, int k, int e, uint8_t* c
         atomicMax(&f->hi1, hi1);
         atomicMax(&f->lo1, lo1);
     }
+    if constexpr (S::kRepair) {
+        for (int o = 32; o > 0; o >>= 1)
+            nrep += __shfl_down(nrep, o, 64);
+        if (lane == 0 && nrep && s.mode == kRepairColumns)
+            atomicAdd(&f->rep, (unsigned long long)nrep);
+    }
+}
+
+// The first column of the tile whose lanes sit at `off` (lane 0: the tile's
+// start), as a scalar, for the repair's cold path.  (From `off` and not from
+// the 32-bit offset the loads use, lane 0's where it is live: that form cost
+// k_rs_jitw_repair<J16> a VGPR pair spilled to scratch, and clean (14, 32)
+// blocks 6 % against the scrub; profiles/repair_generated/.)
+__device__ __forceinline__ long long tile_start(long long off)
+{
+    return (long long)(((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(off >> 32)) << 32) |
+                       (unsigned)__builtin_amdgcn_readfirstlane((int)off));
 }
 
 // The epilogues of k_rs_jit's body (jit_run).  The store: outputs back to
@@ -426,12 +509,19 @@ struct JitEpi8 : S {
         static_assert(!S::kSpan || LocLds<8, NW, 1>::kBytes <= 2 * C * 2 * 64 * 16,
                       "rows <= 8 NW: masks, syn, tables and bases fit the chunk buffers");
         const bool inb = off + 32 <= a.len;
-        scrub_slots<Slots8, NW, 1>(static_cast<const S&>(*this), a.k, a.rows, dsts, b, wave * 8, min(8, a.rows - wave * 8), wave, 0, inb,
-                                   inb ? (uint32_t)off : 0u, reinterpret_cast<uint8_t*>(lds), m4, m2, m1);
+        if constexpr (S::kRepair)
+            scrub_slots<Slots8, NW, 1>(static_cast<const S&>(*this), a.k, a.rows, dsts, b, wave * 8,
+                                       min(8, a.rows - wave * 8), wave, 0, inb, inb ? (uint32_t)off : 0u,
+                                       reinterpret_cast<uint8_t*>(lds), m4, m2, m1, tile_start(off));
+        else
+            scrub_slots<Slots8, NW, 1>(static_cast<const S&>(*this), a.k, a.rows, dsts, b, wave * 8,
+                                       min(8, a.rows - wave * 8), wave, 0, inb, inb ? (uint32_t)off : 0u,
+                                       reinterpret_cast<uint8_t*>(lds), m4, m2, m1);
     }
 };
 using JitScrub8 = JitEpi8<JitScrub>;
 using JitLocate8 = JitEpi8<JitLocate>;
+using JitRepair8 = JitEpi8<JitRepair>;
 
 // `int B` and `long long TILE`: this workgroup's block and its tile
 // (k_rs_jitw: its index) within the block.  Workgroups are dealt round-robin
@@ -602,6 +692,23 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void 
                                 JitLocate8{{s.fold, s.cand, s.cand_stride, s.slots, s.u}});
 }
 
+// The generated repair for e <= 16: k_rs_jit_scrub with the correcting cold
+// path (JitRepair above).  kRepairGated runs after the finalise of a
+// kRepairLocate pass on the same stream: the block's report is final, and a
+// workgroup whose block is not REPAIRED leaves before it loads anything.
+template <int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void k_rs_jit_repair(JitRepairArgs s)
+{
+    __shared__ uint4 lds[2][C * 2 * 64];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(s.j, b, tile)
+    if (s.mode == kRepairGated && s.fold[b].hi1 != kRepairGate)
+        return;  // uniform per workgroup
+    jit_run<NW, true, JitHooks>(s.j, lds, wave, lane, b, tile,
+                                JitRepair8{{s.fold, s.tab, s.mode, s.src, s.par, s.pitch, s.j.len}});
+}
+
 template <int S>
 __device__ __forceinline__ void read_slotw(uint32_t (&W)[8])
 {
@@ -714,12 +821,19 @@ struct JitwEpi : S {
         const uint32_t m4 = vconst(0x0F0F0F0Fu), m2 = vconst(0x33333333u), m1 = vconst(0x55555555u);
         const int r0 = jit::wide_row0(a.rows, wave), nrow = jit::wide_row0(a.rows, wave + 1) - r0;
         const bool inb = off + 32 <= a.len;
-        scrub_slots<SlotsW<W::R>, NV, TPW>(static_cast<const S&>(*this), a.k, a.rows, dsts, b, r0, nrow, wave, tw, inb,
-                                           inb ? (uint32_t)off : 0u, reinterpret_cast<uint8_t*>(lds), m4, m2, m1);
+        if constexpr (S::kRepair)
+            scrub_slots<SlotsW<W::R>, NV, TPW>(static_cast<const S&>(*this), a.k, a.rows, dsts, b, r0, nrow, wave, tw,
+                                               inb, inb ? (uint32_t)off : 0u, reinterpret_cast<uint8_t*>(lds), m4, m2,
+                                               m1, tile_start(off));
+        else
+            scrub_slots<SlotsW<W::R>, NV, TPW>(static_cast<const S&>(*this), a.k, a.rows, dsts, b, r0, nrow, wave, tw,
+                                               inb, inb ? (uint32_t)off : 0u, reinterpret_cast<uint8_t*>(lds), m4, m2,
+                                               m1);
     }
 };
 using JitwScrub = JitwEpi<JitScrub>;
 using JitwLocate = JitwEpi<JitLocate>;
+using JitwRepair = JitwEpi<JitRepair>;
 
 // The same decode with R rows per wave (rs_jit.h Wide): 2 waves per column
 // tile; R = 16: 168 VGPRs (3 waves per SIMD), chunks of 6 sources (6
@@ -1085,6 +1199,23 @@ __global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40)))
                          JitwLocate{{s.fold, s.cand, s.cand_stride, s.slots, s.u}});
 }
 
+// The generated repair for 16 < e <= 64: k_rs_jitw_scrub with the correcting
+// cold path (JitRepair above), gated as k_rs_jit_repair
+template <class W, int TPW, int NV>
+__global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40))) void k_rs_jitw_repair(JitRepairArgs s)
+{
+    __shared__ uint4 lds[2][TPW][W::CS * 2 * 64];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wv % NV, tw = wv / NV;
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(s.j, b, wg)
+    if (s.mode == kRepairGated && s.fold[b].hi1 != kRepairGate)
+        return;  // uniform per workgroup
+    const long long tile = wg * TPW + tw;
+    jitw_run<W, TPW, NV>(s.j, lds, wv, wave, tw, lane, b, wg, tile,
+                         JitwRepair{{s.fold, s.tab, s.mode, s.src, s.par, s.pitch, s.j.len}});
+}
+
 // every 8-byte slot a return: a call that lands in code never written
 // comes straight back
 __global__ void k_jit_fill(uint64_t* code, long long n)
@@ -1446,7 +1577,7 @@ hipError_t launch_rs_jit(const JitArgs& a, long long blocks, hipStream_t st)
 }
 
 // The grids and the kernel choice of launch_rs_jit (shared program) and
-// launch_rs_jitw, on the two kernel families that end in scrub_slots.
+// launch_rs_jitw, on the three kernel families that end in scrub_slots.
 namespace {
 
 struct ScrubFamily {
@@ -1462,6 +1593,14 @@ struct LocateFamily {
     static constexpr auto jit = &jitk::k_rs_jit_locate<NW>;
     template <class W, int TPW, int NV>
     static constexpr auto wide = &jitk::k_rs_jitw_locate<W, TPW, NV>;
+};
+
+struct RepairFamily {
+    using Args = JitRepairArgs;
+    template <int NW>
+    static constexpr auto jit = &jitk::k_rs_jit_repair<NW>;
+    template <class W, int TPW, int NV>
+    static constexpr auto wide = &jitk::k_rs_jitw_repair<W, TPW, NV>;
 };
 
 template <class F, class W>
@@ -1514,6 +1653,14 @@ hipError_t launch_rs_jit_scrub(const JitScrubArgs& s, long long blocks, hipStrea
     if (s.locate && !s.tab)
         return hipErrorInvalidValue;
     return launch_scrub_family<ScrubFamily>(s, blocks, st);
+}
+
+// writable rows a block of k (e) rows apart, as the row pointers of s.j name them
+hipError_t launch_rs_jit_repair(const JitRepairArgs& s, long long blocks, hipStream_t st)
+{
+    if (!s.tab || !s.src || !s.par || s.pitch < s.j.len || s.mode < kRepairLocate || s.mode > kRepairColumns)
+        return hipErrorInvalidValue;
+    return launch_scrub_family<RepairFamily>(s, blocks, st);
 }
 
 // a slot per tile: no workgroup's claim can pass the block's area

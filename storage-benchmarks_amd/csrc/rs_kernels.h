@@ -272,6 +272,22 @@ struct JitLocateArgs {
     int u;
 };
 hipError_t launch_rs_jit_locate(const JitLocateArgs& a, long long blocks, hipStream_t st);
+// The generated repair (k_rs_jit_repair, k_rs_jitw_repair; rsgpu_repair_blocks
+// under RSGPU_REPAIR_KERNEL_GENERATED): the generated scrub with locate, on the
+// 24-byte fold, correcting in its cold path in one of the three modes above (at
+// RepairFold).  j as JitScrubArgs::j; src and par: the writable rows that
+// j.srcs and j.dsts name, block b's at src + b k pitch and par + b e pitch;
+// tab as JitScrubArgs::tab, of a locatable matrix.
+struct JitRepairArgs {
+    JitArgs j;
+    RepairFold* fold;  // [B]: zeroed (kRepairLocate, kRepairColumns) or the final reports (kRepairGated)
+    const uint8_t* tab;
+    int mode;
+    uint8_t* src;
+    uint8_t* par;
+    long long pitch;
+};
+hipError_t launch_rs_jit_repair(const JitRepairArgs& a, long long blocks, hipStream_t st);
 // small uploads through the kernel arguments (k_put_words): bytes % 8 == 0,
 // at most sizeof(PutArgs::w)
 struct PutArgs {

@@ -498,6 +498,27 @@ int shared_program_scrub(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long
     return RSGPU_OK;
 }
 
+int shared_program_repair(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long pitch,
+                          long long blocks, const uint8_t* const* d_srcs, const uint8_t* const* d_par, uint8_t* src,
+                          uint8_t* par, RepairFold* fold, const uint8_t* tab, int mode, const char* name)
+{
+    int rc = RSGPU_OK;
+    const rsgpu_ctx::SharedProg* pg = shared_program(ctx, coef, k, e, &rc);
+    if (!pg)
+        return rc;
+    JitRepairArgs s{};
+    s.j = shared_pass_args(ctx, pg, k, e, 0, len, d_srcs, (uint8_t* const*)d_par);  // e <= 64: one pass
+    s.fold = fold;
+    s.tab = tab;
+    s.mode = mode;
+    s.src = src;
+    s.par = par;
+    s.pitch = pitch;
+    KTimer kt(ctx, name, (size_t)blocks);
+    RS_HIP(ctx, launch_rs_jit_repair(s, blocks, ctx->stream));
+    return RSGPU_OK;
+}
+
 int shared_program_locate(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long blocks,
                           const uint8_t* const* d_srcs, const uint8_t* const* d_par, ScrubFold* fold, uint8_t* cand,
                           size_t cand_stride, int slots, int u, const char* name)

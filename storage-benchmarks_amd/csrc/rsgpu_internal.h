@@ -83,6 +83,13 @@ int jit_probe(rsgpu_ctx* ctx);
 int shared_program_scrub(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long blocks,
                          const uint8_t* const* d_srcs, const uint8_t* const* d_par, ScrubFold* fold,
                          const uint8_t* tab, int locate, const char* name);
+// The generated repair on the same program with the same settings (rs_kernels.h
+// JitRepairArgs): src and par the writable rows the pointers name, `pitch`
+// bytes apart; mode one of kRepairLocate, kRepairGated, kRepairColumns.
+// Recorded as `name`.
+int shared_program_repair(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long pitch,
+                          long long blocks, const uint8_t* const* d_srcs, const uint8_t* const* d_par, uint8_t* src,
+                          uint8_t* par, RepairFold* fold, const uint8_t* tab, int mode, const char* name);
 // The generated locate on the same program with the same settings (rs_kernels.h
 // JitLocateArgs): the fold and the candidate areas of `blocks` blocks, `slots`
 // slots each.  Recorded as `name`.

@@ -421,6 +421,14 @@ int rsgpu_set_degraded_kernel(rsgpu_ctx* ctx, int kernel)
     return RSGPU_OK;
 }
 
+int rsgpu_set_repair_kernel(rsgpu_ctx* ctx, int kernel)
+{
+    if (!ctx || kernel < RSGPU_REPAIR_KERNEL_AUTO || kernel > RSGPU_REPAIR_KERNEL_GENERATED)
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_repair_kernel: unknown kernel");
+    ctx->repair_kernel = kernel;
+    return RSGPU_OK;
+}
+
 int rsgpu_scrub_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                        const unsigned char* d_src, const unsigned char* d_parity,
                        const unsigned char* coef, int flags, rsgpu_scrub_report* d_report)
@@ -534,8 +542,46 @@ int rsgpu_repair_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
     };
     if (!work)
         return finalise(0, blocks);
-    const bool fused = fused_eligible(ctx, k, e, len, pitch, d_src, d_parity, coef);
+    // GENERATED (rsgpu_set_repair_kernel): any matrix, with or without `coef`,
+    // on the rows the generated scrub takes; before FUSED where both apply
+    const bool generated = ctx->repair_kernel == RSGPU_REPAIR_KERNEL_GENERATED &&
+                           rows_aligned(len, pitch, d_src, d_parity) && len < (1ull << 32) && e <= 64 &&
+                           jit_probe(ctx) == 1;
+    const bool fused = !generated && fused_eligible(ctx, k, e, len, pitch, d_src, d_parity, coef);
     const int first_mode = mode == RSGPU_REPAIR_COLUMNS ? kRepairColumns : kRepairLocate;
+    // The matrix's shared program on a slice, correcting in its cold path: row
+    // pointers into the context's scratch and the locate tables at the head of
+    // the two-pass scratch, as the generated scrub; no parity scratch.
+    // ONE_ROW: the launch that only folds, the finalise of the slice's
+    // reports, and the gated correcting launch on the same row pointers.
+    auto generated_slice = [&](size_t b0, size_t nb) -> int {
+        const size_t src_ptr_bytes = align_up(sizeof(void*) * (size_t)k * nb, 256);
+        const size_t par_ptr_bytes = align_up(sizeof(void*) * (size_t)e * nb, 256);
+        int grc = ensure_scratch(ctx, src_ptr_bytes + par_ptr_bytes);
+        if (!grc)
+            grc = ensure_device(ctx, ctx->scrub, kScrubTabBytes);
+        if (!grc)
+            grc = upload_locator(ctx, k, e, loc);
+        if (grc)
+            return grc;
+        char* d = (char*)ctx->scratch.p;
+        uint8_t* src = d_src + b0 * k * pitch;
+        uint8_t* par = d_parity + b0 * e * pitch;
+        RS_HIP(ctx, launch_row_ptrs(src, (long long)pitch, k, (long long)nb, (const uint8_t**)d, ctx->stream));
+        RS_HIP(ctx, launch_row_ptrs(par, (long long)pitch, e, (long long)nb, (const uint8_t**)(d + src_ptr_bytes),
+                                    ctx->stream));
+        auto launch = [&](int m, const char* name) {
+            return shared_program_repair(ctx, loc.c.data(), k, e, (long long)len, (long long)pitch, (long long)nb,
+                                         (const uint8_t* const*)d, (const uint8_t* const*)(d + src_ptr_bytes), src, par,
+                                         fold + b0, (const uint8_t*)ctx->scrub.p, m, name);
+        };
+        grc = launch(first_mode, "k_rs_jit_repair");
+        if (!grc)
+            grc = finalise(b0, nb);
+        if (!grc && mode == RSGPU_REPAIR_ONE_ROW)
+            grc = launch(kRepairGated, "k_rs_jit_repair_gated");
+        return grc;
+    };
     // A slice of the scratch.  COLUMNS: the correcting compare; ONE_ROW: the
     // compare that only folds, the finalise of the slice's reports, and the
     // gated correcting compare, while the slice's computed parity is still in
@@ -565,6 +611,12 @@ int rsgpu_repair_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
         const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
         uint8_t* src = d_src + b0 * k * pitch;
         uint8_t* par = d_parity + b0 * e * pitch;
+        if (generated) {
+            rc = generated_slice(b0, nb);
+            if (rc)
+                return rc;
+            continue;
+        }
         if (!fused) {
             rc = two_pass(ctx, k, e, len, pitch, b0, nb, d_src, coef, &loc, compare);
             if (rc)

@@ -154,6 +154,15 @@ int rsgpu_internal_set_locate_group(rsgpu_ctx* ctx, long long blocks)
     return RSGPU_OK;
 }
 
+// Test hook (not part of include/rsgpu.h): the bytes of the scrub family's
+// device buffer [tables | parity scratch of the two-pass forms] as the context
+// holds it now, 0 before the first call that needed it -- for the tests of the
+// forms that must not grow it.
+long long rsgpu_internal_scrub_scratch_bytes(rsgpu_ctx* ctx)
+{
+    return ctx ? (long long)ctx->scrub.bytes : (long long)RSGPU_ERR_ARG;
+}
+
 int rsgpu_internal_rebuild_wide_layout(rsgpu_ctx* ctx, long long* out)
 {
     if (!ctx || !out || ctx->rebuild_wide.blocks == 0)

@@ -41,6 +41,7 @@ __all__ = [
     "UPDATE_NONE", "UPDATE_DELTA", "LOST_NONE", "SCRUB_UNCHECKED", "SCRUB_BAD_MATRIX",
     "SCRUB_BAD_LIST", "REBUILD_CHECK", "REBUILD_MAX_LOST", "REBUILD_KERNELS", "SCRUB_ROWS",
     "LOCATE_MAX_ROWS", "LOCATE_KERNELS", "CORRECT_REPORT_DTYPE", "DEGRADED_KERNELS",
+    "REPAIR_KERNELS",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -96,6 +97,8 @@ LOCATE_MAX_ROWS = 8
 LOCATE_KERNELS = {"auto": 0, "two_pass": 1, "fused": 2}
 # rsgpu_set_degraded_kernel choices
 DEGRADED_KERNELS = {"auto": 0, "two_pass": 1, "fused": 2}
+# rsgpu_set_repair_kernel choices
+REPAIR_KERNELS = {"auto": 0, "generated": 1}
 
 vp = C.c_void_p
 sz = C.c_size_t
@@ -155,6 +158,7 @@ _SIGS = {
     "rsgpu_set_rebuild_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_set_locate_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_set_degraded_kernel": (C.c_int, [vp, C.c_int]),
+    "rsgpu_set_repair_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_update_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, C.c_int, vp, vp, vp, vp, vp,
                                       C.c_int, vp]),
     "rsgpu_host_alloc": (C.c_int, [vp, C.POINTER(vp), sz]),
@@ -460,7 +464,7 @@ class Context:
         shared generated program with the stored parity compared in registers,
         for any matrix with e <= 64 on 16-byte aligned rows of len % 32 == 0;
         opt-in, auto never picks it.  repair_blocks runs its two-pass form
-        under it.  Together with set_locate_kernel("fused") it also opts
+        under it (its own generated form: set_repair_kernel).  Together with set_locate_kernel("fused") it also opts
         locate_blocks into the generated locate for the matrices that have no
         compiled kernel."""
         self.check(lib().rsgpu_set_scrub_kernel(self._h, SCRUB_KERNELS[kernel]),
@@ -497,6 +501,19 @@ class Context:
         set_scrub_kernel has no influence on these calls."""
         self.check(lib().rsgpu_set_degraded_kernel(self._h, DEGRADED_KERNELS[kernel]),
                    "rsgpu_set_degraded_kernel")
+
+    def set_repair_kernel(self, kernel: str) -> None:
+        """Kernel of repair_blocks (so of GpuEncoder.repair): auto | generated
+        (include/rsgpu.h rsgpu_set_repair_kernel); every choice writes the
+        same rows and reports.  auto: what set_scrub_kernel decides (fused or
+        two_pass).  generated: the matrix's shared generated program with the
+        stored parity compared in registers and the bad byte corrected in the
+        cold path, for any locatable matrix with e <= 64 on 16-byte aligned
+        rows of len % 32 == 0, before fused where both apply; no encode and
+        no parity scratch.  Where it does not apply, auto's choice, silently.
+        Opt-in."""
+        self.check(lib().rsgpu_set_repair_kernel(self._h, REPAIR_KERNELS[kernel]),
+                   "rsgpu_set_repair_kernel")
 
     def scrub_blocks(self, k, e, length, pitch, blocks, d_src, d_par, d_report, coef=None,
                      locate: bool = True) -> None:
@@ -750,7 +767,8 @@ class GpuEncoder:
     def repair(self, mode: str = "one_row") -> np.ndarray:
         """Scrubs this encoder's blocks and corrects their rows in place
         (mode one_row | columns, include/rsgpu.h rsgpu_repair_blocks); the
-        per-block reports as a structured array (REPAIR_REPORT_DTYPE).
+        per-block reports as a structured array (REPAIR_REPORT_DTYPE).  The
+        kernel is the context's (set_scrub_kernel, set_repair_kernel).
         Synchronises (the reports are copied to the host)."""
         rep = self._report(REPAIR_REPORT_DTYPE)
         self.ctx.repair_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, rep,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Compare the gfx950 device assembly of two trees, kernel by kernel.
 
-  tools/kernel_isa_diff.py OLD_TREE NEW_TREE [--allow NAME ...] [--only FILE.hip ...]
+  tools/kernel_isa_diff.py OLD_TREE NEW_TREE [--allow NAME ...] [--only FILE.hip ...] [--differing]
 
 Every storage-benchmarks_amd/csrc/*.hip of both trees is compiled with that
 tree's Makefile flags plus --cuda-device-only -S (no GPU needed).  Generated
@@ -13,7 +13,8 @@ numbers of local labels (.LBBn_m and friends) normalised.
 Prints `same` or `differs` per device function (kernels with their
 descriptors; the rest of a file, data and metadata, as one more entry) and
 exits non-zero when anything differs that no --allow NAME covers.  NAME is a
-substring of the (mangled) symbol, e.g. k_scrub_finalise.
+substring of the (mangled) symbol, e.g. k_scrub_finalise.  --differing prints
+only the entries that differ, and per file how many are the same.
 """
 import argparse
 import concurrent.futures
@@ -104,6 +105,7 @@ def main():
     ap.add_argument("new_tree")
     ap.add_argument("--allow", nargs="*", default=[], metavar="NAME", help="symbols that may differ")
     ap.add_argument("--only", nargs="*", metavar="FILE", help="compare these .hip files only (default: all)")
+    ap.add_argument("--differing", action="store_true", help="print only what differs, and a count of the rest")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
     args = ap.parse_args()
 
@@ -121,12 +123,18 @@ def main():
                 for side, tree in (("old", args.old_tree), ("new", args.new_tree)) for f in files}
         for f in files:
             old, new = (split(normalise(jobs[(side, f)].result())) for side in ("old", "new"))
+            nsame = 0
             for sym in sorted(set(old) | set(new)):
                 same = old.get(sym) == new.get(sym)
                 allowed = not same and any(a in sym for a in args.allow if sym)
                 bad += not same and not allowed
+                nsame += same
+                if same and args.differing:
+                    continue
                 print(f"{f}: {sym or '(data and metadata)'}: "
                       f"{'same' if same else 'differs (allowed)' if allowed else 'differs'}")
+            if args.differing:
+                print(f"{f}: {nsame} entries the same")
     print("no unexpected difference" if not bad else f"{bad} unexpected difference(s)", file=sys.stderr)
     return 1 if bad else 0
 
