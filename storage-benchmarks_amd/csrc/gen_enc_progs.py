@@ -29,12 +29,15 @@ Output: C++ specializations EncProg<K, E, C, R0, NR, T> with
   outs[NR * 8][2]     acc[s][b] ^= values outs[s*8+b][0] ^ outs[s*8+b][1]
 Values 0..7 are the source planes, 255 is "no operand".
 
+Last, PLANS itself as the X-macro RSGPU_BS_PLANS(X), one X(K, E, C, NW) per
+compiled code: the list rs_bitsliced.hip dispatches (k, e) on.
+
 usage: gen_enc_progs.py OUT.inc
 """
 import itertools
 import sys
 
-# (K, E, C, NW) of rs_bitsliced.hip launch_rs_bitsliced
+# (K, E, C, NW): the compiled codes; rs_bitsliced.hip has them from RSGPU_BS_PLANS
 PLANS = [(16, 4, 16, 1), (16, 8, 16, 1), (64, 32, 16, 4), (64, 16, 16, 2), (100, 20, 20, 4),
          (5, 4, 5, 1), (20, 7, 20, 1)]
 NONE = 255
@@ -229,6 +232,7 @@ def main():
             out.append(f"    static constexpr uint8_t outs[8] = {{{', '.join(map(str, outs))}}};")
             out.append("};")
     out.append(f"// {tw_n} twiddle rows, {tw_total / max(1, tw_n):.2f} XORs per row on average")
+    out.append("#define RSGPU_BS_PLANS(X) " + " ".join("X(%d, %d, %d, %d)" % p for p in PLANS))
     with open(sys.argv[1], "w") as f:
         f.write("\n".join(out) + "\n")
 

@@ -43,6 +43,10 @@
 // (k_rs_bs_degraded) reduces the syndromes of a block with known-lost rows on
 // planes before the mask (degraded_tile).
 //
+// The compiled codes are the generator's list (RSGPU_BS_PLANS in
+// enc_progs.inc); with_plan, at the end of the file, is the one dispatch from
+// a call's (k, e) to its plan, for every launcher and every query.
+//
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -955,14 +959,6 @@ __global__ __launch_bounds__(64 * NW, (bs_waves_per_simd<E, NW>())) void k_rs_bs
     }(std::make_integer_sequence<int, NW>{});
 }
 
-template <int K, int E, int C, int NW>
-hipError_t launch_scrub(const ScrubArgs& a, hipStream_t st)
-{
-    dim3 grid((unsigned)((a.len + 2047) / 2048), (unsigned)a.blocks);
-    hipLaunchKernelGGL((k_rs_bs_scrub<K, E, C, NW>), grid, dim3(64 * NW), 0, st, a);
-    return hipGetLastError();
-}
-
 // The locate: k_rs_bs_scrub with span_tile as the cold path of the epilogue.
 template <int K, int E, int C, int NW>
 __global__ __launch_bounds__(64 * NW, (bs_waves_per_simd<E, NW>())) void k_rs_bs_locate(LocArgs a)
@@ -972,14 +968,6 @@ __global__ __launch_bounds__(64 * NW, (bs_waves_per_simd<E, NW>())) void k_rs_bs
     [&]<int... Gs>(std::integer_sequence<int, Gs...>) {
         ((wave == Gs ? run_group<K, E, C, NW, Gs, true, LocArgs>(a, lds) : void()), ...);
     }(std::make_integer_sequence<int, NW>{});
-}
-
-template <int K, int E, int C, int NW>
-hipError_t launch_locate(const LocArgs& a, hipStream_t st)
-{
-    dim3 grid((unsigned)((a.len + 2047) / 2048), (unsigned)a.blocks);
-    hipLaunchKernelGGL((k_rs_bs_locate<K, E, C, NW>), grid, dim3(64 * NW), 0, st, a);
-    return hipGetLastError();
 }
 
 // The repair: k_rs_bs_scrub with the correcting epilogue.  kRepairGated runs
@@ -996,14 +984,6 @@ __global__ __launch_bounds__(64 * NW, (bs_waves_per_simd<E, NW>())) void k_rs_bs
     [&]<int... Gs>(std::integer_sequence<int, Gs...>) {
         ((wave == Gs ? run_group<K, E, C, NW, Gs, true, RepairArgs>(a, lds) : void()), ...);
     }(std::make_integer_sequence<int, NW>{});
-}
-
-template <int K, int E, int C, int NW>
-hipError_t launch_repair(const RepairArgs& a, hipStream_t st)
-{
-    dim3 grid((unsigned)((a.len + 2047) / 2048), (unsigned)a.blocks);
-    hipLaunchKernelGGL((k_rs_bs_repair<K, E, C, NW>), grid, dim3(64 * NW), 0, st, a);
-    return hipGetLastError();
 }
 
 // The degraded scrub: k_rs_bs_scrub with degraded_tile as the epilogue.  A
@@ -1023,14 +1003,6 @@ __global__ __launch_bounds__(64 * NW, (bs_waves_per_simd<E, NW>())) void k_rs_bs
     [&]<int... Gs>(std::integer_sequence<int, Gs...>) {
         (void)((wave == Gs && (run_group<K, E, C, NW, Gs, true, DegArgs>(a, lds), true)) || ...);
     }(std::make_integer_sequence<int, NW>{});
-}
-
-template <int K, int E, int C, int NW>
-hipError_t launch_degraded(const DegArgs& a, hipStream_t st)
-{
-    dim3 grid((unsigned)((a.len + 2047) / 2048), (unsigned)a.blocks);
-    hipLaunchKernelGGL((k_rs_bs_degraded<K, E, C, NW>), grid, dim3(64 * NW), 0, st, a);
-    return hipGetLastError();
 }
 
 // Small batches of a single-chunk code (C == K, E <= 8; C2: one block of
@@ -1355,37 +1327,82 @@ hipError_t launch(const uint8_t* src, uint8_t* out, long long pitch, long long l
 
 RSGPU_DIAG_READER(diag_read_bs)
 
+// One compiled code (RSGPU_BS_PLANS, enc_progs.inc) as a type.  kSplit: the
+// codes of the split kernels (k_rs_bs_split, k_rs_syn_split), a single chunk
+// and one row group.
+template <int K_, int E_, int C_, int NW_>
+struct Plan {
+    static constexpr int K = K_, E = E_, C = C_, NW = NW_;
+    static constexpr bool kSplit = C == K && E <= 8;
+};
+
+// the split subset is (16, 4), (16, 8), (5, 4) and (20, 7), no more and no less
+#define X(K, E, C, NW) \
+    static_assert(Plan<K, E, C, NW>::kSplit == ((K == 16 && (E == 4 || E == 8)) || (K == 5 && E == 4) || (K == 20 && E == 7)));
+RSGPU_BS_PLANS(X)
+#undef X
+#define X(K, E, C, NW) +Plan<K, E, C, NW>::kSplit
+static_assert(0 RSGPU_BS_PLANS(X) == 4);
+#undef X
+
+// The one dispatch from a call's (k, e) to its compile-time plan:
+// f(Plan<K, E, C, NW>{}), or `none` for a code that is not compiled.
+template <class R, class F>
+R with_plan(int k, int e, R none, F&& f)
+{
+#define X(K, E, C, NW) \
+    if (k == K && e == E) \
+        return f(Plan<K, E, C, NW>{});
+    RSGPU_BS_PLANS(X)
+#undef X
+    return none;
+}
+
+// what the scrub, the locate, the degraded scrub and the repair ask of their rows
+bool family_rows(long long blocks, long long len, long long pitch, const void* src, const void* par, const void* fold)
+{
+    return blocks > 0 && blocks <= 65535 && len > 0 && len % 32 == 0 && len < (1ll << 32) && pitch >= len && src &&
+           par && fold;
+}
+
+// One launch of the plan's kernel of a scrub-family form, kernel_of(plan), on
+// that form's Args: a workgroup of NW waves per tile and block.
+template <class A, class KernelOf>
+hipError_t launch_family(int k, int e, const A& a, hipStream_t st, KernelOf&& kernel_of)
+{
+    return with_plan(k, e, hipErrorInvalidValue, [&](auto p) {
+        dim3 grid((unsigned)((a.len + 2047) / 2048), (unsigned)a.blocks);
+        hipLaunchKernelGGL(kernel_of(p), grid, dim3(64 * p.NW), 0, st, a);
+        return hipGetLastError();
+    });
+}
+
 }  // namespace bs
 
 bool rs_bitsliced_available(int k, int e)
 {
-    return (k == 16 && e == 4) || (k == 16 && e == 8) || (k == 64 && e == 32) ||
-           (k == 100 && e == 20) || (k == 5 && e == 4) || (k == 20 && e == 7) ||
-           (k == 64 && e == 16);
+    return bs::with_plan(k, e, false, [](auto) { return true; });
 }
 
 int rs_bitsliced_rows_per_wave(int k, int e)
 {
-    // (E + NW - 1) / NW of launch_rs_bitsliced's plans
-    if (!rs_bitsliced_available(k, e))
-        return 0;
-    const int nw = (k == 64 && e == 32) || (k == 100 && e == 20) ? 4 : (k == 64 && e == 16) ? 2 : 1;
-    return (e + nw - 1) / nw;
+    return bs::with_plan(k, e, 0, [](auto p) { return (p.E + p.NW - 1) / p.NW; });
 }
 
 bool rs_bitsliced_split_available(int k, int e)
 {
-    return (k == 16 && e == 4) || (k == 16 && e == 8) || (k == 5 && e == 4) || (k == 20 && e == 7);
+    return bs::with_plan(k, e, false, [](auto p) { return p.kSplit; });
 }
 
 hipError_t launch_rs_bitsliced_split(int k, int e, const uint8_t* src, uint8_t* out, long long pitch,
                                      long long len, long long blocks, hipStream_t st)
 {
-    if (k == 16 && e == 4) return bs::launch_split<16, 4>(src, out, pitch, len, blocks, st);
-    if (k == 16 && e == 8) return bs::launch_split<16, 8>(src, out, pitch, len, blocks, st);
-    if (k == 5 && e == 4) return bs::launch_split<5, 4>(src, out, pitch, len, blocks, st);
-    if (k == 20 && e == 7) return bs::launch_split<20, 7>(src, out, pitch, len, blocks, st);
-    return hipErrorInvalidValue;
+    return bs::with_plan(k, e, hipErrorInvalidValue, [&](auto p) {
+        if constexpr (p.kSplit)
+            return bs::launch_split<p.K, p.E>(src, out, pitch, len, blocks, st);
+        else
+            return hipErrorInvalidValue;
+    });
 }
 
 hipError_t launch_rs_syn_split(int k, int e, const SynArgs& a, long long blocks, hipStream_t st)
@@ -1393,97 +1410,60 @@ hipError_t launch_rs_syn_split(int k, int e, const SynArgs& a, long long blocks,
     if (blocks <= 0 || blocks > 65535 || a.len <= 0 || a.len % 32 != 0 || !a.src || !a.par || !a.out || !a.err ||
         !a.status)
         return hipErrorInvalidValue;
-    if (k == 16 && e == 4) return bs::launch_syn<16, 4>(a, blocks, st);
-    if (k == 16 && e == 8) return bs::launch_syn<16, 8>(a, blocks, st);
-    if (k == 5 && e == 4) return bs::launch_syn<5, 4>(a, blocks, st);
-    if (k == 20 && e == 7) return bs::launch_syn<20, 7>(a, blocks, st);
-    return hipErrorInvalidValue;
+    return bs::with_plan(k, e, hipErrorInvalidValue, [&](auto p) {
+        if constexpr (p.kSplit)
+            return bs::launch_syn<p.K, p.E>(a, blocks, st);
+        else
+            return hipErrorInvalidValue;
+    });
 }
 
 hipError_t launch_rs_bitsliced(int k, int e, const uint8_t* src, uint8_t* out, long long pitch,
                                long long len, long long blocks, hipStream_t st, int prio)
 {
-    if (k == 16 && e == 4) return bs::launch<16, 4, 16, 1>(src, out, pitch, len, blocks, st, prio);
-    if (k == 16 && e == 8) return bs::launch<16, 8, 16, 1>(src, out, pitch, len, blocks, st, prio);
-    if (k == 64 && e == 32) return bs::launch<64, 32, 16, 4>(src, out, pitch, len, blocks, st, prio);
-    if (k == 64 && e == 16) return bs::launch<64, 16, 16, 2>(src, out, pitch, len, blocks, st, prio);
-    if (k == 100 && e == 20) return bs::launch<100, 20, 20, 4>(src, out, pitch, len, blocks, st, prio);
-    if (k == 5 && e == 4) return bs::launch<5, 4, 5, 1>(src, out, pitch, len, blocks, st, prio);
-    if (k == 20 && e == 7) return bs::launch<20, 7, 20, 1>(src, out, pitch, len, blocks, st, prio);
-    return hipErrorInvalidValue;
+    return bs::with_plan(k, e, hipErrorInvalidValue, [&](auto p) {
+        return bs::launch<p.K, p.E, p.C, p.NW>(src, out, pitch, len, blocks, st, prio);
+    });
 }
 
-// the plans (K, E, C, NW) of launch_rs_bitsliced
 hipError_t launch_rs_bitsliced_scrub(int k, int e, const uint8_t* src, const uint8_t* par, long long pitch,
                                      long long len, long long blocks, ScrubFold* fold, int locate,
                                      hipStream_t st)
 {
-    if (blocks <= 0 || blocks > 65535 || len <= 0 || len % 32 != 0 || len >= (1ll << 32) || pitch < len ||
-        !src || !par || !fold)
+    if (!bs::family_rows(blocks, len, pitch, src, par, fold))
         return hipErrorInvalidValue;
     const bs::ScrubArgs a{src, par, pitch, len, blocks, fold, locate};
-    if (k == 16 && e == 4) return bs::launch_scrub<16, 4, 16, 1>(a, st);
-    if (k == 16 && e == 8) return bs::launch_scrub<16, 8, 16, 1>(a, st);
-    if (k == 64 && e == 32) return bs::launch_scrub<64, 32, 16, 4>(a, st);
-    if (k == 64 && e == 16) return bs::launch_scrub<64, 16, 16, 2>(a, st);
-    if (k == 100 && e == 20) return bs::launch_scrub<100, 20, 20, 4>(a, st);
-    if (k == 5 && e == 4) return bs::launch_scrub<5, 4, 5, 1>(a, st);
-    if (k == 20 && e == 7) return bs::launch_scrub<20, 7, 20, 1>(a, st);
-    return hipErrorInvalidValue;
+    return bs::launch_family(k, e, a, st, [](auto p) { return bs::k_rs_bs_scrub<p.K, p.E, p.C, p.NW>; });
 }
 
 hipError_t launch_rs_bitsliced_locate(int k, int e, const uint8_t* src, const uint8_t* par, long long pitch,
                                       long long len, long long blocks, ScrubFold* fold, uint8_t* cand,
                                       size_t cand_stride, int u, hipStream_t st)
 {
-    if (blocks <= 0 || blocks > 65535 || len <= 0 || len % 32 != 0 || len >= (1ll << 32) || pitch < len ||
-        !src || !par || !fold || !cand || u < 1 || u > kLocMax ||
+    if (!bs::family_rows(blocks, len, pitch, src, par, fold) || !cand || u < 1 || u > kLocMax ||
         cand_stride < (size_t)((len + 2047) / 2048) * kLocateSlotBytes)
         return hipErrorInvalidValue;
     const bs::LocArgs a{src, par, pitch, len, blocks, fold, cand, cand_stride, u};
-    if (k == 16 && e == 4) return bs::launch_locate<16, 4, 16, 1>(a, st);
-    if (k == 16 && e == 8) return bs::launch_locate<16, 8, 16, 1>(a, st);
-    if (k == 64 && e == 32) return bs::launch_locate<64, 32, 16, 4>(a, st);
-    if (k == 64 && e == 16) return bs::launch_locate<64, 16, 16, 2>(a, st);
-    if (k == 100 && e == 20) return bs::launch_locate<100, 20, 20, 4>(a, st);
-    if (k == 5 && e == 4) return bs::launch_locate<5, 4, 5, 1>(a, st);
-    if (k == 20 && e == 7) return bs::launch_locate<20, 7, 20, 1>(a, st);
-    return hipErrorInvalidValue;
+    return bs::launch_family(k, e, a, st, [](auto p) { return bs::k_rs_bs_locate<p.K, p.E, p.C, p.NW>; });
 }
 
 hipError_t launch_rs_bitsliced_degraded(int k, int e, const uint8_t* src, const uint8_t* par, long long pitch,
                                         long long len, long long blocks, const uint8_t* tab, ScrubFold* fold,
                                         int locate, hipStream_t st)
 {
-    if (blocks <= 0 || blocks > 65535 || len <= 0 || len % 32 != 0 || len >= (1ll << 32) || pitch < len ||
-        !src || !par || !tab || !fold || (uintptr_t)tab % 16 != 0)
+    if (!bs::family_rows(blocks, len, pitch, src, par, fold) || !tab || (uintptr_t)tab % 16 != 0)
         return hipErrorInvalidValue;
     const bs::DegArgs a{src, par, pitch, len, blocks, tab, fold, locate};
-    if (k == 16 && e == 4) return bs::launch_degraded<16, 4, 16, 1>(a, st);
-    if (k == 16 && e == 8) return bs::launch_degraded<16, 8, 16, 1>(a, st);
-    if (k == 64 && e == 32) return bs::launch_degraded<64, 32, 16, 4>(a, st);
-    if (k == 64 && e == 16) return bs::launch_degraded<64, 16, 16, 2>(a, st);
-    if (k == 100 && e == 20) return bs::launch_degraded<100, 20, 20, 4>(a, st);
-    if (k == 5 && e == 4) return bs::launch_degraded<5, 4, 5, 1>(a, st);
-    if (k == 20 && e == 7) return bs::launch_degraded<20, 7, 20, 1>(a, st);
-    return hipErrorInvalidValue;
+    return bs::launch_family(k, e, a, st, [](auto p) { return bs::k_rs_bs_degraded<p.K, p.E, p.C, p.NW>; });
 }
 
 hipError_t launch_rs_bitsliced_repair(int k, int e, uint8_t* src, uint8_t* par, long long pitch, long long len,
                                       long long blocks, RepairFold* fold, int mode, hipStream_t st)
 {
-    if (blocks <= 0 || blocks > 65535 || len <= 0 || len % 32 != 0 || len >= (1ll << 32) || pitch < len ||
-        !src || !par || !fold || mode < kRepairLocate || mode > kRepairColumns)
+    if (!bs::family_rows(blocks, len, pitch, src, par, fold) || mode < kRepairLocate || mode > kRepairColumns)
         return hipErrorInvalidValue;
     const bs::RepairArgs a{src, par, pitch, len, blocks, fold, mode};
-    if (k == 16 && e == 4) return bs::launch_repair<16, 4, 16, 1>(a, st);
-    if (k == 16 && e == 8) return bs::launch_repair<16, 8, 16, 1>(a, st);
-    if (k == 64 && e == 32) return bs::launch_repair<64, 32, 16, 4>(a, st);
-    if (k == 64 && e == 16) return bs::launch_repair<64, 16, 16, 2>(a, st);
-    if (k == 100 && e == 20) return bs::launch_repair<100, 20, 20, 4>(a, st);
-    if (k == 5 && e == 4) return bs::launch_repair<5, 4, 5, 1>(a, st);
-    if (k == 20 && e == 7) return bs::launch_repair<20, 7, 20, 1>(a, st);
-    return hipErrorInvalidValue;
+    return bs::launch_family(k, e, a, st, [](auto p) { return bs::k_rs_bs_repair<p.K, p.E, p.C, p.NW>; });
 }
 
 }  // namespace rsgpu

@@ -381,11 +381,7 @@ int karatsuba_launch(rsgpu_ctx* ctx, long long len, size_t pitch, size_t blocks,
     const int k = 64, e = 32;
     *unavailable = false;
     const std::vector<uint8_t> c = parity_matrix(k, e, nullptr);
-    const size_t src_ptr_bytes = align_up(sizeof(void*) * (size_t)k * blocks, 256);
-    const size_t dst_ptr_bytes = align_up(sizeof(void*) * (size_t)e * blocks, 256);
-    int rc = ensure_scratch(ctx, src_ptr_bytes + dst_ptr_bytes);
-    if (rc)
-        return rc;
+    int rc = RSGPU_OK;
     const std::string err_before = ctx->err;
     const rsgpu_ctx::SharedProg* pg = shared_program(ctx, c.data(), k, e, &rc, true);
     if (!pg && rc == RSGPU_ERR_UNSUPPORTED) {
@@ -396,12 +392,11 @@ int karatsuba_launch(rsgpu_ctx* ctx, long long len, size_t pitch, size_t blocks,
     }
     if (!pg)
         return rc;
-    char* d = (char*)ctx->scratch.p;
-    RS_HIP(ctx, launch_row_ptrs(d_src, (long long)pitch, k, (long long)blocks, (const uint8_t**)d, ctx->stream));
-    RS_HIP(ctx, launch_row_ptrs(d_parity, (long long)pitch, e, (long long)blocks,
-                                (const uint8_t**)(d + src_ptr_bytes), ctx->stream));
-    JitArgs j = jit_args((const uint8_t* const*)d, (uint8_t* const*)(d + src_ptr_bytes), pg->code, pg->chunk_stride,
-                         0, k, e, e, len, nullptr);
+    RowPtrs rp;
+    rc = row_ptr_tables(ctx, k, e, pitch, blocks, d_src, d_parity, rp);
+    if (rc)
+        return rc;
+    JitArgs j = jit_args(rp.src, rp.par, pg->code, pg->chunk_stride, 0, k, e, e, len, nullptr);
     j.chunk_rot_ticks = ctx->jitw_rot >= 0 ? ctx->jitw_rot : kKaraRotTicks;
     j.prio = ctx->jitw_prio;
     KTimer kt(ctx, "k_rs_jit(encode)", blocks);
@@ -460,83 +455,43 @@ int encode_slice(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t 
         return RSGPU_OK;
     }
     const std::vector<uint8_t> c = parity_matrix(k, e, coef);
-    const size_t src_ptr_bytes = align_up(sizeof(void*) * (size_t)k * blocks, 256);
-    const size_t dst_ptr_bytes = align_up(sizeof(void*) * (size_t)e * blocks, 256);
-    const int rc = ensure_scratch(ctx, src_ptr_bytes + dst_ptr_bytes + dot_table_bytes(k, e));
+    RowPtrs rp;
+    const int rc = row_ptr_tables(ctx, k, e, pitch, blocks, d_src, d_parity, rp, dot_table_bytes(k, e));
     if (rc)
         return rc;
-    char* d = (char*)ctx->scratch.p;
-    RS_HIP(ctx, launch_row_ptrs(d_src, (long long)pitch, k, (long long)blocks,
-                                (const uint8_t**)d, ctx->stream));
-    RS_HIP(ctx, launch_row_ptrs(d_parity, (long long)pitch, e, (long long)blocks,
-                                (const uint8_t**)(d + src_ptr_bytes), ctx->stream));
-    return dot_from_host_coef(ctx, c.data(), k, e, (long long)len, (long long)blocks,
-                              (const uint8_t* const*)d, (uint8_t* const*)(d + src_ptr_bytes),
-                              src_ptr_bytes + dst_ptr_bytes, aligned, "k_rs_tc(encode)",
-                              "k_rs_jit(encode)");
+    return dot_from_host_coef(ctx, c.data(), k, e, (long long)len, (long long)blocks, rp.src, rp.par, rp.bytes,
+                              aligned, "k_rs_tc(encode)", "k_rs_jit(encode)");
 }
 
 }  // namespace
 
 namespace rsgpu {
 
-int shared_program_scrub(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long blocks,
-                         const uint8_t* const* d_srcs, const uint8_t* const* d_par, ScrubFold* fold,
-                         const uint8_t* tab, int locate, const char* name)
+int row_ptr_tables(rsgpu_ctx* ctx, int k, int e, size_t pitch, size_t blocks, const uint8_t* d_src,
+                   const uint8_t* d_par, RowPtrs& rp, size_t extra)
 {
-    int rc = RSGPU_OK;
-    const rsgpu_ctx::SharedProg* pg = shared_program(ctx, coef, k, e, &rc);
-    if (!pg)
+    const size_t src_bytes = align_up(sizeof(void*) * (size_t)k * blocks, 256);
+    rp.bytes = src_bytes + align_up(sizeof(void*) * (size_t)e * blocks, 256);
+    const int rc = ensure_scratch(ctx, rp.bytes + extra);
+    if (rc)
         return rc;
-    JitScrubArgs s{};
-    s.j = shared_pass_args(ctx, pg, k, e, 0, len, d_srcs, (uint8_t* const*)d_par);  // e <= 64: one pass
-    s.fold = fold;
-    s.tab = tab;
-    s.locate = locate;
-    KTimer kt(ctx, name, (size_t)blocks);
-    RS_HIP(ctx, launch_rs_jit_scrub(s, blocks, ctx->stream));
+    char* d = (char*)ctx->scratch.p;
+    rp.src = (const uint8_t* const*)d;
+    rp.par = (uint8_t* const*)(d + src_bytes);
+    RS_HIP(ctx, launch_row_ptrs(d_src, (long long)pitch, k, (long long)blocks, (const uint8_t**)d, ctx->stream));
+    RS_HIP(ctx, launch_row_ptrs(d_par, (long long)pitch, e, (long long)blocks, (const uint8_t**)(d + src_bytes),
+                                ctx->stream));
     return RSGPU_OK;
 }
 
-int shared_program_repair(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long pitch,
-                          long long blocks, const uint8_t* const* d_srcs, const uint8_t* const* d_par, uint8_t* src,
-                          uint8_t* par, RepairFold* fold, const uint8_t* tab, int mode, const char* name)
+int shared_epilogue_args(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, const RowPtrs& rp,
+                         JitArgs& j)
 {
     int rc = RSGPU_OK;
     const rsgpu_ctx::SharedProg* pg = shared_program(ctx, coef, k, e, &rc);
-    if (!pg)
-        return rc;
-    JitRepairArgs s{};
-    s.j = shared_pass_args(ctx, pg, k, e, 0, len, d_srcs, (uint8_t* const*)d_par);  // e <= 64: one pass
-    s.fold = fold;
-    s.tab = tab;
-    s.mode = mode;
-    s.src = src;
-    s.par = par;
-    s.pitch = pitch;
-    KTimer kt(ctx, name, (size_t)blocks);
-    RS_HIP(ctx, launch_rs_jit_repair(s, blocks, ctx->stream));
-    return RSGPU_OK;
-}
-
-int shared_program_locate(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long blocks,
-                          const uint8_t* const* d_srcs, const uint8_t* const* d_par, ScrubFold* fold, uint8_t* cand,
-                          size_t cand_stride, int slots, int u, const char* name)
-{
-    int rc = RSGPU_OK;
-    const rsgpu_ctx::SharedProg* pg = shared_program(ctx, coef, k, e, &rc);
-    if (!pg)
-        return rc;
-    JitLocateArgs s{};
-    s.j = shared_pass_args(ctx, pg, k, e, 0, len, d_srcs, (uint8_t* const*)d_par);  // e <= 64: one pass
-    s.fold = fold;
-    s.cand = cand;
-    s.cand_stride = cand_stride;
-    s.slots = slots;
-    s.u = u;
-    KTimer kt(ctx, name, (size_t)blocks);
-    RS_HIP(ctx, launch_rs_jit_locate(s, blocks, ctx->stream));
-    return RSGPU_OK;
+    if (pg)
+        j = shared_pass_args(ctx, pg, k, e, 0, len, rp.src, rp.par);  // e <= 64: one pass
+    return rc;
 }
 
 const GfTables& host_gf()

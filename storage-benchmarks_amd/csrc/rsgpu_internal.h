@@ -74,28 +74,25 @@ bool tc_handlers_ready(rsgpu_ctx* ctx);
 // once per context
 int jit_probe(rsgpu_ctx* ctx);
 
-// The generated scrub of `blocks` blocks on the shared program of the e x k
-// matrix `coef` (e <= 64, jit_probe(ctx) == 1; the program the GENERATED encode
-// of the same matrix runs, built on first use), with the encode's launch
-// settings: d_srcs [B][k] and d_par [B][e] row pointers (16-byte aligned rows,
-// len % 32 == 0, the parity only read), rs_kernels.h JitScrubArgs for the
-// rest.  Recorded as `name`.
-int shared_program_scrub(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long blocks,
-                         const uint8_t* const* d_srcs, const uint8_t* const* d_par, ScrubFold* fold,
-                         const uint8_t* tab, int locate, const char* name);
-// The generated repair on the same program with the same settings (rs_kernels.h
-// JitRepairArgs): src and par the writable rows the pointers name, `pitch`
-// bytes apart; mode one of kRepairLocate, kRepairGated, kRepairColumns.
-// Recorded as `name`.
-int shared_program_repair(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long pitch,
-                          long long blocks, const uint8_t* const* d_srcs, const uint8_t* const* d_par, uint8_t* src,
-                          uint8_t* par, RepairFold* fold, const uint8_t* tab, int mode, const char* name);
-// The generated locate on the same program with the same settings (rs_kernels.h
-// JitLocateArgs): the fold and the candidate areas of `blocks` blocks, `slots`
-// slots each.  Recorded as `name`.
-int shared_program_locate(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, long long blocks,
-                          const uint8_t* const* d_srcs, const uint8_t* const* d_par, ScrubFold* fold, uint8_t* cand,
-                          size_t cand_stride, int slots, int u, const char* name);
+// The row-pointer tables [blocks][k] of d_src and [blocks][e] of d_par (rows
+// `pitch` bytes apart) at the head of the context's scratch, which is grown to
+// hold them and `extra` bytes behind them (from `bytes` on) before the two
+// launches that fill them are enqueued.
+struct RowPtrs {
+    const uint8_t* const* src;
+    uint8_t* const* par;
+    size_t bytes;
+};
+int row_ptr_tables(rsgpu_ctx* ctx, int k, int e, size_t pitch, size_t blocks, const uint8_t* d_src,
+                   const uint8_t* d_par, RowPtrs& rp, size_t extra = 0);
+
+// j: what the generated scrub, repair and locate (rs_kernels.h JitScrubArgs,
+// JitRepairArgs, JitLocateArgs) launch with on the tables rp: the shared
+// program of the e x k matrix `coef` (e <= 64, jit_probe(ctx) == 1; the program
+// the GENERATED encode of the same matrix runs, built on first use) with the
+// encode's launch settings; 16-byte aligned rows, len % 32 == 0.
+int shared_epilogue_args(rsgpu_ctx* ctx, const uint8_t* coef, int k, int e, long long len, const RowPtrs& rp,
+                         JitArgs& j);
 
 // >= bytes of executable device memory at ctx->d_jit, a new generation when regrown
 int jit_ensure(rsgpu_ctx* ctx, size_t bytes);

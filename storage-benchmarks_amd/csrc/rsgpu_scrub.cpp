@@ -123,6 +123,42 @@ int upload_locator(rsgpu_ctx* ctx, int k, int e, const Locator& loc)
     return rc;
 }
 
+// The rows the generated forms take (k_rs_jit_scrub, k_rs_jit_repair,
+// k_rs_jit_locate and their wide kin).  jit_probe probes the device on a
+// context's first call: ask only where the call's kernel choice wants the
+// generated form, so that no other call ever probes.
+bool generated_rows(rsgpu_ctx* ctx, int e, size_t len, size_t pitch, const void* d_src, const void* d_parity)
+{
+    return rows_aligned(len, pitch, d_src, d_parity) && len < (1ull << 32) && e <= 64 && jit_probe(ctx) == 1;
+}
+
+// What a generated slice of nb blocks at src / par needs before its launch:
+// the scrub table buffer, the tables of `loc` (when given) at its head, the
+// row pointers in the context's scratch, and in s.j the launch of the shared
+// program of the matrix c on them.  No parity scratch.
+template <class Args>
+int generated_prepare(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t nb, const uint8_t* src,
+                      const uint8_t* par, const uint8_t* c, const Locator* loc, Args& s)
+{
+    int rc = ensure_device(ctx, ctx->scrub, kScrubTabBytes);
+    if (!rc && loc)
+        rc = upload_locator(ctx, k, e, *loc);
+    RowPtrs rp;
+    if (!rc)
+        rc = row_ptr_tables(ctx, k, e, pitch, nb, src, par, rp);
+    return rc ? rc : shared_epilogue_args(ctx, c, k, e, (long long)len, rp, s.j);
+}
+
+// ... and the launch itself, recorded as `name`
+template <class Args>
+int generated_launch(rsgpu_ctx* ctx, const Args& s, size_t nb, const char* name,
+                     hipError_t (*launch)(const Args&, long long, hipStream_t))
+{
+    KTimer kt(ctx, name, nb);
+    RS_HIP(ctx, launch(s, (long long)nb, ctx->stream));
+    return RSGPU_OK;
+}
+
 // The two-pass walk over blocks [first, first + count) of d_src: the scratch
 // grown, the tables of `loc` (when given) at its head, uploaded when it holds
 // another matrix's; then slice by slice the encode into the scratch and
@@ -264,6 +300,33 @@ constexpr const char* kRebuildPassNames[3] = {"k_rebuild_blocks(pass)", "k_rebui
 
 size_t round16(size_t n) { return (n + 15) / 16 * 16; }
 
+// What the narrow and the wide rebuild fill alike of RebuildArgs, for blocks
+// [g0, g0 + ng); the tables' place and the lane group are the caller's.
+RebuildArgs rebuild_args(const rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t g0, size_t ng,
+                         unsigned char* d_src, unsigned char* d_parity, int u, const unsigned char* d_lost, bool check,
+                         rsgpu_scrub_report* d_report)
+{
+    const bool work = e > 0 && len > 0;
+    RebuildArgs a{};
+    a.k = k;
+    a.e = e;
+    a.u = u;
+    a.check = check && work ? 1 : 0;
+    a.work = work ? 1 : 0;
+    a.pitch = (long long)pitch;
+    a.len = (long long)len;
+    a.blocks = (long long)ng;
+    a.lost = d_lost + g0 * (size_t)u;
+    a.src_bytes = rebuild_src_bytes(k);
+    a.report = d_report + g0;
+    if (work) {
+        a.src = d_src + g0 * (size_t)k * pitch;
+        a.par = d_parity + g0 * (size_t)e * pitch;
+        set_tables(a, ctx);
+    }
+    return a;
+}
+
 // The rebuild of lists that the narrow prepare does not take (u > 8), and of
 // any list under THREADED.  Per group of blocks: k_rebuild_wide_prepare, then
 //   threaded   k_rs_tc with a row count per block over [0, len - len % 32) and
@@ -313,24 +376,9 @@ int rebuild_wide(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t 
         const size_t ng = std::min(group, blocks - g0);
         RebuildWideArgs wa{};
         RebuildArgs& a = wa.r;
-        a.k = k;
-        a.e = e;
-        a.u = u;
-        a.check = check && work ? 1 : 0;
-        a.work = work ? 1 : 0;
-        a.pitch = (long long)pitch;
-        a.len = (long long)len;
-        a.blocks = (long long)ng;
-        a.lost = d_lost + g0 * (size_t)u;
+        a = rebuild_args(ctx, k, e, len, pitch, g0, ng, d_src, d_parity, u, d_lost, check, d_report);
         a.tab = passes ? (uint8_t*)base + lay.lane : nullptr;
         a.tab_stride = lane_stride;
-        a.src_bytes = rebuild_src_bytes(k);
-        a.report = d_report + g0;
-        if (work) {
-            a.src = d_src + g0 * (size_t)k * pitch;
-            a.par = d_parity + g0 * (size_t)e * pitch;
-            set_tables(a, ctx);
-        }
         wa.passes = passes;
         wa.slots = slots;
         if (slots) {
@@ -377,6 +425,15 @@ int rebuild_wide(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t 
     return RSGPU_OK;
 }
 
+// the five kernel choices: 0 (AUTO) to `last` into the context's member
+int set_kernel(rsgpu_ctx* ctx, int kernel, int last, int rsgpu_ctx::*choice, const char* msg)
+{
+    if (!ctx || kernel < 0 || kernel > last)
+        return fail(ctx, RSGPU_ERR_ARG, msg);
+    ctx->*choice = kernel;
+    return RSGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -391,42 +448,27 @@ int rsgpu_scrub_locatable(int k, int e, const unsigned char* coef)
 
 int rsgpu_set_scrub_kernel(rsgpu_ctx* ctx, int kernel)
 {
-    if (!ctx || kernel < RSGPU_SCRUB_AUTO || kernel > RSGPU_SCRUB_GENERATED)
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_scrub_kernel: unknown kernel");
-    ctx->scrub_kernel = kernel;
-    return RSGPU_OK;
+    return set_kernel(ctx, kernel, RSGPU_SCRUB_GENERATED, &rsgpu_ctx::scrub_kernel, "rsgpu_set_scrub_kernel: unknown kernel");
 }
 
 int rsgpu_set_rebuild_kernel(rsgpu_ctx* ctx, int kernel)
 {
-    if (!ctx || kernel < RSGPU_REBUILD_AUTO || kernel > RSGPU_REBUILD_THREADED)
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_rebuild_kernel: unknown kernel");
-    ctx->rebuild_kernel = kernel;
-    return RSGPU_OK;
+    return set_kernel(ctx, kernel, RSGPU_REBUILD_THREADED, &rsgpu_ctx::rebuild_kernel, "rsgpu_set_rebuild_kernel: unknown kernel");
 }
 
 int rsgpu_set_locate_kernel(rsgpu_ctx* ctx, int kernel)
 {
-    if (!ctx || kernel < RSGPU_LOCATE_AUTO || kernel > RSGPU_LOCATE_FUSED)
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_locate_kernel: unknown kernel");
-    ctx->locate_kernel = kernel;
-    return RSGPU_OK;
+    return set_kernel(ctx, kernel, RSGPU_LOCATE_FUSED, &rsgpu_ctx::locate_kernel, "rsgpu_set_locate_kernel: unknown kernel");
 }
 
 int rsgpu_set_degraded_kernel(rsgpu_ctx* ctx, int kernel)
 {
-    if (!ctx || kernel < RSGPU_DEGRADED_AUTO || kernel > RSGPU_DEGRADED_FUSED)
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_degraded_kernel: unknown kernel");
-    ctx->degraded_kernel = kernel;
-    return RSGPU_OK;
+    return set_kernel(ctx, kernel, RSGPU_DEGRADED_FUSED, &rsgpu_ctx::degraded_kernel, "rsgpu_set_degraded_kernel: unknown kernel");
 }
 
 int rsgpu_set_repair_kernel(rsgpu_ctx* ctx, int kernel)
 {
-    if (!ctx || kernel < RSGPU_REPAIR_KERNEL_AUTO || kernel > RSGPU_REPAIR_KERNEL_GENERATED)
-        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_set_repair_kernel: unknown kernel");
-    ctx->repair_kernel = kernel;
-    return RSGPU_OK;
+    return set_kernel(ctx, kernel, RSGPU_REPAIR_KERNEL_GENERATED, &rsgpu_ctx::repair_kernel, "rsgpu_set_repair_kernel: unknown kernel");
 }
 
 int rsgpu_scrub_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
@@ -462,51 +504,32 @@ int rsgpu_scrub_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, s
     const bool fused = fused_eligible(ctx, k, e, len, pitch, d_src, d_parity, coef);
     // GENERATED: any matrix, with or without `coef` (rsgpu.h)
     const bool generated = work && ctx->scrub_kernel == RSGPU_SCRUB_GENERATED &&
-                           rows_aligned(len, pitch, d_src, d_parity) && len < (1ull << 32) && e <= 64 &&
-                           jit_probe(ctx) == 1;
+                           generated_rows(ctx, e, len, pitch, d_src, d_parity);
     // the matrix's shared program on a slice, the stored parity compared in
-    // registers: row pointers into the context's scratch as the encode's, the
-    // locate tables where the two-pass scratch has them, no parity scratch
+    // registers; the locate tables where the two-pass scratch has them
     auto generated_slice = [&](size_t b0, size_t nb) -> int {
         const std::vector<uint8_t> c = locate ? loc.c : parity_matrix(k, e, coef);
-        const size_t src_ptr_bytes = align_up(sizeof(void*) * (size_t)k * nb, 256);
-        const size_t par_ptr_bytes = align_up(sizeof(void*) * (size_t)e * nb, 256);
-        int grc = ensure_scratch(ctx, src_ptr_bytes + par_ptr_bytes);
-        if (!grc)
-            grc = ensure_device(ctx, ctx->scrub, kScrubTabBytes);
-        if (!grc && locate)
-            grc = upload_locator(ctx, k, e, loc);
-        if (grc)
-            return grc;
-        char* d = (char*)ctx->scratch.p;
-        RS_HIP(ctx, launch_row_ptrs(d_src + b0 * k * pitch, (long long)pitch, k, (long long)nb, (const uint8_t**)d,
-                                    ctx->stream));
-        RS_HIP(ctx, launch_row_ptrs(d_parity + b0 * e * pitch, (long long)pitch, e, (long long)nb,
-                                    (const uint8_t**)(d + src_ptr_bytes), ctx->stream));
-        return shared_program_scrub(ctx, c.data(), k, e, (long long)len, (long long)nb, (const uint8_t* const*)d,
-                                    (const uint8_t* const*)(d + src_ptr_bytes), fold + b0,
-                                    (const uint8_t*)ctx->scrub.p, locate ? 1 : 0, "k_rs_jit_scrub");
+        JitScrubArgs s{};
+        const int grc = generated_prepare(ctx, k, e, len, pitch, nb, d_src + b0 * k * pitch, d_parity + b0 * e * pitch,
+                                          c.data(), locate ? &loc : nullptr, s);
+        s.fold = fold + b0;
+        s.tab = (const uint8_t*)ctx->scrub.p;
+        s.locate = locate ? 1 : 0;
+        return grc ? grc : generated_launch(ctx, s, nb, "k_rs_jit_scrub", launch_rs_jit_scrub);
     };
-    // block index in grid.y: larger batches as consecutive slices
-    for (size_t b0 = 0; work && b0 < blocks; b0 += kMaxGridBlocks) {
-        const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
-        if (generated) {
-            rc = generated_slice(b0, nb);
-            if (rc)
-                return rc;
-            continue;
-        }
-        if (!fused) {
-            rc = two_pass(ctx, k, e, len, pitch, b0, nb, d_src, coef, locate ? &loc : nullptr, compare);
-            if (rc)
-                return rc;
-            continue;
-        }
+    rc = for_grid_slices(work ? blocks : 0, [&](size_t b0, size_t nb) -> int {
+        if (generated)
+            return generated_slice(b0, nb);
+        if (!fused)
+            return two_pass(ctx, k, e, len, pitch, b0, nb, d_src, coef, locate ? &loc : nullptr, compare);
         KTimer kt(ctx, "k_rs_bs_scrub", nb);
         RS_HIP(ctx, launch_rs_bitsliced_scrub(k, e, d_src + b0 * k * pitch, d_parity + b0 * e * pitch,
                                               (long long)pitch, (long long)len, (long long)nb, fold + b0,
                                               locate ? 1 : 0, ctx->stream));
-    }
+        return RSGPU_OK;
+    });
+    if (rc)
+        return rc;
     KTimer kt(ctx, "k_scrub_finalise", blocks);
     RS_HIP(ctx, launch_scrub_finalise(d_report, (long long)blocks, locate ? 1 : 0, ctx->stream));
     return RSGPU_OK;
@@ -545,41 +568,29 @@ int rsgpu_repair_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
     // GENERATED (rsgpu_set_repair_kernel): any matrix, with or without `coef`,
     // on the rows the generated scrub takes; before FUSED where both apply
     const bool generated = ctx->repair_kernel == RSGPU_REPAIR_KERNEL_GENERATED &&
-                           rows_aligned(len, pitch, d_src, d_parity) && len < (1ull << 32) && e <= 64 &&
-                           jit_probe(ctx) == 1;
+                           generated_rows(ctx, e, len, pitch, d_src, d_parity);
     const bool fused = !generated && fused_eligible(ctx, k, e, len, pitch, d_src, d_parity, coef);
     const int first_mode = mode == RSGPU_REPAIR_COLUMNS ? kRepairColumns : kRepairLocate;
-    // The matrix's shared program on a slice, correcting in its cold path: row
-    // pointers into the context's scratch and the locate tables at the head of
-    // the two-pass scratch, as the generated scrub; no parity scratch.
-    // ONE_ROW: the launch that only folds, the finalise of the slice's
-    // reports, and the gated correcting launch on the same row pointers.
+    // The matrix's shared program on a slice, correcting in its cold path, as
+    // the generated scrub.  ONE_ROW: the launch that only folds, the finalise
+    // of the slice's reports, and the gated correcting launch on the same row
+    // pointers.
     auto generated_slice = [&](size_t b0, size_t nb) -> int {
-        const size_t src_ptr_bytes = align_up(sizeof(void*) * (size_t)k * nb, 256);
-        const size_t par_ptr_bytes = align_up(sizeof(void*) * (size_t)e * nb, 256);
-        int grc = ensure_scratch(ctx, src_ptr_bytes + par_ptr_bytes);
+        JitRepairArgs s{};
+        s.src = d_src + b0 * k * pitch;
+        s.par = d_parity + b0 * e * pitch;
+        int grc = generated_prepare(ctx, k, e, len, pitch, nb, s.src, s.par, loc.c.data(), &loc, s);
+        s.fold = fold + b0;
+        s.tab = (const uint8_t*)ctx->scrub.p;
+        s.pitch = (long long)pitch;
+        s.mode = first_mode;
         if (!grc)
-            grc = ensure_device(ctx, ctx->scrub, kScrubTabBytes);
-        if (!grc)
-            grc = upload_locator(ctx, k, e, loc);
-        if (grc)
-            return grc;
-        char* d = (char*)ctx->scratch.p;
-        uint8_t* src = d_src + b0 * k * pitch;
-        uint8_t* par = d_parity + b0 * e * pitch;
-        RS_HIP(ctx, launch_row_ptrs(src, (long long)pitch, k, (long long)nb, (const uint8_t**)d, ctx->stream));
-        RS_HIP(ctx, launch_row_ptrs(par, (long long)pitch, e, (long long)nb, (const uint8_t**)(d + src_ptr_bytes),
-                                    ctx->stream));
-        auto launch = [&](int m, const char* name) {
-            return shared_program_repair(ctx, loc.c.data(), k, e, (long long)len, (long long)pitch, (long long)nb,
-                                         (const uint8_t* const*)d, (const uint8_t* const*)(d + src_ptr_bytes), src, par,
-                                         fold + b0, (const uint8_t*)ctx->scrub.p, m, name);
-        };
-        grc = launch(first_mode, "k_rs_jit_repair");
+            grc = generated_launch(ctx, s, nb, "k_rs_jit_repair", launch_rs_jit_repair);
         if (!grc)
             grc = finalise(b0, nb);
+        s.mode = kRepairGated;
         if (!grc && mode == RSGPU_REPAIR_ONE_ROW)
-            grc = launch(kRepairGated, "k_rs_jit_repair_gated");
+            grc = generated_launch(ctx, s, nb, "k_rs_jit_repair_gated", launch_rs_jit_repair);
         return grc;
     };
     // A slice of the scratch.  COLUMNS: the correcting compare; ONE_ROW: the
@@ -607,22 +618,15 @@ int rsgpu_repair_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
     };
     // block index in grid.y: larger batches as consecutive slices, each
     // complete (located, finalised, corrected) before the next
-    for (size_t b0 = 0; b0 < blocks; b0 += kMaxGridBlocks) {
-        const size_t nb = std::min(kMaxGridBlocks, blocks - b0);
+    return for_grid_slices(blocks, [&](size_t b0, size_t nb) -> int {
         uint8_t* src = d_src + b0 * k * pitch;
         uint8_t* par = d_parity + b0 * e * pitch;
-        if (generated) {
-            rc = generated_slice(b0, nb);
-            if (rc)
-                return rc;
-            continue;
-        }
+        if (generated)
+            return generated_slice(b0, nb);
         if (!fused) {
             rc = two_pass(ctx, k, e, len, pitch, b0, nb, d_src, coef, &loc, compare);
-            if (rc)
-                return rc;
-            if (mode == RSGPU_REPAIR_ONE_ROW)
-                continue;  // finalised slice by slice
+            if (rc || mode == RSGPU_REPAIR_ONE_ROW)
+                return rc;  // ONE_ROW: finalised slice by slice
         } else {
             KTimer kt(ctx, "k_rs_bs_repair", nb);
             RS_HIP(ctx, launch_rs_bitsliced_repair(k, e, src, par, (long long)pitch, (long long)len, (long long)nb,
@@ -636,8 +640,8 @@ int rsgpu_repair_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
             RS_HIP(ctx, launch_rs_bitsliced_repair(k, e, src, par, (long long)pitch, (long long)len, (long long)nb,
                                                    fold + b0, kRepairGated, ctx->stream));
         }
-    }
-    return RSGPU_OK;
+        return RSGPU_OK;
+    });
 }
 
 int rsgpu_correct_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
@@ -676,11 +680,11 @@ int rsgpu_correct_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch,
         return RSGPU_OK;
     };
     // block index in grid.y: larger batches as consecutive slices
-    for (size_t b0 = 0; work && b0 < blocks; b0 += kMaxGridBlocks) {
-        rc = two_pass(ctx, k, e, len, pitch, b0, std::min(kMaxGridBlocks, blocks - b0), d_src, coef, &loc, compare);
-        if (rc)
-            return rc;
-    }
+    rc = for_grid_slices(work ? blocks : 0, [&](size_t b0, size_t nb) {
+        return two_pass(ctx, k, e, len, pitch, b0, nb, d_src, coef, &loc, compare);
+    });
+    if (rc)
+        return rc;
     KTimer kt(ctx, "k_correct_finalise", blocks);
     RS_HIP(ctx, launch_correct_finalise(d_report, (long long)blocks, ctx->stream));
     return RSGPU_OK;
@@ -878,26 +882,10 @@ int rsgpu_rebuild_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch,
     const int most = std::min(u + (check ? 1 : 0), e);  // rows of any block's list as it is rebuilt
     for (size_t g0 = 0; g0 < blocks; g0 += group) {
         const size_t ng = std::min(group, blocks - g0);
-        RebuildArgs a{};
-        a.k = k;
-        a.e = e;
-        a.u = u;
-        a.check = check && work ? 1 : 0;
-        a.work = work ? 1 : 0;
-        a.pitch = (long long)pitch;
-        a.len = (long long)len;
-        a.blocks = (long long)ng;
-        a.lost = d_lost + g0 * (size_t)u;
+        RebuildArgs a = rebuild_args(ctx, k, e, len, pitch, g0, ng, d_src, d_parity, u, d_lost, check, d_report);
         a.tab = (uint8_t*)ctx->rebuild.p;
         a.tab_stride = stride;
-        a.src_bytes = rebuild_src_bytes(k);
         a.g = lane_group(most);
-        a.report = d_report + g0;
-        if (work) {
-            a.src = d_src + g0 * (size_t)k * pitch;
-            a.par = d_parity + g0 * (size_t)e * pitch;
-            set_tables(a, ctx);
-        }
         {
             KTimer kt(ctx, "k_rebuild_prepare", ng);
             RS_HIP(ctx, launch_rebuild_prepare(a, ctx->stream));
@@ -947,7 +935,7 @@ int rsgpu_locate_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
                             tiles * kLocateSlotBytes <= kDegTabBytes;
     const bool compiled = want_fused && fused_rows(k, e, len, pitch, d_src, d_parity, coef);
     const bool generated = want_fused && !compiled && ctx->scrub_kernel == RSGPU_SCRUB_GENERATED &&
-                           rows_aligned(len, pitch, d_src, d_parity) && len < (1ull << 32) && jit_probe(ctx) == 1;
+                           generated_rows(ctx, e, len, pitch, d_src, d_parity);
     const bool fused = compiled || generated;
     const bool vec = pitch % 16 == 0 && (uintptr_t)d_parity % 16 == 0;
     const long long n16 = work && vec ? (long long)(len / 16) : 0;
@@ -963,17 +951,15 @@ int rsgpu_locate_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
     size_t group = std::max<size_t>(1, std::min({blocks, kMaxGridBlocks, kDegTabBytes / std::max<size_t>(1, stride)}));
     if (ctx->locate_group_max)
         group = std::min(group, ctx->locate_group_max);
-    // the generated form's row pointers of a group: [group][k] then [group][e]
-    const size_t src_ptr_bytes = align_up(sizeof(void*) * (size_t)k * group, 256);
-    const size_t par_ptr_bytes = align_up(sizeof(void*) * (size_t)e * group, 256);
     const std::vector<uint8_t> matrix = generated ? parity_matrix(k, e, coef) : std::vector<uint8_t>();
     if (work) {
         rc = ensure_device(ctx, ctx->locate, group * stride);
         // the scratch of the largest group now, so that no walk below grows it
         if (!rc && !fused)
             rc = grow_parity_scratch(ctx, group, per_block);
-        if (!rc && generated)
-            rc = ensure_scratch(ctx, src_ptr_bytes + par_ptr_bytes);
+        if (!rc && generated)  // the row pointers of the largest group: [group][k] then [group][e]
+            rc = ensure_scratch(ctx, align_up(sizeof(void*) * (size_t)k * group, 256) +
+                                         align_up(sizeof(void*) * (size_t)e * group, 256));
         // the matrix on the device (behind the update's tables)
         if (!rc)
             rc = update_tables(ctx, k, e, coef);
@@ -1014,15 +1000,16 @@ int rsgpu_locate_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, 
             // fused: the claims are counted in the reports' status field, zero since the memset
             a.claimed = fused ? 1 : 0;
             if (generated) {
-                char* d = (char*)ctx->scratch.p;
-                RS_HIP(ctx, launch_row_ptrs(d_src + g0 * (size_t)k * pitch, (long long)pitch, k, (long long)ng,
-                                            (const uint8_t**)d, ctx->stream));
-                RS_HIP(ctx, launch_row_ptrs(d_parity + g0 * per_block, (long long)pitch, e, (long long)ng,
-                                            (const uint8_t**)(d + src_ptr_bytes), ctx->stream));
-                rc = shared_program_locate(ctx, matrix.data(), k, e, (long long)len, (long long)ng,
-                                           (const uint8_t* const*)d, (const uint8_t* const*)(d + src_ptr_bytes),
-                                           reinterpret_cast<ScrubFold*>(d_report + g0), a.cand, stride, slots, u,
-                                           "k_rs_jit_locate");
+                JitLocateArgs s{};
+                s.fold = reinterpret_cast<ScrubFold*>(d_report + g0);
+                s.cand = a.cand;
+                s.cand_stride = stride;
+                s.slots = slots;
+                s.u = u;
+                rc = generated_prepare(ctx, k, e, len, pitch, ng, d_src + g0 * (size_t)k * pitch,
+                                       d_parity + g0 * per_block, matrix.data(), nullptr, s);
+                if (!rc)
+                    rc = generated_launch(ctx, s, ng, "k_rs_jit_locate", launch_rs_jit_locate);
                 if (rc)
                     return rc;
             } else if (compiled) {

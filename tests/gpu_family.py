@@ -1,7 +1,8 @@
 """What the GPU suites of the scrub family share (tests/test_gpu_scrub.py,
 test_gpu_repair.py, test_gpu_update.py, test_gpu_degraded.py,
 test_gpu_rebuild.py): the context of a module, synthetic blocks and their
-parity on the device, the comparison of reports with a model's tuples, and the
+parity on the device, the timing records of a call, the comparison of reports
+with a model's tuples, and the
 stripes, lists and damage of the degraded scrub, which the rebuild suite runs
 on as well.  Not a test module; the suites import torch before they import
 this one."""
@@ -28,6 +29,18 @@ def device_context(reset_scrub_kernel=False):
     if reset_scrub_kernel:
         c.set_scrub_kernel("auto")
     c.close()
+
+
+def recorded(ctx, call, blocks=False):
+    """The names of the timing records that call() leaves, in order; with
+    `blocks`, (name, blocks) per record."""
+    ctx.timing_enable(True)
+    try:
+        ctx.timing_read()
+        call()
+        return [(n, b) if blocks else n for n, _, b in ctx.timing_read()]
+    finally:
+        ctx.timing_enable(False)
 
 
 def matrix(k, e, kind):

@@ -1,6 +1,6 @@
 """The launch sequences of the scrub family (include/rsgpu.h rsgpu_scrub_blocks,
-rsgpu_repair_blocks, rsgpu_scrub_degraded_blocks), pinned through the timing
-log: the exact ordered list of record names each entry point produces, for a
+rsgpu_repair_blocks, rsgpu_scrub_degraded_blocks, rsgpu_locate_blocks,
+rsgpu_correct_blocks, rsgpu_rebuild_blocks), pinned through the timing log: the exact ordered list of record names each entry point produces, for a
 compiled code, (5, 4), and for one that is not, (3, 3) with a caller's Cauchy
 matrix, on 2 blocks.  ENC stands for whatever a plain encode_blocks call with
 the same arguments records; it is captured here, not spelled out.  The
@@ -19,6 +19,7 @@ import pytest
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
+import gpu_family as gf  # noqa: E402
 import rsgpu  # noqa: E402
 import scrub_model as sm  # noqa: E402
 
@@ -37,6 +38,10 @@ def ctx():
     torch.cuda.synchronize()
     c.set_scrub_kernel("auto")
     c.set_decode_kernel("auto")
+    c.set_locate_kernel("auto")
+    c.set_degraded_kernel("auto")
+    c.set_repair_kernel("auto")
+    c.set_rebuild_kernel("auto")
     c.close()
 
 
@@ -60,17 +65,18 @@ class Rows:
             self.src[(k + 1) * pitch + L // 2] ^= 0x5A
         torch.cuda.synchronize()
 
-    def names(self, call, kernel="auto"):
-        """The record names of one call, under scrub kernel choice `kernel`."""
+    def names(self, call, kernel="auto", locate="auto", degraded="auto"):
+        """The record names of one call, under scrub kernel choice `kernel`,
+        locate kernel choice `locate` and degraded kernel choice `degraded`."""
         self.ctx.set_scrub_kernel(kernel)
-        self.ctx.timing_enable(True)
+        self.ctx.set_locate_kernel(locate)
+        self.ctx.set_degraded_kernel(degraded)
         try:
-            self.ctx.timing_read()
-            call()
-            return [n for n, _, _ in self.ctx.timing_read()]
+            return gf.recorded(self.ctx, call)
         finally:
-            self.ctx.timing_enable(False)
             self.ctx.set_scrub_kernel("auto")
+            self.ctx.set_locate_kernel("auto")
+            self.ctx.set_degraded_kernel("auto")
 
     def enc(self):
         """ENC: a plain encode of the same rows, into a buffer of its own."""
@@ -87,10 +93,26 @@ class Rows:
         return self.names(lambda: self.ctx.repair_blocks(self.k, self.e, self.L, self.pitch, B, self.src, self.par,
                                                          self.rep, coef=self.coef, mode=mode), kernel)
 
-    def degraded(self):
+    def degraded(self, kernel="auto"):
         lost = torch.tensor([[1, 255], [255, 255]], dtype=torch.uint8, device=self.src.device)
         return self.names(lambda: self.ctx.scrub_degraded_blocks(self.k, self.e, self.L, self.pitch, B, self.src,
-                                                                 self.par, 2, lost, self.rep, coef=self.coef))
+                                                                 self.par, 2, lost, self.rep, coef=self.coef),
+                          degraded=kernel)
+
+    def locate(self, locate="auto", kernel="auto"):
+        rows = torch.zeros(B * 2, dtype=torch.uint8, device=self.src.device)
+        return self.names(lambda: self.ctx.locate_blocks(self.k, self.e, self.L, self.pitch, B, self.src, self.par,
+                                                         2, rows, self.rep, coef=self.coef), kernel, locate=locate)
+
+    def correct(self):
+        rep = torch.zeros(B * rsgpu.CORRECT_REPORT_DTYPE.itemsize, dtype=torch.uint8, device=self.src.device)
+        return self.names(lambda: self.ctx.correct_blocks(self.k, self.e, self.L, self.pitch, B, self.src, self.par,
+                                                          rep, coef=self.coef, t=1))
+
+    def rebuild(self, check):
+        lost = torch.tensor([[1, 255], [255, 255]], dtype=torch.uint8, device=self.src.device)
+        return self.names(lambda: self.ctx.rebuild_blocks(self.k, self.e, self.L, self.pitch, B, self.src, self.par,
+                                                          2, lost, self.rep, coef=self.coef, check=check))
 
 
 def test_the_codes_are_what_the_cases_assume():
@@ -150,6 +172,53 @@ def test_degraded(ctx, code):
     assert Rows(ctx, code, 0, 64).degraded() == ["k_degraded_prepare"]
 
 
+@CODES
+def test_locate_two_pass(ctx, code):
+    r = Rows(ctx, code, 64, 64)
+    assert r.locate() == r.enc() + ["k_locate_span", "k_locate_finish"]
+    r = Rows(ctx, code, 64, 65)
+    assert r.locate() == r.enc() + ["k_locate_span(bytes)", "k_locate_finish"]
+    assert Rows(ctx, code, 0, 64).locate() == ["k_locate_finish"]
+
+
+def test_locate_two_pass_with_a_byte_tail(ctx):
+    r = Rows(ctx, CAUCHY, 72, 80)
+    assert r.locate() == r.enc() + ["k_locate_span", "k_locate_span(tail)", "k_locate_finish"]
+
+
+def test_locate_fused(ctx):
+    r = Rows(ctx, COMPILED, 64, 64)
+    assert r.locate("fused") == ["k_rs_bs_locate", "k_locate_finish"]
+
+
+def test_locate_generated(ctx):
+    r = Rows(ctx, CAUCHY, 64, 64)
+    assert r.locate("fused", "generated") == ["k_rs_jit_locate", "k_locate_finish"]
+
+
+@CODES
+def test_correct(ctx, code):
+    r = Rows(ctx, code, 64, 64)
+    assert r.correct() == r.enc() + ["k_correct_compare", "k_correct_finalise"]
+    assert Rows(ctx, code, 0, 64).correct() == ["k_correct_finalise"]
+
+
+def test_degraded_fused(ctx):
+    r = Rows(ctx, COMPILED, 64, 64)
+    assert r.degraded("fused") == ["k_degraded_prepare", "k_rs_bs_degraded", "k_degraded_finalise"]
+
+
+@CODES
+def test_rebuild(ctx, code):
+    rebuilt = ["k_rebuild_prepare", "k_rebuild_blocks"]
+    r = Rows(ctx, code, 64, 64)
+    assert r.rebuild(check=False) == rebuilt
+    r = Rows(ctx, code, 64, 64)
+    checked = ["k_degraded_prepare"] + r.enc() + ["k_degraded_compare", "k_degraded_finalise"]
+    assert r.rebuild(check=True) == checked + rebuilt
+    assert Rows(ctx, code, 0, 64).rebuild(check=False) == ["k_rebuild_prepare"]
+
+
 # ---- decode ------------------------------------------------------------------
 
 KERNELS = ("auto", "generated", "one_matrix", "general")
@@ -203,19 +272,14 @@ class Erased:
         check: the first `blocks` blocks are decoded as they were erased."""
         nb = self.blocks if blocks is None else blocks
         self.ctx.set_decode_kernel(kernel)
-        self.ctx.timing_enable(True)
         try:
-            self.ctx.timing_read()
-            call(nb)
-            recs = self.ctx.timing_read()
+            self.recs = gf.recorded(self.ctx, lambda: call(nb), blocks=True)
         finally:
-            self.ctx.timing_enable(False)
             self.ctx.set_decode_kernel("auto")
         torch.cuda.synchronize()
         if check and self.n:
             assert (self.status[:nb] == 0).all(), self.status[:nb]
             assert torch.equal(self.rows(self.out, self.n)[:nb, :, : self.L], self.want[:nb]), "decoded rows differ"
-        self.recs = [(n, b) for n, _, b in recs]
         return [n for n, _ in self.recs]
 
     def args(self, nb):

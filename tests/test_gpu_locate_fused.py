@@ -39,13 +39,9 @@ def ctx():
 
 def records(ctx, call):
     """call()'s result and the names of the timing records it left."""
-    ctx.timing_enable(True)
-    try:
-        ctx.timing_read()
-        out = call()
-        return out, {n for n, _, _ in ctx.timing_read()}
-    finally:
-        ctx.timing_enable(False)
+    out = []
+    names = gf.recorded(ctx, lambda: out.append(call()))
+    return out[0], set(names)
 
 
 class FusedBlocks(Blocks):

@@ -97,15 +97,12 @@ def run(st, kernel, pre, seed):
     st.par_all.copy_(pre[1])
     st.noise(seed)
     st.ctx.set_rebuild_kernel(kernel)
-    st.ctx.timing_enable(True)
+    got = []
     try:
-        st.ctx.timing_read()
-        got = st.rebuild(check=False)
-        names = [n for n, _, _ in st.ctx.timing_read()]
+        names = gf.recorded(st.ctx, lambda: got.append(st.rebuild(check=False)))
     finally:
-        st.ctx.timing_enable(False)
         st.ctx.set_rebuild_kernel("auto")
-    return got, names
+    return got[0], names
 
 
 def wide_names(st, kernel):
@@ -345,14 +342,12 @@ def test_threaded_with_the_check(ctx, orc):
         st.src_all.copy_(pre[0])
         st.par_all.copy_(pre[1])
         ctx.set_rebuild_kernel(kernel)
-        ctx.timing_enable(True)
+        got = []
         try:
-            ctx.timing_read()
-            got = st.rebuild(check=True)
-            names = [n for n, _, _ in ctx.timing_read()]
+            names = gf.recorded(ctx, lambda: got.append(st.rebuild(check=True)))
         finally:
-            ctx.timing_enable(False)
             ctx.set_rebuild_kernel("auto")
+        got = got[0]
         same(got, want)
         st.same_bytes(es, ep)
         st.same_bytes(*st.orig)
@@ -434,13 +429,9 @@ def test_more_blocks_than_a_grid_holds(ctx):
             view_p[blocks, r - k, :L] = 0x3D
     torch.cuda.synchronize()
     assert not torch.equal(st.src_all, st.orig[0]) and not torch.equal(st.par_all, st.orig[1])
-    ctx.timing_enable(True)
-    try:
-        ctx.timing_read()
-        got = st.rebuild(check=False)
-        names = [n for n, _, _ in ctx.timing_read()]
-    finally:
-        ctx.timing_enable(False)
+    got = []
+    names = gf.recorded(ctx, lambda: got.append(st.rebuild(check=False)))
+    got = got[0]
     assert names == ["k_rebuild_wide_prepare", "k_rs_tc(rebuild)"] * 2
     assert (got["status"] == dm.CLEAN).all() and (got["bad_columns"] == 0).all() and (got["row"] == -1).all()
     st.same_bytes(*st.orig)

@@ -75,16 +75,14 @@ class Blocks(gf.DeviceBlocks):
         self.ctx.set_scrub_kernel(scrub_kernel)
         self.ctx.set_repair_kernel(repair_kernel)
         self.rep.fill_(gf.POISON)
-        if names is not None:
-            self.ctx.timing_enable(True)
-            self.ctx.timing_read()
+        call = lambda: self.ctx.repair_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,  # noqa: E731
+                                               self.rep, coef=self.coef, mode=mode)
         try:
-            self.ctx.repair_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, self.rep,
-                                   coef=self.coef, mode=mode)
-            if names is not None:
-                names += [n for n, _, _ in self.ctx.timing_read()]
+            if names is None:
+                call()
+            else:
+                names += gf.recorded(self.ctx, call)
         finally:
-            self.ctx.timing_enable(False)
             self.ctx.set_repair_kernel("auto")
             self.ctx.set_scrub_kernel("auto")
         torch.cuda.synchronize()
@@ -245,14 +243,8 @@ def test_launch_sequence_and_no_parity_scratch(mode):
         k, e, L = 10, 4, 6144  # a block's parity is larger than the buffer's tables
         blk = Blocks(c, k, e, L, kind="cauchy")
         assert scrub_scratch_bytes(c) == 0
-        enc = []
-        c.timing_enable(True)
-        try:
-            c.timing_read()
-            c.encode_blocks(k, e, L, blk.pitch, B, blk.src, blk.alloc(e), coef=blk.coef)
-            enc = [n for n, _, _ in c.timing_read()]
-        finally:
-            c.timing_enable(False)
+        spare = blk.alloc(e)
+        enc = gf.recorded(c, lambda: c.encode_blocks(k, e, L, blk.pitch, B, blk.src, spare, coef=blk.coef))
         assert enc
         blk.hit([(1, 4, 2100, 0x66), (3, k + 2, 0, 0x09)])
         damaged = blk.snapshot()

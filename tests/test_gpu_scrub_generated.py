@@ -54,16 +54,14 @@ class Blocks(gf.DeviceBlocks):
         names: a list that receives the call's record names."""
         self.ctx.set_scrub_kernel(kernel)
         self.rep.fill_(gf.POISON)
-        if names is not None:
-            self.ctx.timing_enable(True)
-            self.ctx.timing_read()
+        call = lambda: self.ctx.scrub_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par,  # noqa: E731
+                                              self.rep, coef=self.coef if isinstance(coef, str) else coef, locate=locate)
         try:
-            self.ctx.scrub_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, self.par, self.rep,
-                                  coef=self.coef if isinstance(coef, str) else coef, locate=locate)
-            if names is not None:
-                names += [n for n, _, _ in self.ctx.timing_read()]
+            if names is None:
+                call()
+            else:
+                names += gf.recorded(self.ctx, call)
         finally:
-            self.ctx.timing_enable(False)
             self.ctx.set_scrub_kernel("auto")
         torch.cuda.synchronize()
         return self.rep.cpu().numpy().view(DT).copy()
@@ -75,13 +73,8 @@ class Blocks(gf.DeviceBlocks):
     def enc_names(self):
         """What a plain encode of the same rows records (into a spare buffer)."""
         spare = self.alloc(self.e)[self.offset:]
-        self.ctx.timing_enable(True)
-        try:
-            self.ctx.timing_read()
-            self.ctx.encode_blocks(self.k, self.e, self.L, self.pitch, self.B, self.src, spare, coef=self.coef)
-            return [n for n, _, _ in self.ctx.timing_read()]
-        finally:
-            self.ctx.timing_enable(False)
+        return gf.recorded(self.ctx, lambda: self.ctx.encode_blocks(self.k, self.e, self.L, self.pitch, self.B,
+                                                                    self.src, spare, coef=self.coef))
 
     def check(self, others=("two_pass",)):
         """generated == the model, and == every kernel of `others` byte for
@@ -259,13 +252,10 @@ def test_repair_runs_its_two_pass_form(ctx, mode):
         blk.xor(3, k + 2, 0, 0x09)
         rep = torch.full((B * RDT.itemsize,), gf.POISON, dtype=torch.uint8, device=blk.dev)
         ctx.set_scrub_kernel(kernel)
-        ctx.timing_enable(True)
         try:
-            ctx.timing_read()
-            ctx.repair_blocks(k, e, L, blk.pitch, B, blk.src, blk.par, rep, coef=blk.coef, mode=mode)
-            names = [n for n, _, _ in ctx.timing_read()]
+            names = gf.recorded(ctx, lambda: ctx.repair_blocks(k, e, L, blk.pitch, B, blk.src, blk.par, rep,
+                                                               coef=blk.coef, mode=mode))
         finally:
-            ctx.timing_enable(False)
             ctx.set_scrub_kernel("auto")
         torch.cuda.synchronize()
         out[kernel] = (names, rep.cpu().numpy().tobytes(), blk.src_all.cpu(), blk.par_all.cpu(), blk)
