@@ -941,7 +941,8 @@ int rsgpu_set_repair_kernel(rsgpu_ctx *ctx, int kernel);
  * synchronisation and no host decision between finding and writing; more
  * than 65535 blocks run as consecutive slices.
  *
- * The two-pass form only: the encode of a slice into the context's scratch
+ * Two forms, chosen by rsgpu_set_correct_kernel (below); AUTO runs TWO_PASS.
+ * TWO_PASS: the encode of a slice into the context's scratch
  * (the TWO_PASS scrub's slices, at most 128 MiB of parity), then
  * k_correct_compare, which is k_repair_compare -- a thread ORs the syndromes
  * of 16 columns per 16-byte load, a clean group costs nothing more, a bad
@@ -969,9 +970,9 @@ int rsgpu_set_repair_kernel(rsgpu_ctx *ctx, int kernel);
  * 189.1 ms on the one-row, two-row and whole-row damage.  Advice: scrub
  * first; where the damage lies in whole rows, locate and rebuild; take this
  * call for the blocks they give up as DAMAGED, whose damage is scattered.
- * Not built: a form fused into the compiled or generated encode
- * (rsgpu_set_scrub_kernel has no influence on this call); t > 2; e > 64;
- * host-resident blocks. */
+ * rsgpu_set_scrub_kernel has no influence on this call.
+ * Not built: a form fused into the generated encode, for matrices that are
+ * not compiled in; t > 2; e > 64; host-resident blocks. */
 typedef struct rsgpu_correct_report {
     unsigned long long bad_columns;       /* before the call */
     unsigned long long corrected_columns; /* columns written, one- and two-row together */
@@ -983,6 +984,59 @@ typedef struct rsgpu_correct_report {
 int rsgpu_correct_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                          unsigned char *d_src, unsigned char *d_parity,
                          const unsigned char *coef, int t, rsgpu_correct_report *d_report);
+
+/* Kernel of rsgpu_correct_blocks, per context; rows written and reports are
+ * the same under every choice, byte for byte.  An unknown value or a null
+ * context is RSGPU_ERR_ARG.  All argument checks, the UNSUPPORTED cases (a
+ * matrix that is not locatable, t = 1 with e < 3, t = 2 with e outside [5,
+ * 64]) and the e == 0 / len == 0 paths come before the choice and do not
+ * depend on it.
+ *   AUTO      TWO_PASS: the fused form is opt-in.
+ *   TWO_PASS  the encode into the scratch, then k_correct_compare.
+ *   FUSED     fused into the compiled encode, as the FUSED scrub and repair
+ *             are: per slice of at most 65535 blocks one launch of
+ *             k_rs_bs_correct, which is k_rs_bs_repair in its COLUMNS mode --
+ *             k_rs_bs's accumulation, the stored parity read once and
+ *             compared in registers, nothing written for a clean tile -- and
+ *             after all slices k_correct_finalise.  No encode is launched, the
+ *             parity scratch is neither touched nor grown, the locate tables
+ *             are not uploaded.  A dirty tile lays its syndromes into LDS in
+ *             four passes; a column one row explains is corrected as COLUMNS
+ *             corrects it, and with t = 2 the others go to the wave one at a
+ *             time while the pass's syndromes are in LDS: TWO_PASS's search
+ *             (two parity rows off the non-zero syndromes; a data row with a
+ *             parity row, a lane per data row; the data pairs, a lane per
+ *             higher row, solved from syndromes 0 and 1 and screened at
+ *             syndrome 2) on the compiled codes' own coefficients 2^(p r), so
+ *             nothing of the matrix is read from memory.  Its tables (the
+ *             field's logarithms, 1.3 KB per workgroup; 8 bytes per data row
+ *             and 64 per wave) lie in the encode's 32 KB of LDS; no kernel has
+ *             scratch, each runs at its k_rs_bs_repair sibling's waves per
+ *             SIMD, no plan is left out (profiles/correct_fused).
+ *             Measured at (64, 32), 1 MB rows, 1024 blocks on one MI355X, one
+ *             process, medians of 24 runs (profiles/correct_fused, DESIGN.md
+ *             3.10): clean blocks 22.10 ms, rsgpu_repair_blocks COLUMNS under
+ *             the FUSED scrub kernel 21.55 ms (ratio over 24 mirrored pairs
+ *             0.876 - 1.054, mean 1.011, stdev 0.035: inside the pair's
+ *             run-to-run spread), TWO_PASS 36.09 ms.  One row per block bad
+ *             in 1 % of the columns 33.92 ms, a second row bad in the same
+ *             columns 108.72 ms, 12 rows with two per column 108.72 ms
+ *             (1.15 ns per one-row column and 7.31 ns per pending
+ *             column over the device); two whole rows bad 4796 ms
+ *             (TWO_PASS 7566 ms in the same process).  At the scrub's
+ *             price on clean blocks this call with t = 2 can be the scrub
+ *             pass itself; whole damaged rows still belong to
+ *             rsgpu_locate_blocks and rsgpu_rebuild_blocks.
+ *             Where the FUSED scrub's kernels apply: the compiled codes (16,4)
+ *             (16,8) (64,32) (64,16) (100,20) (5,4) (20,7) without `coef`,
+ *             pitch % 16 == 0, 16-byte aligned d_src and d_parity, len % 32 ==
+ *             0, len < 4 GiB -- so t = 2 on (16,8) (20,7) (64,16) (64,32)
+ *             (100,20), t = 1 on those and on (16,4) (5,4).
+ * A choice that does not apply falls back to TWO_PASS, silently. */
+#define RSGPU_CORRECT_AUTO 0
+#define RSGPU_CORRECT_TWO_PASS 1
+#define RSGPU_CORRECT_FUSED 2
+int rsgpu_set_correct_kernel(rsgpu_ctx *ctx, int kernel);
 
 /* ---- partial-stripe update: parity follows a few overwritten rows -------- */
 

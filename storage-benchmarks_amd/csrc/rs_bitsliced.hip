@@ -50,6 +50,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
 #include <utility>
 
 #include "bitslice.h"
@@ -58,6 +59,7 @@
 #include "kernel_hooks.h"
 #include "plane_mul.h"
 #include "rs_kernels.h"
+#include "rs_pairs.h"
 #include "rs_span.h"
 
 namespace rsgpu {
@@ -324,6 +326,26 @@ struct DegArgs {
     int locate;
 };
 
+// The correction per column (rsgpu_correct_blocks under FUSED,
+// k_rs_bs_correct): the repair's arguments in its kRepairColumns mode with the
+// 32-byte fold, and t; with t == 2 scrub_tile's walk hands the columns no row
+// explains to correct_pending.
+struct CorrectArgs {
+    static constexpr bool kScrub = true;
+    static constexpr bool kDegraded = false;
+    static constexpr bool kRepair = true;
+    static constexpr bool kSpan = false;
+    static constexpr int flat = 0;
+    static constexpr int locate = 1;
+    static constexpr int mode = kRepairColumns;
+    uint8_t* src;  // [B][K] rows
+    uint8_t* par;  // [B][E] rows, the stored parity
+    long long pitch, len;
+    long long blocks;
+    CorrectFold* fold;  // [B], zeroed before the launch (rs_kernels.h)
+    int t;              // 1, or 2 (E >= 5)
+};
+
 // log / antilog tables of the cold paths (the scrub's row location, the
 // small-batch decode's solve below)
 alignas(16) __device__ const GfTables kGfBs = make_gf_tables();
@@ -415,6 +437,78 @@ __device__ __forceinline__ void span_tile(const LocArgs& a, uint32_t (&acc)[NR][
     }
 }
 
+// scrub_tile's cold path of the correction with t == 2 (CorrectArgs): the bad
+// columns of a step of the walk that no row explains (`pend`, a lane each; the
+// lanes of a wave walk 64 consecutive columns, lane 0 column c0) go to the
+// wave one at a time, all 64 lanes on each, under wave-uniform control, with
+// the pass's syndromes still in LDS.  The search is rs_correct.hip's for the
+// compiled codes' own coefficients, 2^(p r) (rs_pairs.h): nothing of the matrix
+// is read from memory.  The lanes' matches are counted, up to two; the lane
+// that holds the only one XORs both bytes into the global rows, column c of
+// pass `pass` being byte 8 pass + c % 8 of tile lane c / 8 as in the walk.
+// In place for scrub_tile's reasons: the syndromes are in LDS, no byte of
+// global memory is read twice.  Returns the columns corrected (0 or more,
+// the same in every lane).
+// LDS, in the part buffers: masks 1 KiB | syn [E][520] | PairGf (1288 B, the
+// workgroup's, correct_tables) | per wave CorRow [K] and the column's
+// syndromes [64].
+template <int E>
+constexpr int kCorGfAt = 1024 + E * kSpanRow;
+template <int K>
+constexpr int kCorWaveBytes = K * (int)sizeof(CorRow) + 64;
+template <int K, int E, int G>
+constexpr int kCorWaveAt = kCorGfAt<E> + ((int)sizeof(PairGf) + 7) / 8 * 8 + G * kCorWaveBytes<K>;
+
+
+template <int E, int NW>
+__device__ __forceinline__ void correct_tables(const CorrectArgs& a, uint8_t* ldsb, int tid)
+{
+    for (int i = tid; i < (int)sizeof(PairGf); i += 64 * NW)
+        ldsb[kCorGfAt<E> + i] = pair_gf_byte(kGfBs, i);
+}
+
+template <int K, int E, int NW, int G>
+__device__ __forceinline__ unsigned correct_pending(const CorrectArgs& a, bool pend, int c0, int pass, long long wb,
+                                                    int lane, uint8_t* ldsb)
+{
+    static_assert(E >= 3 && E <= 64 && K <= 255, "a lane per syndrome; 2^r distinct over the data rows");
+    static_assert(kCorGfAt<E> % 8 == 0 && kCorWaveBytes<K> % 8 == 0, "the rows' tables are aligned");
+    static_assert(kCorWaveAt<K, E, NW> <= 2 * S * 2 * 64 * 16, "correct LDS fits the part buffers");
+    const uint8_t* syn = ldsb + 1024;
+    const PairGf& gf = *reinterpret_cast<const PairGf*>(ldsb + kCorGfAt<E>);
+    CorRow* row = reinterpret_cast<CorRow*>(ldsb + kCorWaveAt<K, E, G>);
+    uint8_t* wsyn = reinterpret_cast<uint8_t*>(row + K);
+    unsigned done = 0;
+    unsigned long long todo = __ballot(pend);
+    while (todo) {
+        const int c = c0 + __ffsll(todo) - 1;
+        todo &= todo - 1;
+        if (lane < E)
+            wsyn[lane] = syn[lane * kSpanRow + c];
+        const uint8_t s0 = syn[c], s1 = syn[kSpanRow + c], s2 = syn[2 * kSpanRow + c];
+        for (int r = lane; r < K; r += 64)
+            row[r] = rs_pair_row(gf, s0, s1, s2, r);
+        // what a lane wrote is read by the other lanes of the wave from here on
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        const CorPairs p = rs_pair_search_lane(gf, K, E, wsyn, row, lane);
+        const long long lo = (long long)blockIdx.x * 2048 + (c >> 3) * 32;
+        const bool one = __ballot(p.cnt >= 2) == 0 && __popcll(__ballot(p.cnt == 1)) == 1 && lo + 32 <= a.len;
+        if (one && p.cnt == 1) {
+            const long long at = lo + 8 * pass + (c & 7);
+            uint8_t* ga = (p.ra < K ? a.src + ((size_t)wb * K + p.ra) * a.pitch
+                                    : a.par + ((size_t)wb * E + (p.ra - K)) * a.pitch) + at;
+            uint8_t* gb = (p.rb < K ? a.src + ((size_t)wb * K + p.rb) * a.pitch
+                                    : a.par + ((size_t)wb * E + (p.rb - K)) * a.pitch) + at;
+            *ga ^= p.xa;
+            *gb ^= p.xb;
+        }
+        done += one;
+        // the next column's syndromes overwrite what the lanes still read here
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    }
+    return done;
+}
+
 // Wave G's rows [R0, R0 + NR) of one tile.  The lane's 32 bytes of each
 // stored parity row, as planes, XORed into the accumulators: the syndromes,
 // in place.  Their OR over planes and rows gives the lane's bad-byte mask
@@ -452,12 +546,23 @@ __device__ __forceinline__ void span_tile(const LocArgs& a, uint32_t (&acc)[NR][
 // the store, the fold by selects): every nesting level keeps a saved exec
 // mask in an SGPR pair, and nested branches here cost the (64, 32) kernel 9
 // SGPR spills in its main loop and 1 % of its time (profiles/repair).
+//
+// The correction (CorrectArgs) is the repair in its kRepairColumns mode on the
+// 32-byte fold.  With t == 2 a bad column no row explains is pending: the wave
+// takes a step's pending columns at the top of the next step
+// (correct_pending, above), and folds its two-row corrections as `rep`, `two`
+// and hi1 = lo1 = kScrubNoRow.  syn's rows then lie 520 bytes apart, as
+// span_tile's, for the lanes that read a column's syndromes p = lane.
+// Everything of it hangs off `kCorrect`; the other kernels' code is what it
+// was (profiles/correct_fused).
 template <int K, int E, int NW, int G, int R0, int NR, class A>
 __device__ __forceinline__ void scrub_tile(const A& a, uint32_t (&acc)[NR][8], bool inb, long long wo,
                                            long long wb, long long blk, int lane, uint4* ldsv, uint32_t m4,
                                            uint32_t m2, uint32_t m1)
 {
     static_assert(E >= 2 && 1024 + E * 512 <= 2 * S * 2 * 64 * 16, "scrub LDS fits the part buffers");
+    constexpr bool kCorrect = std::is_same_v<A, CorrectArgs>;
+    constexpr int kRow = kCorrect ? kSpanRow : 512;  // syn's row stride
     uint32_t* wmask = reinterpret_cast<uint32_t*>(ldsv);
     uint8_t* syn = reinterpret_cast<uint8_t*>(ldsv) + 1024;
     const uint8_t* pb = a.par + (size_t)wb * E * a.pitch;
@@ -520,6 +625,9 @@ __device__ __forceinline__ void scrub_tile(const A& a, uint32_t (&acc)[NR][8], b
     const int tid = G * 64 + lane;
     unsigned hi1 = 0, lo1 = 0;
     [[maybe_unused]] unsigned nrep = 0;
+    [[maybe_unused]] unsigned ntwo = 0;  // the correction: the wave's columns corrected in two rows
+    if constexpr (kCorrect)
+        correct_tables<E, NW>(a, reinterpret_cast<uint8_t*>(ldsv), tid);  // read from the first pass's barrier on
 #pragma unroll
     for (int rr = 0; rr < NR; ++rr)
         tr8(acc[rr], m4, m2, m1);  // syndrome planes -> bytes, in place
@@ -529,18 +637,31 @@ __device__ __forceinline__ void scrub_tile(const A& a, uint32_t (&acc)[NR][8], b
             ((pass == Ps ? [&] {
 #pragma unroll
                 for (int rr = 0; rr < NR; ++rr)
-                    *reinterpret_cast<uint2*>(syn + (R0 + rr) * 512 + lane * 8) =
+                    *reinterpret_cast<uint2*>(syn + (R0 + rr) * kRow + lane * 8) =
                         inb ? make_uint2(acc[rr][2 * Ps], acc[rr][2 * Ps + 1]) : make_uint2(0u, 0u);
             }()
                          : void()),
              ...);
         }(std::make_integer_sequence<int, 4>{});
         __syncthreads();
-        for (int c = tid; c < 512; c += 64 * NW) {
-            const uint32_t s0 = syn[c], s1 = syn[512 + c];
+        // The correction: a step's pending column (bad, no row explains it)
+        // goes to the wave when the step ends, by `continue` or not, while the
+        // pass's syndromes are in LDS: the trip count is the same in every
+        // lane, all 64 are there.
+        [[maybe_unused]] bool pend = false;
+        auto step_ends = [&]([[maybe_unused]] int c) {
+            if constexpr (kCorrect) {
+                if (a.t == 2)
+                    ntwo += correct_pending<K, E, NW, G>(a, pend, c - lane, pass, wb, lane,
+                                                         reinterpret_cast<uint8_t*>(ldsv));
+                pend = false;
+            }
+        };
+        for (int c = tid; c < 512; step_ends(c), c += 64 * NW) {
+            const uint32_t s0 = syn[c], s1 = syn[kRow + c];
             int nz = 0, p0 = 0;
             for (int p = 0; p < E; ++p) {
-                const bool on = syn[p * 512 + c] != 0;
+                const bool on = syn[p * kRow + c] != 0;
                 nz += on;
                 p0 = on ? p : p0;
             }
@@ -554,7 +675,7 @@ __device__ __forceinline__ void scrub_tile(const A& a, uint32_t (&acc)[NR][8], b
                     const int lx = glog[s0];  // x = s_0: c[0][r] = 1
                     bool ok = true;
                     for (int p = 2; p < E; ++p)
-                        ok &= syn[p * 512 + c] == gexp[(p * r) % 255 + lx];
+                        ok &= syn[p * kRow + c] == gexp[(p * r) % 255 + lx];
                     row = ok ? r : -1;
                 }
             } else if (nz == 1) {
@@ -567,7 +688,7 @@ __device__ __forceinline__ void scrub_tile(const A& a, uint32_t (&acc)[NR][8], b
                 uint8_t* g = (src_row ? a.src : a.par) +
                              ((size_t)wb * (src_row ? K : E) + (src_row ? row : row - K)) * a.pitch + lo +
                              8 * pass + (c & 7);
-                const uint8_t x = src_row ? (uint8_t)s0 : syn[(row >= K ? row - K : 0) * 512 + c];
+                const uint8_t x = src_row ? (uint8_t)s0 : syn[(row >= K ? row - K : 0) * kRow + c];
                 if (a.mode != kRepairLocate && row >= 0 && lo + 32 <= a.len) {
                     *g ^= x;
                     ++nrep;
@@ -577,12 +698,22 @@ __device__ __forceinline__ void scrub_tile(const A& a, uint32_t (&acc)[NR][8], b
                 const bool folds = a.mode == kRepairLocate || (a.mode == kRepairColumns && row >= 0);
                 hi1 = max(hi1, !folds ? 0u : row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
                 lo1 = max(lo1, !folds ? 0u : row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
+                if constexpr (kCorrect)
+                    pend = row < 0;
                 continue;
             }
             hi1 = max(hi1, row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
             lo1 = max(lo1, row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
         }
         __syncthreads();  // the next pass overwrites syn
+    }
+    if constexpr (kCorrect) {
+        // a two-row correction: no common row of the block's corrected columns
+        hi1 = ntwo ? kScrubNoRow : hi1;
+        lo1 = ntwo ? kScrubNoRow : lo1;
+        nrep += lane == 0 ? ntwo : 0u;
+        if (lane == 0 && ntwo)
+            atomicAdd(&f->two, (unsigned long long)ntwo);
     }
     for (int off = 32; off > 0; off >>= 1) {
         hi1 = max(hi1, (unsigned)__shfl_down((int)hi1, off, 64));
@@ -983,6 +1114,18 @@ __global__ __launch_bounds__(64 * NW, (bs_waves_per_simd<E, NW>())) void k_rs_bs
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     [&]<int... Gs>(std::integer_sequence<int, Gs...>) {
         ((wave == Gs ? run_group<K, E, C, NW, Gs, true, RepairArgs>(a, lds) : void()), ...);
+    }(std::make_integer_sequence<int, NW>{});
+}
+
+// The correction per column: k_rs_bs_repair in its kRepairColumns mode whose
+// walk, with t == 2, takes the columns no row explains to correct_pending.
+template <int K, int E, int C, int NW>
+__global__ __launch_bounds__(64 * NW, (bs_waves_per_simd<E, NW>())) void k_rs_bs_correct(CorrectArgs a)
+{
+    __shared__ uint4 lds[2][S * 2 * 64];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    [&]<int... Gs>(std::integer_sequence<int, Gs...>) {
+        ((wave == Gs ? run_group<K, E, C, NW, Gs, true, CorrectArgs>(a, lds) : void()), ...);
     }(std::make_integer_sequence<int, NW>{});
 }
 
@@ -1464,6 +1607,15 @@ hipError_t launch_rs_bitsliced_repair(int k, int e, uint8_t* src, uint8_t* par, 
         return hipErrorInvalidValue;
     const bs::RepairArgs a{src, par, pitch, len, blocks, fold, mode};
     return bs::launch_family(k, e, a, st, [](auto p) { return bs::k_rs_bs_repair<p.K, p.E, p.C, p.NW>; });
+}
+
+hipError_t launch_rs_bitsliced_correct(int k, int e, uint8_t* src, uint8_t* par, long long pitch, long long len,
+                                       long long blocks, CorrectFold* fold, int t, hipStream_t st)
+{
+    if (!bs::family_rows(blocks, len, pitch, src, par, fold) || !((t == 1 && e >= 3) || (t == 2 && e >= 5 && e <= 64)))
+        return hipErrorInvalidValue;
+    const bs::CorrectArgs a{src, par, pitch, len, blocks, fold, t};
+    return bs::launch_family(k, e, a, st, [](auto p) { return bs::k_rs_bs_correct<p.K, p.E, p.C, p.NW>; });
 }
 
 }  // namespace rsgpu

@@ -50,6 +50,7 @@
 #include "gf256.h"
 #include "rs_kernels.h"
 #include "rs_lane.h"
+#include "rs_pairs.h"
 #include "rs_span.h"
 
 namespace rsgpu {
@@ -65,18 +66,9 @@ constexpr int kCorThreads = 256, kCorWaves = kCorThreads / 64;
 
 alignas(16) __device__ const GfTables kCorGf = make_gf_tables();
 
-// Logarithms as the pair search keeps them: 16 bits, kLogZero for 0, so that a
-// product is one read of `ex` at the sum of two of them -- ex[i] = 2^i below
-// 510 (two real logarithms sum to 508 at the most) and 0 from there on.
-constexpr unsigned kLogZero = 512;
-
-// what the search keeps of a data row r per column ...
-struct CorRow {
-    uint16_t a0, a1;  // log of s_2 c[0][r] and of s_2 c[1][r]
-    uint16_t c2, u;   // log of c[2][r] and of u_r (at the top)
-};
-
-// ... and what a wave keeps in LDS for its pair searches
+// What a wave keeps in LDS for its pair searches (rs_pairs.h: the logarithms
+// as the search keeps them, kLogZero, and CorRow, what it keeps of a data row
+// per column)
 struct CorWave {
     uint8_t log[256];
     uint8_t ex[2 * kLogZero + 4];
@@ -96,13 +88,6 @@ __device__ __forceinline__ uint8_t cor_mul(const CorWave& w, uint8_t a, uint8_t 
 __device__ __forceinline__ uint8_t cor_div(const CorWave& w, uint8_t a, uint8_t b)
 {
     return a ? w.ex[w.log[a] + 255 - w.log[b]] : 0;
-}
-
-// the sum of two real logarithms, or kLogZero, below 255 (a factor's logarithm)
-__device__ __forceinline__ unsigned cor_log_mul(unsigned la, unsigned lb)
-{
-    const unsigned l = la + lb;
-    return l >= kLogZero ? kLogZero : l >= 255 ? l - 255 : l;
 }
 
 // The wave's tables: the field's, and of rows 0 to 2 of the matrix.
@@ -126,23 +111,6 @@ struct CorLane {
     unsigned long long bad, rep, two;
     unsigned hi1, lo1;
 };
-
-// what a lane has found of a column's pairs
-struct CorPairs {
-    int cnt, ra, rb;  // matching pairs (up to 2); the first one, xa in row ra and xb in row rb
-    uint8_t xa, xb;
-};
-
-__device__ __forceinline__ void pair_found(CorPairs& c, int ra, int rb, uint8_t xa, uint8_t xb)
-{
-    if (c.cnt == 0) {
-        c.ra = ra;
-        c.rb = rb;
-        c.xa = xa;
-        c.xb = xb;
-    }
-    c.cnt = min(c.cnt + 1, 2);
-}
 
 // Byte column i of a block, as scrub_column of rs_kernels.hip in the repair's
 // COLUMNS mode: counted when bad, corrected and folded when one row explains

@@ -605,5 +605,9 @@ struct CorrectCmpArgs {
 };
 hipError_t launch_correct_compare(const CorrectCmpArgs& a, hipStream_t st);
 hipError_t launch_correct_finalise(void* report, long long blocks, hipStream_t st);
+// k_rs_bs_correct: k_rs_bs_scrub's conditions; the fold zeroed, launch_correct_finalise
+// after the last slice.  t as CorrectCmpArgs'.
+hipError_t launch_rs_bitsliced_correct(int k, int e, uint8_t* src, uint8_t* par, long long pitch, long long len,
+                                       long long blocks, CorrectFold* fold, int t, hipStream_t st);
 
 }  // namespace rsgpu

@@ -96,6 +96,9 @@ struct rsgpu_ctx {
     // (rsgpu_set_degraded_kernel)
     DevBuf degraded;
     int degraded_kernel = RSGPU_DEGRADED_AUTO;
+    // correction per column (rsgpu_correct_blocks): its kernel choice
+    // (rsgpu_set_correct_kernel)
+    int correct_kernel = RSGPU_CORRECT_AUTO;
     // repair in place (rsgpu_repair_blocks): its own kernel choice
     // (rsgpu_set_repair_kernel) on top of the scrub's
     int repair_kernel = RSGPU_REPAIR_KERNEL_AUTO;

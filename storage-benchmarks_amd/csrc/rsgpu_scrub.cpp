@@ -425,7 +425,7 @@ int rebuild_wide(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t 
     return RSGPU_OK;
 }
 
-// the five kernel choices: 0 (AUTO) to `last` into the context's member
+// the six kernel choices: 0 (AUTO) to `last` into the context's member
 int set_kernel(rsgpu_ctx* ctx, int kernel, int last, int rsgpu_ctx::*choice, const char* msg)
 {
     if (!ctx || kernel < 0 || kernel > last)
@@ -464,6 +464,11 @@ int rsgpu_set_locate_kernel(rsgpu_ctx* ctx, int kernel)
 int rsgpu_set_degraded_kernel(rsgpu_ctx* ctx, int kernel)
 {
     return set_kernel(ctx, kernel, RSGPU_DEGRADED_FUSED, &rsgpu_ctx::degraded_kernel, "rsgpu_set_degraded_kernel: unknown kernel");
+}
+
+int rsgpu_set_correct_kernel(rsgpu_ctx* ctx, int kernel)
+{
+    return set_kernel(ctx, kernel, RSGPU_CORRECT_FUSED, &rsgpu_ctx::correct_kernel, "rsgpu_set_correct_kernel: unknown kernel");
 }
 
 int rsgpu_set_repair_kernel(rsgpu_ctx* ctx, int kernel)
@@ -668,7 +673,7 @@ int rsgpu_correct_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch,
     }
     CorrectFold* fold = reinterpret_cast<CorrectFold*>(d_report);
     RS_HIP(ctx, hipMemsetAsync(d_report, 0, blocks * sizeof(rsgpu_correct_report), ctx->stream));
-    // the two-pass form only: per slice of the scratch the encode, then the
+    // TWO_PASS (and AUTO): per slice of the scratch the encode, then the
     // correcting compare while the slice's computed parity is still there
     auto compare = [&](size_t b0, size_t nb, const uint8_t* calc) -> int {
         CorrectCmpArgs a =
@@ -679,9 +684,20 @@ int rsgpu_correct_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch,
         RS_HIP(ctx, launch_correct_compare(a, ctx->stream));
         return RSGPU_OK;
     };
+    // FUSED (rsgpu_set_correct_kernel), on the rows the fused kernels take: a
+    // slice is one launch of the compiled code's kernel, which compares in
+    // registers and corrects in its cold path; no scratch, no locate tables
+    const bool fused = work && ctx->correct_kernel == RSGPU_CORRECT_FUSED &&
+                       fused_rows(k, e, len, pitch, d_src, d_parity, coef);
     // block index in grid.y: larger batches as consecutive slices
-    rc = for_grid_slices(work ? blocks : 0, [&](size_t b0, size_t nb) {
-        return two_pass(ctx, k, e, len, pitch, b0, nb, d_src, coef, &loc, compare);
+    rc = for_grid_slices(work ? blocks : 0, [&](size_t b0, size_t nb) -> int {
+        if (!fused)
+            return two_pass(ctx, k, e, len, pitch, b0, nb, d_src, coef, &loc, compare);
+        KTimer kt(ctx, "k_rs_bs_correct", nb);
+        RS_HIP(ctx, launch_rs_bitsliced_correct(k, e, d_src + b0 * k * pitch, d_parity + b0 * e * pitch,
+                                                (long long)pitch, (long long)len, (long long)nb, fold + b0, t,
+                                                ctx->stream));
+        return RSGPU_OK;
     });
     if (rc)
         return rc;

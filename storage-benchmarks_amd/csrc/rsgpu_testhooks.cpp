@@ -20,6 +20,7 @@
 #include "rs_jit.h"
 #include "rs_kernels.h"
 #include "rs_lane.h"
+#include "rs_pairs.h"
 #include "rsgpu_ctx.h"
 
 using namespace rsgpu;
@@ -405,6 +406,47 @@ int rsgpu_internal_plane_mul_acc(unsigned c, const uint32_t* s, uint32_t* t)
     plane_mul_acc(tv, sv, c);
     std::memcpy(t, tv, sizeof tv);
     return RSGPU_OK;
+}
+
+// Test hook (not part of include/rsgpu.h): k_rs_bs_correct's pair search
+// (rs_pairs.h rs_pair_search_lane) on the host, for the CPU suite to compare
+// with the model's brute force: the gf_gen_rs_matrix code (k, e), the syndrome
+// column syn [e]; every lane of 64 searches, and the lanes' results combine as
+// the kernel's ballots combine them.  Returns the number of matching pairs (0,
+// 1, or 2 for several); with 1, out [4] = row a, row b, x_a, x_b.
+int rsgpu_internal_rs_pair_search(int k, int e, const unsigned char* syn, int* out)
+{
+    if (k < 1 || k > 255 || e < 3 || e > 64 || !syn || !out)
+        return RSGPU_ERR_ARG;
+    static const GfTables gf = make_gf_tables();
+    PairGf g;
+    for (int i = 0; i < (int)sizeof g; ++i)
+        reinterpret_cast<uint8_t*>(&g)[i] = pair_gf_byte(gf, i);
+    std::vector<CorRow> row((size_t)k);
+    for (int r = 0; r < k; ++r)
+        row[r] = rs_pair_row(g, syn[0], syn[1], syn[2], r);
+    uint8_t wsyn[64] = {};
+    std::memcpy(wsyn, syn, (size_t)e);
+    bool several = false;
+    int holders = 0;
+    CorPairs held{};
+    for (int lane = 0; lane < 64; ++lane) {
+        const CorPairs c = rs_pair_search_lane(g, k, e, wsyn, row.data(), lane);
+        several |= c.cnt >= 2;
+        if (c.cnt == 1) {
+            ++holders;
+            held = c;
+        }
+    }
+    if (several || holders > 1)
+        return 2;
+    if (holders == 0)
+        return 0;
+    out[0] = held.ra;
+    out[1] = held.rb;
+    out[2] = held.xa;
+    out[3] = held.xb;
+    return 1;
 }
 
 }  // extern "C"

@@ -41,7 +41,7 @@ __all__ = [
     "UPDATE_NONE", "UPDATE_DELTA", "LOST_NONE", "SCRUB_UNCHECKED", "SCRUB_BAD_MATRIX",
     "SCRUB_BAD_LIST", "REBUILD_CHECK", "REBUILD_MAX_LOST", "REBUILD_KERNELS", "SCRUB_ROWS",
     "LOCATE_MAX_ROWS", "LOCATE_KERNELS", "CORRECT_REPORT_DTYPE", "DEGRADED_KERNELS",
-    "REPAIR_KERNELS",
+    "REPAIR_KERNELS", "CORRECT_KERNELS",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -99,6 +99,8 @@ LOCATE_KERNELS = {"auto": 0, "two_pass": 1, "fused": 2}
 DEGRADED_KERNELS = {"auto": 0, "two_pass": 1, "fused": 2}
 # rsgpu_set_repair_kernel choices
 REPAIR_KERNELS = {"auto": 0, "generated": 1}
+# rsgpu_set_correct_kernel choices
+CORRECT_KERNELS = {"auto": 0, "two_pass": 1, "fused": 2}
 
 vp = C.c_void_p
 sz = C.c_size_t
@@ -159,6 +161,7 @@ _SIGS = {
     "rsgpu_set_locate_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_set_degraded_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_set_repair_kernel": (C.c_int, [vp, C.c_int]),
+    "rsgpu_set_correct_kernel": (C.c_int, [vp, C.c_int]),
     "rsgpu_update_blocks": (C.c_int, [vp, C.c_int, C.c_int, sz, sz, sz, C.c_int, vp, vp, vp, vp, vp,
                                       C.c_int, vp]),
     "rsgpu_host_alloc": (C.c_int, [vp, C.POINTER(vp), sz]),
@@ -501,6 +504,18 @@ class Context:
         set_scrub_kernel has no influence on these calls."""
         self.check(lib().rsgpu_set_degraded_kernel(self._h, DEGRADED_KERNELS[kernel]),
                    "rsgpu_set_degraded_kernel")
+
+    def set_correct_kernel(self, kernel: str) -> None:
+        """Kernel of correct_blocks (so of GpuEncoder.correct): auto | two_pass
+        | fused (include/rsgpu.h rsgpu_set_correct_kernel); every choice
+        writes the same rows and reports.  fused: one launch of the compiled
+        encode's program per slice with the stored parity compared in
+        registers and the one- and two-row corrections in the cold path,
+        where the fused scrub applies (the compiled codes, no coef, 16-byte
+        aligned rows, len % 32 == 0); otherwise two_pass, silently.  Opt-in,
+        auto runs two_pass; set_scrub_kernel has no influence on this call."""
+        self.check(lib().rsgpu_set_correct_kernel(self._h, CORRECT_KERNELS[kernel]),
+                   "rsgpu_set_correct_kernel")
 
     def set_repair_kernel(self, kernel: str) -> None:
         """Kernel of repair_blocks (so of GpuEncoder.repair): auto | generated

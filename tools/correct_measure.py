@@ -19,12 +19,20 @@ brings the rows back, which an untimed, checked run of each kind and a scrub at
 the end confirm.  Then `rounds` mirrored rounds, every kind twice per round.  A
 run's time is the sum of its kernels' HIP-event times from rsgpu_timing_read.
 
+With --fused the fused forms are measured beside them
+(profiles/correct_fused/README.md): `fused_correct_*` is rsgpu_correct_blocks
+under rsgpu_set_correct_kernel FUSED (k_rs_bs_correct) on the same kinds of
+damage, `fused_columns_clean` is rsgpu_repair_blocks COLUMNS under the FUSED
+scrub kernel (k_rs_bs_repair), the yardstick of `fused_correct_clean`; the
+summary holds that ratio over the mirrored pairs as well.  The kinds of a run
+are then the fused ones and `correct_clean`; --kinds names others.
+
 Besides the statistics per kind the summary holds correct_clean /
 columns_clean over the mirrored pairs (same round, same half), to be read
 against the two kinds' own run-to-run spread.
 
     python tools/correct_measure.py out.json [--k 64 --e 32 --len 1000000 --blocks 1024 --rounds 12]
-                                             [--skip kind,kind]
+                                             [--skip kind,kind] [--fused] [--kinds kind,kind]
 """
 import sys
 
@@ -42,6 +50,8 @@ SCATTER = 12
 def main():
     ap = ml.shape_parser()
     ap.add_argument("--skip", default="", help="kinds to leave out, comma separated")
+    ap.add_argument("--fused", action="store_true", help="the fused kinds and correct_clean")
+    ap.add_argument("--kinds", default="", help="exactly these kinds, comma separated")
     a = ap.parse_args()
     k, e, L, B = a.k, a.e, a.len, a.blocks
     assert k >= SCATTER and 5 <= e <= 64
@@ -83,12 +93,17 @@ def main():
     one = lambda: sparse(r1, c1, x1)  # noqa: E731
     two = lambda: (sparse(r1, c1, x1), sparse(r2, c1, x2))  # noqa: E731
     both = lambda: (whole(r1, w1), whole(r2, w2))  # noqa: E731
+    FUSED = "fused_"
     damage = {"correct1_one": one, "correct_one": one, "correct_two": two, "correct_whole": both,
               "correct_scattered": scattered, "heal_one": one, "heal_two": two, "heal_whole": both}
     torch.cuda.synchronize()
 
     def run(kind):
         """One timed run: (ms, {kernel name: ms})."""
+        fused = kind.startswith(FUSED)
+        kind = kind[len(FUSED):] if fused else kind
+        ctx.set_scrub_kernel("fused" if fused else "two_pass")
+        ctx.set_correct_kernel("fused" if fused else "two_pass")
         if kind in damage:
             damage[kind]()
             torch.cuda.synchronize()
@@ -103,9 +118,14 @@ def main():
         return ml.timed(ctx, lambda: ctx.correct_blocks(k, e, L, pitch, B, enc.src, enc.par, crep, t=t))
 
     skip = set(filter(None, a.skip.split(",")))
-    kinds = [kd for kd in ["columns_clean", "correct_clean", "correct1_one", "correct_one", "correct_two",
-                           "correct_whole", "correct_scattered", "heal_one", "heal_two", "heal_whole"]
-             if kd not in skip]
+    every = ["columns_clean", "correct_clean", "correct1_one", "correct_one", "correct_two",
+             "correct_whole", "correct_scattered", "heal_one", "heal_two", "heal_whole"]
+    if a.fused:
+        every = [FUSED + "columns_clean", FUSED + "correct_clean", "correct_clean", FUSED + "correct_one",
+                 FUSED + "correct_two", FUSED + "correct_scattered", FUSED + "correct_whole"]
+    if a.kinds:
+        every = a.kinds.split(",")
+    kinds = [kd for kd in every if kd not in skip]
     bad = {"correct1_one": (ncols, 0), "correct_one": (ncols, 0), "correct_two": (ncols, ncols),
            "correct_whole": (L, L), "correct_scattered": (part * (SCATTER // 2), part * (SCATTER // 2))}
     kernels_seen = {}
@@ -114,15 +134,21 @@ def main():
         ms, by = run(kind)
         print(f"checked {kind}: {ms:.2f} ms", file=sys.stderr, flush=True)
         kernels_seen[kind] = sorted(by)
+        fused = kind.startswith(FUSED)
+        kind = kind[len(FUSED):] if fused else kind
         if kind == "columns_clean":
             r = rrep.cpu().numpy().view(rsgpu.REPAIR_REPORT_DTYPE)
-            assert (r["status"] == rsgpu.REPAIR_CLEAN).all() and "k_repair_compare" in by, kind
+            assert (r["status"] == rsgpu.REPAIR_CLEAN).all(), kind
+            assert sorted(by) == ["k_repair_finalise", "k_rs_bs_repair"] if fused else "k_repair_compare" in by, by
         elif kind.startswith("heal"):
             r = srep.cpu().numpy().view(rsgpu.SCRUB_REPORT_DTYPE)
             assert (r["status"] == (rsgpu.SCRUB_ONE_ROW if kind == "heal_one" else rsgpu.SCRUB_ROWS)).all(), kind
         else:
             r = crep.cpu().numpy().view(DT)
-            assert "k_correct_compare" in by, kind
+            if fused:
+                assert sorted(by) == ["k_correct_finalise", "k_rs_bs_correct"], by
+            else:
+                assert "k_correct_compare" in by, kind
             if kind == "correct_clean":
                 assert (r["status"] == rsgpu.REPAIR_CLEAN).all() and (r["bad_columns"] == 0).all(), kind
             else:
@@ -132,6 +158,7 @@ def main():
         ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, srep)
         torch.cuda.synchronize()
         assert ml.all_clean(srep), "the blocks after " + kind
+        bad[FUSED + kind] = bad.get(kind, (0, 0))
 
     def progress(kind):
         out = run(kind)
@@ -154,7 +181,19 @@ def main():
         cmp_ratios = [r["kernels"]["k_correct_compare"] for r in out["runs"] if r["kind"] == "correct_clean"]
         rep_ratios = [r["kernels"]["k_repair_compare"] for r in out["runs"] if r["kind"] == "columns_clean"]
         summ["correct_clean"]["compare_kernel_over_columns"] = float(np.median(cmp_ratios) / np.median(rep_ratios))
+    fc, fr = FUSED + "correct_clean", FUSED + "columns_clean"
+    if fc in kinds and fr in kinds:
+        ratios = [at[(rnd, h, fc)] / at[(rnd, h, fr)] for rnd in range(a.rounds) for h in (False, True)]
+        summ[fc]["over_fused_columns_in_pairs"] = ml.stats(ratios)
+        summ[fc]["over_fused_columns_in_pairs"]["mean"] = float(np.mean(ratios))
+        # the pairs' own run-to-run spread: each kind's two runs of a round against each other
+        for kd in (fc, fr):
+            own = [at[(rnd, False, kd)] / at[(rnd, True, kd)] for rnd in range(a.rounds)]
+            summ[kd]["first_over_second_half"] = {**ml.stats(own), "mean": float(np.mean(own))}
+        if "correct_clean" in kinds:
+            summ[fc]["over_two_pass_median"] = summ[fc]["median"] / summ["correct_clean"]["median"]
     ml.finish(a.out, out, summ)
+    ctx.set_correct_kernel("auto")
     ctx.set_scrub_kernel("auto")
     ctx.set_locate_kernel("auto")
     ctx.close()
