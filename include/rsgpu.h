@@ -102,7 +102,11 @@ void rsgpu_ec_init_tables(int k, int rows, unsigned char *a, unsigned char *gftb
  * isa/ec_highlevel_func.c:106-135 avx2 split): coding[r][i] =
  * XOR_j c[r][j]*data[j][i].  `gftbls` is HOST memory in ISA-L's 32-byte table
  * format (as produced by ec_init_tables); `data` / `coding` are HOST arrays
- * of DEVICE pointers; any len >= 0 and any alignment. */
+ * of DEVICE pointers; any len >= 0 and any alignment.
+ *
+ * This and the other pointer calls below write bytes [0, len) of each output
+ * row (coding[r], dest) and nothing else: no byte before or behind a row, and
+ * never any byte of data[j] / src. */
 int rsgpu_ec_encode_data(rsgpu_ctx *ctx, int len, int k, int rows, const unsigned char *gftbls,
                          unsigned char **data, unsigned char **coding);
 
@@ -122,7 +126,9 @@ int rsgpu_ec_encode_data_update(rsgpu_ctx *ctx, int len, int k, int rows, int ve
  *     c[vec_i] * src[i], tables of vec coefficients.
  *   gf_vect_mul.h:108 gf_vect_mul (isa/ec_base.c:323-329): dest[i] =
  *     c * src[i] with c = gftbl[1]; returns 0, or non-zero when len is not a
- *     multiple of 32 (the dispatched ISA-L function's contract). */
+ *     multiple of 32 (the dispatched ISA-L function's contract), and then
+ *     writes nothing.
+ * Each writes [0, len) of dest only (see rsgpu_ec_encode_data). */
 int rsgpu_gf_vect_dot_prod(rsgpu_ctx *ctx, int len, int vlen, const unsigned char *gftbls,
                            unsigned char **src, unsigned char *dest);
 int rsgpu_gf_vect_mad(rsgpu_ctx *ctx, int len, int vec, int vec_i, const unsigned char *gftbls,
@@ -134,7 +140,11 @@ int rsgpu_gf_vect_mul(rsgpu_ctx *ctx, int len, const unsigned char *gftbl, void 
 /* isa_encoder::encode_all over `blocks` independent blocks (isa.cpp:69-79):
  * parity[b][p] = XOR_j a[k+p][j] * src[b][j] with a = gf_gen_rs_matrix(k+e, k)
  * when `coef` is NULL, else with the HOST e x k row-major matrix `coef`.
- * src: [blocks][k] rows, parity: [blocks][e] rows, both at `pitch`. */
+ * src: [blocks][k] rows, parity: [blocks][e] rows, both at `pitch`.
+ *
+ * Under every encode kernel the call writes bytes [0, len) of each parity row
+ * and nothing else: bytes in [len, pitch) of any row are never written, nor
+ * is any byte of d_src. */
 int rsgpu_encode_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                         const unsigned char *d_src, unsigned char *d_parity,
                         const unsigned char *coef);
@@ -226,7 +236,15 @@ int rsgpu_set_decode_kernel(rsgpu_ctx *ctx, int kernel);
  * block with a non-zero status is skipped; its output is unspecified.
  * d_workspace holds rsgpu_decode_workspace_bytes() bytes.  Batches of more
  * than 65535 blocks run as consecutive slices (as do rsgpu_encode_blocks,
- * rsgpu_decode_general and rsgpu_verify_blocks). */
+ * rsgpu_decode_general and rsgpu_verify_blocks).
+ *
+ * What the call writes, under every decode kernel: bytes [0, len) of each of
+ * the blocks x e rows of d_out, the first rsgpu_decode_workspace_bytes() bytes
+ * of d_workspace and the first `blocks` ints of d_status.  Bytes in [len,
+ * pitch) of any row are never written, nor is any byte of d_src, d_parity or
+ * d_err, any byte of d_workspace beyond rsgpu_decode_workspace_bytes(), or any
+ * int of d_status beyond `blocks`.  A block with a non-zero status has
+ * unspecified bytes only in [0, len) of its own output rows. */
 int rsgpu_decode_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                         const unsigned char *d_src, const unsigned char *d_parity,
                         const unsigned char *d_err, unsigned char *d_out, void *d_workspace,
@@ -243,7 +261,12 @@ int rsgpu_decode_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, 
  * the workspace layout) from them.  The generated-code decode keeps the code
  * of the context's LAST prepare: an apply whose (k, e, blocks, workspace)
  * differ from it, or that follows another decode call on the context (which
- * rewrites or regrows the code), returns RSGPU_ERR_ARG and launches nothing. */
+ * rewrites or regrows the code), returns RSGPU_ERR_ARG and launches nothing.
+ *
+ * Together the two write what rsgpu_decode_blocks writes, and never what it
+ * never writes: the prepare only the first rsgpu_decode_workspace_bytes()
+ * bytes of d_workspace and the first `blocks` ints of d_status (no byte of
+ * d_out), the apply only bytes [0, len) of the rows of d_out. */
 int rsgpu_decode_prepare(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                          const unsigned char *d_src, const unsigned char *d_parity,
                          const unsigned char *d_err, unsigned char *d_out, void *d_workspace,
@@ -265,7 +288,15 @@ int rsgpu_decode_apply(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, s
  * singular the reference's retry (replace the last survivor by a later row,
  * :163-184) runs, and only when that fails the block gets status -1 ("BAD
  * MATRIX").  Status -2: malformed list (not ascending, index >= m, or more
- * than m - k erasures).  Erased rows are never read. */
+ * than m - k erasures).  Erased rows are never read.
+ *
+ * The call writes bytes [0, len) of each of the blocks x nerrs rows of d_out,
+ * the first rsgpu_decode_general_workspace_bytes() bytes of d_workspace and
+ * the first `blocks` ints of d_status.  Bytes in [len, pitch) of any row are
+ * never written, nor is any byte of d_src, d_parity or d_err, any byte of
+ * d_workspace beyond that size, or any int of d_status beyond `blocks`.  A
+ * block with a non-zero status has unspecified bytes only in [0, len) of its
+ * own output rows. */
 size_t rsgpu_decode_general_workspace_bytes(int k, int m, int nerrs, size_t blocks);
 int rsgpu_decode_general(rsgpu_ctx *ctx, int k, int m, size_t len, size_t pitch, size_t blocks,
                          const unsigned char *encode_matrix, const unsigned char *d_src,
@@ -1105,7 +1136,10 @@ int rsgpu_host_free(rsgpu_ctx *ctx, void *hptr);
  * rows, at `pitch` >= len.  The batch streams through device staging in
  * chunks, copy-in / rsgpu_encode_blocks / copy-out of consecutive chunks
  * overlapped on three streams.  Synchronous: the parity is in h_parity on
- * return.  `coef` as rsgpu_encode_blocks. */
+ * return.  `coef` as rsgpu_encode_blocks.  In host memory the call writes
+ * bytes [0, len) of each row of h_parity and nothing else, whatever the
+ * pitch: bytes in [len, pitch) of any row are never written, nor is any byte
+ * of h_src. */
 int rsgpu_encode_blocks_host(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                              const unsigned char *h_src, unsigned char *h_parity,
                              const unsigned char *coef);
@@ -1117,7 +1151,13 @@ int rsgpu_encode_blocks_host(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pi
  * whole blocks, erased rows included, which the kernels never read) and the
  * parity rows -- and the recovered rows land in h_out [blocks][e] (in h_err
  * order).  h_status [blocks] (may be NULL) receives rsgpu_decode_blocks'
- * per-block status.  Pipelined and synchronous as rsgpu_encode_blocks_host. */
+ * per-block status.  Pipelined and synchronous as rsgpu_encode_blocks_host.
+ * In host memory the call writes bytes [0, len) of each of the blocks x e
+ * rows of h_out and `blocks` ints of h_status, and nothing else: bytes in
+ * [len, pitch) of any row are never written, nor is any byte of h_src,
+ * h_parity or h_err, or any int of h_status beyond `blocks`.  A block with a
+ * non-zero status has unspecified bytes only in [0, len) of its own rows of
+ * h_out. */
 int rsgpu_decode_blocks_host(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                              const unsigned char *h_src, const unsigned char *h_parity,
                              const unsigned char *h_err, unsigned char *h_out, int *h_status);

@@ -77,15 +77,18 @@ int io_setup(rsgpu_ctx* ctx, size_t bytes)
     return RSGPU_OK;
 }
 
-// rows x len bytes between pitches (one 2D copy; a plain one when both
-// pitches are equal)
+// rows x len bytes between pitches: one 2D copy, or a plain one where
+// nothing but row bytes lies between the first and the last byte copied (a
+// single row, or rows without padding on both sides).  Equal pitches with
+// padding still go row by row: a flat copy would carry the source's padding
+// (stale staging content on the way out) over the destination's [len, pitch)
 hipError_t copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t len, size_t rows,
                      hipMemcpyKind kind, hipStream_t st)
 {
     if (rows == 0 || len == 0)
         return hipSuccess;
-    if (dpitch == spitch)
-        return hipMemcpyAsync(dst, src, (rows - 1) * spitch + len, kind, st);
+    if (rows == 1 || (dpitch == len && spitch == len))
+        return hipMemcpyAsync(dst, src, rows * len, kind, st);
     return hipMemcpy2DAsync(dst, dpitch, src, spitch, len, rows, kind, st);
 }
 
