@@ -380,7 +380,9 @@ int rsgpu_scrub_locatable(int k, int e, const unsigned char *coef);
  *             rsgpu_set_repair_kernel's GENERATED (below, at
  *             rsgpu_repair_blocks).  rsgpu_locate_blocks does, under
  *             rsgpu_set_locate_kernel's FUSED (below): the two settings
- *             together select the generated locate.
+ *             together select the generated locate.  rsgpu_correct_blocks
+ *             does likewise, under rsgpu_set_correct_kernel's FUSED (below),
+ *             for the matrices that are not compiled in.
  *             Measured on an MI355X, 1 MB rows, 1.5 GB of rows per call, clean
  *             data, kernel times, medians of 24 runs: (10,4) 0.37 ms against
  *             0.49 ms TWO_PASS (gf_gen_rs_matrix and Cauchy alike), (6,3) 0.40
@@ -1001,9 +1003,11 @@ int rsgpu_set_repair_kernel(rsgpu_ctx *ctx, int kernel);
  * 189.1 ms on the one-row, two-row and whole-row damage.  Advice: scrub
  * first; where the damage lies in whole rows, locate and rebuild; take this
  * call for the blocks they give up as DAMAGED, whose damage is scattered.
- * rsgpu_set_scrub_kernel has no influence on this call.
- * Not built: a form fused into the generated encode, for matrices that are
- * not compiled in; t > 2; e > 64; host-resident blocks. */
+ * rsgpu_set_scrub_kernel decides one thing for this call: under
+ * rsgpu_set_correct_kernel's FUSED, RSGPU_SCRUB_GENERATED selects the form
+ * fused into the generated encode for the matrices that are not compiled in
+ * (below).  Under AUTO and TWO_PASS it has no influence.
+ * Not built: t > 2; e > 64; host-resident blocks. */
 typedef struct rsgpu_correct_report {
     unsigned long long bad_columns;       /* before the call */
     unsigned long long corrected_columns; /* columns written, one- and two-row together */
@@ -1063,6 +1067,42 @@ int rsgpu_correct_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch,
  *             pitch % 16 == 0, 16-byte aligned d_src and d_parity, len % 32 ==
  *             0, len < 4 GiB -- so t = 2 on (16,8) (20,7) (64,16) (64,32)
  *             (100,20), t = 1 on those and on (16,4) (5,4).
+ *             Otherwise, when the context's scrub kernel is
+ *             RSGPU_SCRUB_GENERATED (rsgpu_set_scrub_kernel: the family's
+ *             opt-in to the generated programs), fused into the generated
+ *             encode: any matrix, with or without `coef`, for e <= 64, 16-byte
+ *             aligned rows (pitch % 16 == 0), len % 32 == 0 and len < 4 GiB, on
+ *             a device with an executable memory pool.  Per slice one launch of
+ *             k_rs_jit_correct (e <= 16) or k_rs_jitw_correct (both recorded as
+ *             k_rs_jit_correct) on the matrix's shared program, which is the
+ *             GENERATED repair's kernel in its COLUMNS mode -- the stored
+ *             parity compared in registers, nothing written for a clean
+ *             workgroup -- then k_correct_finalise; no encode, no parity
+ *             scratch.  A dirty workgroup lays its syndromes into LDS in eight
+ *             passes of 256 columns per tile; a column one row explains is
+ *             corrected as COLUMNS corrects it, and with t = 2 the others go to
+ *             their wave one at a time while the pass's syndromes are in LDS:
+ *             TWO_PASS's search on the matrix read from memory, rows 0 to 2 of
+ *             it kept as logarithms in LDS (3 k bytes per workgroup, beside the
+ *             field's 1.3 KB; 8 k bytes per wave for the rows of a column).
+ *             Those tables share the encode's chunk buffers with the
+ *             syndromes.  They fit for every k + e <= 250 in every layout but
+ *             the four waves of 16 rows (48 < e <= 64), which take t = 2 while
+ *             256 e + 32 k <= 21240: every k up to e = 59, k <= 151 at e = 64;
+ *             beyond that t = 2 falls back to TWO_PASS (t = 1 never does).  No
+ *             kernel has scratch, each runs at its k_rs_jit_repair /
+ *             k_rs_jitw_repair sibling's waves per SIMD
+ *             (profiles/correct_generated).  Its times are not measured yet.
+ *             Hot path and clean exit are the GENERATED repair's, so clean
+ *             blocks should cost what its COLUMNS mode costs; the eight-pass
+ *             cold path is small code, not fast code, and loses to TWO_PASS on
+ *             damaged blocks at small e in the generated locate and repair
+ *             (profiles/locate_generated, profiles/repair_generated): expect
+ *             the same here, and take this form for scrub passes over mostly
+ *             clean blocks.
+ *             The compiled form has precedence where both apply; under any
+ *             other scrub kernel FUSED falls back to TWO_PASS for a matrix that
+ *             is not compiled in.
  * A choice that does not apply falls back to TWO_PASS, silently. */
 #define RSGPU_CORRECT_AUTO 0
 #define RSGPU_CORRECT_TWO_PASS 1

@@ -31,6 +31,7 @@
 #include "rs_jit.h"
 #include "rs_kernels.h"
 #include "rs_lane.h"
+#include "rs_pairs.h"
 #include "rs_span.h"
 #include "tc_handlers.inc"
 
@@ -251,6 +252,144 @@ struct LocLds {
     static_assert(NV == 1 || NV == 2 || NV == 4, "the waves divide the tile's 64 lanes");
 };
 
+// The correction per column (rsgpu_correct_blocks under FUSED with the scrub
+// kernel GENERATED; k_rs_jit_correct, k_rs_jitw_correct): JitRepair in its
+// kRepairColumns mode on the 32-byte fold.  With t == 2 a bad column that no
+// row explains is pending instead of left: when a trip of the walk ends --
+// thread wave 64 + lane of a tile's NV 64 takes columns wave 64 + lane, + 64 NV,
+// ... of the pass's 256, so wave w owns tile lanes 16 w .. 16 w + 15 (mod 16
+// NV) and makes 4 / NV trips -- the wave takes the trip's pending columns one
+// at a time, all 64 lanes on each, under wave-uniform control
+// (correct_pending, below), while the pass's syndromes are still in LDS,
+// before the pass's closing barrier.  A two-row correction adds to `rep` and
+// `two` and sets the fold's hi1 / lo1 to kScrubNoRow.  In place for
+// JitRepair's reasons: the two bytes are bytes of the dword the pass owns, in
+// rows whose sources every wave has read before the body's last barrier.
+// LDS, in the chunk buffers (CorLds): masks | syn [TPW][e][256] | PairGf, the
+// workgroup's | rows 0 to 2 of the matrix as logarithms, the workgroup's, in
+// the mask part's free end where the masks leave 768 bytes | per wave
+// CorRow [k].  syn keeps JitRepair's row stride of 256 bytes and not kLocRow:
+// no read of this search is strided by the lane -- a column's syndromes are
+// read at the same address in every lane (pair_search_lane) -- and 4 bytes
+// more per row would cost the four-wave 16-row layout 8 more rows of k.
+struct JitCorrect {
+    static constexpr bool kSpan = false;
+    static constexpr bool kRepair = true;
+    static constexpr int locate = 1;
+    static constexpr int mode = kRepairColumns;
+    CorrectFold* fold;  // [B], zeroed
+    const uint8_t* tab;
+    int t;
+    uint8_t* src;  // [B][k] rows of the slice
+    uint8_t* par;  // [B][e] rows of the slice, the stored parity
+    long long pitch, len;
+    long long tile0 = 0;  // k_rs_jitw_correct: the first column of the wave's tile (JitwEpi)
+};
+
+template <int NV, int TPW>
+struct CorLds {
+    static constexpr int kWaves = NV * TPW;
+    static constexpr int kGfBytes = ((int)sizeof(PairGf) + 7) / 8 * 8;
+    static constexpr int kLogBytes = 3 * 256;
+    // the masks take 4 kWaves 64 bytes of their part
+    static constexpr bool kLogInMasks = 4 * kWaves * 64 + kLogBytes <= kScrubMaskBytes;
+    static constexpr int gf_at(int e) { return kScrubMaskBytes + TPW * e * 256; }
+    static constexpr int log_at(int e) { return kLogInMasks ? kScrubMaskBytes - kLogBytes : gf_at(e) + kGfBytes; }
+    static constexpr int rows_at(int e) { return gf_at(e) + kGfBytes + (kLogInMasks ? 0 : kLogBytes); }
+    static constexpr int bytes(int k, int e) { return rows_at(e) + kWaves * k * (int)sizeof(CorRow); }
+    // every (k, e) of e0 <= e <= e1 with k + e <= 250
+    static constexpr bool fits_all(int e0, int e1, int cap)
+    {
+        for (int e = e0; e <= e1; ++e)
+            if (bytes(250 - e, e) > cap)
+                return false;
+        return true;
+    }
+    static_assert(sizeof(PairGf) == 1284 && sizeof(CorRow) == 8 && kScrubMaskBytes % 8 == 0 && kGfBytes % 8 == 0 &&
+                      kLogBytes % 8 == 0,
+                  "the rows' tables are aligned");
+};
+
+typedef __attribute__((address_space(3))) uint8_t cor_lds_u8;
+typedef __attribute__((address_space(3))) const PairGf cor_lds_gf;
+typedef __attribute__((address_space(3))) CorRow cor_lds_row;
+
+// The workgroup's tables of the search, on entry to the cold path: read from
+// the first pass's barrier on; the chunk buffers are free since the barrier
+// before the masks.
+template <int NV, int TPW>
+__device__ __forceinline__ void correct_tables(const uint8_t* tab, int k, int e, uint8_t* ldsb, int tid)
+{
+    using Lay = CorLds<NV, TPW>;
+    cor_lds_u8* gfb = (cor_lds_u8*)ldsb + Lay::gf_at(e);
+    cor_lds_u8* lg = (cor_lds_u8*)ldsb + Lay::log_at(e);
+#pragma unroll 1
+    for (int i = tid; i < (int)sizeof(PairGf); i += 64 * NV * TPW)
+        gfb[i] = pair_gf_byte(kGfJit, i);
+#pragma unroll 1
+    for (int r = tid; r < k; r += 64 * NV * TPW) {
+        lg[r] = pair_log8(kGfJit, tab[256 + r]);
+        lg[256 + r] = pair_log8(kGfJit, tab[256 + k + r]);
+        lg[512 + r] = pair_log8(kGfJit, tab[256 + 2 * k + r]);
+    }
+}
+
+// The pending columns of a trip of the walk (`pend`, a lane each; lane 0's is
+// column c0 of the pass), one after the other, the whole wave on each: the
+// search of rs_correct.hip's head on the tables above, the lanes' matches
+// counted up to two, and the lane that holds the only one XORs both bytes into
+// the global rows; two matching pairs, or none, leave the column byte for
+// byte.  Returns the columns corrected, the same in every lane.
+template <int NV, int TPW>
+__device__ __forceinline__ unsigned correct_pending(const JitCorrect& s, bool pend, int c0, int pass, int k, int e,
+                                                    int b, long long tile0, int lane, int slot, int tw,
+                                                    uint8_t* ldsb)
+{
+    using Lay = CorLds<NV, TPW>;
+    unsigned long long todo = __ballot(pend);
+    if (!todo)
+        return 0;
+    cor_lds_u8* syn = (cor_lds_u8*)ldsb + kScrubMaskBytes + tw * e * 256;
+    cor_lds_gf* gf = (cor_lds_gf*)((cor_lds_u8*)ldsb + Lay::gf_at(e));
+    cor_lds_u8* lg = (cor_lds_u8*)ldsb + Lay::log_at(e);
+    cor_lds_row* row = (cor_lds_row*)((cor_lds_u8*)ldsb + Lay::rows_at(e)) + slot * k;
+    unsigned done = 0;
+    while (todo) {
+        const int c = c0 + __ffsll(todo) - 1;
+        todo &= todo - 1;
+        // what every lane reads at one address goes to a scalar register
+        auto uniform = [](unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); };
+        const unsigned ls0 = uniform(pair_logp(gf, syn[c])), ls1 = uniform(pair_logp(gf, syn[256 + c])),
+                       ls2 = uniform(pair_logp(gf, syn[512 + c]));
+#pragma unroll 1
+        for (int r = lane; r < k; r += 64) {
+            const CorRow v = pair_row(gf, ls0, ls1, ls2, lg[r], lg[256 + r], lg[512 + r]);
+            row[r].a0 = v.a0;
+            row[r].a1 = v.a1;
+            row[r].c2 = v.c2;
+            row[r].u = v.u;
+        }
+        // what a lane wrote is read by the other lanes of the wave from here on
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        const CorPairs p = pair_hits(pair_search_lane(gf, k, e, syn + c, 256, lg, lg + 256, lg + 512, row,
+                                                      (const g_u8*)(s.tab + 256), lane, uniform));
+        const long long col = tile0 + (c >> 2) * 32 + 4 * pass + (c & 3);
+        const bool one = __ballot(p.cnt >= 2) == 0 && __popcll(__ballot(p.cnt == 1)) == 1 && col < s.len;
+        if (one && p.cnt == 1) {
+            g_u8* ga = (g_u8*)(p.ra < k ? s.src + ((size_t)b * k + p.ra) * s.pitch
+                                        : s.par + ((size_t)b * e + (p.ra - k)) * s.pitch) + col;
+            g_u8* gb = (g_u8*)(p.rb < k ? s.src + ((size_t)b * k + p.rb) * s.pitch
+                                        : s.par + ((size_t)b * e + (p.rb - k)) * s.pitch) + col;
+            *ga ^= p.xa;
+            *gb ^= p.xb;
+        }
+        done += one;
+        // the next column's rows overwrite what the lanes still read here
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    }
+    return done;
+}
+
 template <class SL, int NV, int TPW, class S>
 __device__ __forceinline__ void scrub_slots(const S& s, int k, int e, uint8_t* const* dsts, int b, int r0,
                                             int nrow, int wave, int tw, bool inb, uint32_t po, uint8_t* ldsb,
@@ -338,11 +477,24 @@ __device__ __forceinline__ void scrub_slots(const S& s, int k, int e, uint8_t* c
         sb[tw * NV + wave].n = 0;
         sb[tw * NV + wave].ovf = 0;
     }
+    constexpr bool kCorrect = std::is_same_v<S, JitCorrect>;
+    [[maybe_unused]] unsigned ntwo = 0;  // the correction: the wave's columns corrected in two rows
+    if constexpr (kCorrect)
+        if (s.t == 2)
+            correct_tables<NV, TPW>(s.tab, k, e, ldsb, (tw * NV + wave) * 64 + lane);
 #pragma unroll 1
     for (int pass = 0; pass < 8; ++pass) {
         // bytes 4 pass .. 4 pass + 3 of the lane's 32 of every row (zeros from an idle lane)
         lds_u32* mine4 = (lds_u32*)(syn + r0 * kRow + lane * 4);
         const uint32_t po4 = po + 4 * pass;
+        // the correction: the transposes' masks afresh per pass, so that they
+        // are not live across the pair search of the pass before
+        uint32_t p4 = m4, p2 = m2, p1 = m1;
+        if constexpr (kCorrect) {
+            p4 = vconst(0x0F0F0F0Fu);
+            p2 = vconst(0x33333333u);
+            p1 = vconst(0x55555555u);
+        }
         [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
             (
                 [&] {
@@ -358,7 +510,7 @@ __device__ __forceinline__ void scrub_slots(const S& s, int k, int e, uint8_t* c
                                      : "v"(po4), "s"(dp[Ss])
                                      : "memory");
                         SL::template read<Ss>(W);
-                        tr8(W, m4, m2, m1);  // computed parity, bytes
+                        tr8(W, p4, p2, p1);  // computed parity, bytes
                         uint32_t d = W[0];
 #pragma unroll
                         for (int q = 1; q < 8; ++q)
@@ -392,7 +544,19 @@ __device__ __forceinline__ void scrub_slots(const S& s, int k, int e, uint8_t* c
                 }
             }
         } else {
-            for (int c = wave * 64 + lane; c < 256; c += 64 * NV) {
+            // The correction: a trip's pending column (bad, no row explains it)
+            // goes to the wave when the trip ends, by `continue` or not: the
+            // trip count is the same in every lane, all 64 are there.
+            [[maybe_unused]] bool pend = false;
+            auto trip_ends = [&]([[maybe_unused]] int c) {
+                if constexpr (kCorrect) {
+                    if (s.t == 2)
+                        ntwo += correct_pending<NV, TPW>(s, pend, __builtin_amdgcn_readfirstlane(c - lane), pass, k, e,
+                                                         b, tile0, lane, tw * NV + wave, tw, ldsb);
+                    pend = false;
+                }
+            };
+            for (int c = wave * 64 + lane; c < 256; trip_ends(c), c += 64 * NV) {
                 int nz = 0, p0 = 0;
 #pragma unroll 1
                 for (int p = 0; p < e; ++p) {
@@ -422,6 +586,8 @@ __device__ __forceinline__ void scrub_slots(const S& s, int k, int e, uint8_t* c
                     const bool folds = s.mode == kRepairLocate || (s.mode == kRepairColumns && row >= 0);
                     hi1 = max(hi1, !folds ? 0u : row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
                     lo1 = max(lo1, !folds ? 0u : row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
+                    if constexpr (kCorrect)
+                        pend = row < 0;
                     continue;
                 }
                 hi1 = max(hi1, row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
@@ -443,6 +609,14 @@ __device__ __forceinline__ void scrub_slots(const S& s, int k, int e, uint8_t* c
                                     s.cand + (size_t)b * s.cand_stride + (size_t)at * kLocateSlotBytes);
         }
         return;
+    }
+    if constexpr (kCorrect) {
+        // a two-row correction: no common row of the block's corrected columns
+        hi1 = ntwo ? kScrubNoRow : hi1;
+        lo1 = ntwo ? kScrubNoRow : lo1;
+        nrep += lane == 0 ? ntwo : 0u;
+        if (lane == 0 && ntwo)
+            atomicAdd(&f->two, (unsigned long long)ntwo);
     }
     for (int o = 32; o > 0; o >>= 1) {
         hi1 = max(hi1, (unsigned)__shfl_down((int)hi1, o, 64));
@@ -508,6 +682,8 @@ struct JitEpi8 : S {
         static_assert(kScrubMaskBytes + 32 * 256 <= 2 * C * 2 * 64 * 16, "rows <= 32: syn fits the chunk buffers");
         static_assert(!S::kSpan || LocLds<8, NW, 1>::kBytes <= 2 * C * 2 * 64 * 16,
                       "rows <= 8 NW: masks, syn, tables and bases fit the chunk buffers");
+        static_assert(!std::is_same_v<S, JitCorrect> || CorLds<NW, 1>::fits_all(1, 8 * NW, 2 * C * 2 * 64 * 16),
+                      "rows <= 8 NW: the correction's tables fit the chunk buffers at every k");
         const bool inb = off + 32 <= a.len;
         if constexpr (S::kRepair)
             scrub_slots<Slots8, NW, 1>(static_cast<const S&>(*this), a.k, a.rows, dsts, b, wave * 8,
@@ -522,6 +698,7 @@ struct JitEpi8 : S {
 using JitScrub8 = JitEpi8<JitScrub>;
 using JitLocate8 = JitEpi8<JitLocate>;
 using JitRepair8 = JitEpi8<JitRepair>;
+using JitCorrect8 = JitEpi8<JitCorrect>;
 
 // `int B` and `long long TILE`: this workgroup's block and its tile
 // (k_rs_jitw: its index) within the block.  Workgroups are dealt round-robin
@@ -709,6 +886,20 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void 
                                 JitRepair8{{s.fold, s.tab, s.mode, s.src, s.par, s.pitch, s.j.len}});
 }
 
+// The generated correction for e <= 16: k_rs_jit_repair in its kRepairColumns
+// mode whose cold path, with t == 2, takes the columns no row explains to
+// correct_pending (JitCorrect above)
+template <int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void k_rs_jit_correct(JitCorrectArgs s)
+{
+    __shared__ uint4 lds[2][C * 2 * 64];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(s.j, b, tile)
+    jit_run<NW, true, JitHooks>(s.j, lds, wave, lane, b, tile,
+                                JitCorrect8{{s.fold, s.tab, s.t, s.src, s.par, s.pitch, s.j.len}});
+}
+
 template <int S>
 __device__ __forceinline__ void read_slotw(uint32_t (&W)[8])
 {
@@ -818,8 +1009,31 @@ struct JitwEpi : S {
                       "e <= 32 (two waves), e <= 64 (four): syn fits the chunk buffers");
         static_assert(!S::kSpan || LocLds<W::R, NV, TPW>::kBytes <= 2 * TPW * W::CS * 2 * 64 * 16,
                       "e <= R NV: masks, syn, tables and bases fit the chunk buffers");
+        // the correction's tables: at every k, but for the four waves of 16
+        // rows, whose bound is correct_fits' (256 e + 32 k <= 21240 there)
+        static_assert(!std::is_same_v<S, JitCorrect> || (NV == 4 && W::R == 16) ||
+                          CorLds<NV, TPW>::fits_all(1, NV * W::R, 2 * TPW * W::CS * 2 * 64 * 16),
+                      "e <= R NV: the correction's tables fit the chunk buffers at every k");
+        static_assert(!std::is_same_v<S, JitCorrect> || !(NV == 4 && W::R == 16) ||
+                          (CorLds<4, 1>::fits_all(1, 59, 2 * W::CS * 2 * 64 * 16) &&
+                           CorLds<4, 1>::bytes(151, 64) <= 2 * W::CS * 2 * 64 * 16 &&
+                           CorLds<4, 1>::bytes(152, 64) > 2 * W::CS * 2 * 64 * 16),
+                      "four waves of 16 rows: every k up to e = 59, k <= 151 at e = 64");
         const uint32_t m4 = vconst(0x0F0F0F0Fu), m2 = vconst(0x33333333u), m1 = vconst(0x55555555u);
         const int r0 = jit::wide_row0(a.rows, wave), nrow = jit::wide_row0(a.rows, wave + 1) - r0;
+        if constexpr (std::is_same_v<S, JitCorrect>) {
+            // The lane's offset afresh from the tile's first column, which the
+            // kernel left in the epilogue as a scalar: `off` kept live across
+            // the main loop is the VGPR pair that k_rs_jitw_repair<J10> and
+            // <J12> hold in scratch (profiles/repair_generated/)
+            const long long o =
+                this->tile0 + 32 * (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            const bool in = o + 32 <= a.len;
+            scrub_slots<SlotsW<W::R>, NV, TPW>(static_cast<const S&>(*this), a.k, a.rows, dsts, b, r0, nrow, wave, tw,
+                                               in, in ? (uint32_t)o : 0u, reinterpret_cast<uint8_t*>(lds), m4, m2,
+                                               m1, this->tile0);
+            return;
+        }
         const bool inb = off + 32 <= a.len;
         if constexpr (S::kRepair)
             scrub_slots<SlotsW<W::R>, NV, TPW>(static_cast<const S&>(*this), a.k, a.rows, dsts, b, r0, nrow, wave, tw,
@@ -834,6 +1048,7 @@ struct JitwEpi : S {
 using JitwScrub = JitwEpi<JitScrub>;
 using JitwLocate = JitwEpi<JitLocate>;
 using JitwRepair = JitwEpi<JitRepair>;
+using JitwCorrect = JitwEpi<JitCorrect>;
 
 // The same decode with R rows per wave (rs_jit.h Wide): 2 waves per column
 // tile; R = 16: 168 VGPRs (3 waves per SIMD), chunks of 6 sources (6
@@ -1214,6 +1429,21 @@ __global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40)))
     const long long tile = wg * TPW + tw;
     jitw_run<W, TPW, NV>(s.j, lds, wv, wave, tw, lane, b, wg, tile,
                          JitwRepair{{s.fold, s.tab, s.mode, s.src, s.par, s.pitch, s.j.len}});
+}
+
+// The generated correction for 16 < e <= 64: k_rs_jitw_repair in its
+// kRepairColumns mode with the pair search in its cold path (JitCorrect above)
+template <class W, int TPW, int NV>
+__global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40))) void k_rs_jitw_correct(JitCorrectArgs s)
+{
+    __shared__ uint4 lds[2][TPW][W::CS * 2 * 64];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wv % NV, tw = wv / NV;
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(s.j, b, wg)
+    const long long tile = wg * TPW + tw;
+    jitw_run<W, TPW, NV>(s.j, lds, wv, wave, tw, lane, b, wg, tile,
+                         JitwCorrect{{s.fold, s.tab, s.t, s.src, s.par, s.pitch, s.j.len, tile * 2048}});
 }
 
 // every 8-byte slot a return: a call that lands in code never written
@@ -1603,6 +1833,14 @@ struct RepairFamily {
     static constexpr auto wide = &jitk::k_rs_jitw_repair<W, TPW, NV>;
 };
 
+struct CorrectFamily {
+    using Args = JitCorrectArgs;
+    template <int NW>
+    static constexpr auto jit = &jitk::k_rs_jit_correct<NW>;
+    template <class W, int TPW, int NV>
+    static constexpr auto wide = &jitk::k_rs_jitw_correct<W, TPW, NV>;
+};
+
 template <class F, class W>
 void launch_wide(const typename F::Args& s, int nv, int tpw, dim3 grid, dim3 blk, hipStream_t st)
 {
@@ -1661,6 +1899,31 @@ hipError_t launch_rs_jit_repair(const JitRepairArgs& s, long long blocks, hipStr
     if (!s.tab || !s.src || !s.par || s.pitch < s.j.len || s.mode < kRepairLocate || s.mode > kRepairColumns)
         return hipErrorInvalidValue;
     return launch_scrub_family<RepairFamily>(s, blocks, st);
+}
+
+// The chunk buffers hold the search's tables (jitk::CorLds): always but for
+// the four waves of 16 rows per tile (48 < e <= 64, one tile per workgroup, 24
+// KiB), where masks, syn, PairGf and four waves' CorRow [k] come to 3336 +
+// 256 e + 32 k bytes.  The other layouts fit at every k + e <= 250, which their
+// epilogues assert.
+bool jit_correct_fits(int k, int e, int t)
+{
+    if (t != 2)
+        return true;
+    if (jit::wide_waves(e) == 4 && jitw_rows(e) == 16)
+        return jitk::CorLds<4, 1>::bytes(k, e) <= 2 * jit::J16::CS * 2 * 64 * 16;
+    return true;
+}
+
+// rows as launch_rs_jit_repair's; t == 2 needs the three syndromes the search
+// screens at, a lane per syndrome, and the tables in LDS
+hipError_t launch_rs_jit_correct(const JitCorrectArgs& s, long long blocks, hipStream_t st)
+{
+    if (!s.tab || !s.src || !s.par || s.pitch < s.j.len || s.j.k + s.j.rows > 250 ||
+        !((s.t == 1 && s.j.rows >= 3) || (s.t == 2 && s.j.rows >= 5 && s.j.rows <= 64)) ||
+        !jit_correct_fits(s.j.k, s.j.rows, s.t))
+        return hipErrorInvalidValue;
+    return launch_scrub_family<CorrectFamily>(s, blocks, st);
 }
 
 // a slot per tile: no workgroup's claim can pass the block's area

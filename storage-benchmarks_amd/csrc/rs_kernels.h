@@ -288,6 +288,28 @@ struct JitRepairArgs {
     long long pitch;
 };
 hipError_t launch_rs_jit_repair(const JitRepairArgs& a, long long blocks, hipStream_t st);
+// The generated correction (k_rs_jit_correct, k_rs_jitw_correct;
+// rsgpu_correct_blocks under RSGPU_CORRECT_FUSED with the scrub kernel
+// GENERATED): the generated repair in its kRepairColumns mode on the 32-byte
+// fold (CorrectFold, below), whose cold path, with t == 2, searches the row
+// pairs for every bad column no single row explains (rs_correct.hip's search
+// for a matrix read from memory, rs_pairs.h pair_search_lane).  j, src, par,
+// pitch and tab as JitRepairArgs'; t as CorrectCmpArgs'.  The search keeps its
+// tables in the chunk buffers; jit_correct_fits says whether they fit for
+// (k, e, t) -- t == 1 always, t == 2 everywhere but at 60 <= e <= 64 with
+// 256 e + 32 k > 21240 -- and the launch refuses where they do not.
+struct CorrectFold;
+struct JitCorrectArgs {
+    JitArgs j;
+    CorrectFold* fold;  // [B], zeroed before the launch
+    const uint8_t* tab;
+    int t;
+    uint8_t* src;
+    uint8_t* par;
+    long long pitch;
+};
+bool jit_correct_fits(int k, int e, int t);
+hipError_t launch_rs_jit_correct(const JitCorrectArgs& a, long long blocks, hipStream_t st);
 // small uploads through the kernel arguments (k_put_words): bytes % 8 == 0,
 // at most sizeof(PutArgs::w)
 struct PutArgs {

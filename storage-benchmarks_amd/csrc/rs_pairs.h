@@ -4,8 +4,11 @@
 // codes, whose coefficients are c[p][r] = 2^(p r).  Shared by rs_correct.hip
 // (k_correct_compare: the bookkeeping and the logarithms; its search reads any
 // matrix from memory), rs_bitsliced.hip (k_rs_bs_correct) and the host
-// (rsgpu_testhooks.cpp rsgpu_internal_rs_pair_search).  Nothing here crosses
-// lanes: the ballots over the lanes' results and the write are the kernels'.
+// (rsgpu_testhooks.cpp rsgpu_internal_rs_pair_search); below it the search for
+// a matrix read from memory, shared by rs_jit.hip (k_rs_jit_correct,
+// k_rs_jitw_correct) and the host (rsgpu_internal_pair_search).  Nothing here
+// crosses lanes: the ballots over the lanes' results and the write are the
+// kernels'.
 #pragma once
 #include <stdint.h>
 
@@ -151,6 +154,169 @@ RS_HD inline CorPairs rs_pair_search_lane(const PairGf& g, int k, int e, const u
         }
     }
     return c;
+}
+
+// ---------------------------------------------------------------------------
+// The same search for a matrix read from memory (rs_correct.hip's head): what
+// k_rs_jit_correct / k_rs_jitw_correct (rs_jit.hip) and the host
+// (rsgpu_testhooks.cpp rsgpu_internal_pair_search) run per lane.  The tables
+// come as pointers of the caller's own kind -- LDS pointers in the kernels,
+// plain ones on the host -- so every read is of a scalar member.
+// ---------------------------------------------------------------------------
+
+// Rows 0 to 2 of the matrix as the search keeps them, a byte per data row: the
+// logarithm, 255 for a coefficient 0 (rows 0 and 1 of a locatable matrix have
+// none).
+constexpr unsigned kLog8Zero = 255;
+RS_HD inline uint8_t pair_log8(const GfTables& gf, uint8_t v) { return v ? gf.log[v] : (uint8_t)kLog8Zero; }
+RS_HD inline unsigned pair_log8_wide(unsigned l) { return l == kLog8Zero ? kLogZero : l; }
+
+template <class GP>
+RS_HD inline unsigned pair_logp(GP g, uint8_t v)
+{
+    return v ? g->log[v] : kLogZero;
+}
+
+// Row r of a column whose syndromes 0 to 2 have the logarithms ls0, ls1, ls2
+// (pair_logp), l0 l1 l2 being the row's bytes of the three logarithm rows.
+template <class GP>
+RS_HD inline CorRow pair_row(GP g, unsigned ls0, unsigned ls1, unsigned ls2, unsigned l0, unsigned l1, unsigned l2)
+{
+    CorRow row;
+    row.a0 = (uint16_t)cor_log_mul(ls2, l0);
+    row.a1 = (uint16_t)cor_log_mul(ls2, l1);
+    row.c2 = (uint16_t)pair_log8_wide(l2);
+    // u_r = s_0 c[1][r] ^ s_1 c[0][r]
+    row.u = (uint16_t)pair_logp(g, (uint8_t)(g->ex[ls0 + l1] ^ g->ex[ls1 + l0]));
+    return row;
+}
+
+// What a lane has found, in two registers: cnt = the matching pairs so far (up
+// to 2) | xb << 8, first = ra | rb << 9 | xa << 18 of the first one (rows below
+// 512).
+struct PairHits {
+    unsigned cnt, first;
+};
+
+RS_HD inline void pair_hit(PairHits& h, unsigned ra, unsigned rb, unsigned xa, unsigned xb)
+{
+    const unsigned n = h.cnt & 3u;
+    h.first = n == 0 ? (ra | rb << 9 | xa << 18) : h.first;
+    h.cnt = (n == 0 ? xb << 8 : h.cnt & ~3u) | (n + 1 < 2 ? n + 1 : 2u);
+}
+
+RS_HD inline CorPairs pair_hits(const PairHits& h)
+{
+    CorPairs c{};
+    c.cnt = (int)(h.cnt & 3u);
+    c.ra = (int)(h.first & 511u);
+    c.rb = (int)(h.first >> 9 & 511u);
+    c.xa = (uint8_t)(h.first >> 18);
+    c.xb = (uint8_t)(h.cnt >> 8);
+    return c;
+}
+
+// What lane `lane` of 64 finds of the pairs {a, b} with syn = x h_a + y h_b, x
+// and y non-zero, for the e x k matrix coef of a locatable code, 3 <= e <= 64,
+// k <= 255.  syn[p * stride]: the column's syndrome p; l0, l1, l2 [k]: rows 0
+// to 2 of coef as pair_log8 gives them; row [k]: pair_row of every data row for
+// this column.  Every pair is met by exactly one lane, as in
+// rs_pair_search_lane; survivors of the screen at syndrome 2 are verified
+// coordinate by coordinate against coef.  uni(v): v, which is the same in
+// every lane -- the kernels pass a readfirstlane, so that what is read at one
+// address for all lanes lives in a scalar register.  (The wide generated
+// kernels leave the compiler 40 VGPRs, and the search runs inside their cold
+// path's walk: the loops stay rolled, the lane's matches are two registers,
+// the matrix is read through a 32-bit index.)
+template <class GP, class SP, class LP, class RP, class CP, class UNI>
+RS_HD inline PairHits pair_search_lane(GP g, int k, int e, SP syn, int stride, LP l0, LP l1, LP l2, RP row, CP coef,
+                                       int lane, UNI uni)
+{
+    PairHits h{0, 0};
+    const unsigned s0 = uni(syn[0]), s1 = uni(syn[stride]);
+    const unsigned ls0 = uni(pair_logp(g, (uint8_t)s0)), ls1 = uni(pair_logp(g, (uint8_t)s1));
+
+    if (lane == 0) {  // the column's only non-zero syndromes are s_p and s_q
+        unsigned nz = 0, p = 0, q = 0;
+#pragma unroll 1
+        for (int i = 0; i < e; ++i)
+            if (syn[i * stride]) {
+                p = nz == 0 ? (unsigned)i : p;
+                q = (unsigned)i;
+                ++nz;
+            }
+        if (nz == 2)
+            pair_hit(h, (unsigned)k + p, (unsigned)k + q, syn[p * stride], syn[q * stride]);
+    }
+
+    // a data row and a parity row: syndromes 1 and 2 from the logarithm rows,
+    // the others, for the few rows that get there, from the matrix
+#pragma unroll 1
+    for (int r = lane; r < k; r += 64) {
+        if (s0) {  // parity row k + p, p >= 1: x = s_0 / c[0][r] fails at exactly one q, which is p
+            const unsigned lx = cor_log_mul(ls0, 255u - l0[r]);
+            unsigned miss = 0, p = 0;
+            if (syn[stride] != g->ex[l1[r] + lx]) {
+                ++miss;
+                p = 1;
+            }
+            if (syn[2 * stride] != g->ex[pair_log8_wide(l2[r]) + lx]) {
+                ++miss;
+                p = 2;
+            }
+#pragma unroll 1
+            for (int q = 3; q < e && miss < 2; ++q)
+                if (syn[q * stride] != g->ex[pair_logp(g, coef[(unsigned)(q * k + r)]) + lx]) {
+                    ++miss;
+                    p = (unsigned)q;
+                }
+            if (miss == 1) {
+                const unsigned cp = p == 1 ? l1[r] : p == 2 ? pair_log8_wide(l2[r])
+                                                            : pair_logp(g, coef[(unsigned)((int)p * k + r)]);
+                pair_hit(h, (unsigned)r, (unsigned)k + p, g->ex[lx], (unsigned)(syn[p * stride] ^ g->ex[cp + lx]));
+            }
+        }
+        if (s1) {  // parity row k: x = s_1 / c[1][r] holds at every q >= 2
+            const unsigned lx = cor_log_mul(ls1, 255u - l1[r]);
+            bool ok = syn[2 * stride] == g->ex[pair_log8_wide(l2[r]) + lx];
+#pragma unroll 1
+            for (int q = 3; q < e && ok; ++q)
+                ok = syn[q * stride] == g->ex[pair_logp(g, coef[(unsigned)(q * k + r)]) + lx];
+            const unsigned y = s0 ^ g->ex[l0[r] + lx];
+            if (ok && y)
+                pair_hit(h, (unsigned)r, (unsigned)k, g->ex[lx], y);
+        }
+    }
+
+    // two data rows: a lane per rb in bands of 64, every ra below it
+#pragma unroll 1
+    for (int rb = lane; rb < k; rb += 64) {
+        const unsigned bu = row[rb].u;
+        if (bu == kLogZero)
+            continue;
+#pragma unroll 1
+        for (int ra = 0; ra < rb; ++ra) {
+            const unsigned au = uni(row[ra].u);
+            // coordinate 2: det s_2 ^ c[2][ra] u_rb ^ c[2][rb] u_ra
+            if (au == kLogZero || (g->ex[uni(row[ra].a0) + l1[rb]] ^ g->ex[uni(row[ra].a1) + l0[rb]] ^
+                                   g->ex[uni(row[ra].c2) + bu] ^ g->ex[row[rb].c2 + au]) != 0)
+                continue;
+            const unsigned det = g->ex[uni(l0[ra]) + l1[rb]] ^ g->ex[uni(l1[ra]) + l0[rb]];
+            if (!det)
+                continue;
+            // x = u_rb / det, y = u_ra / det: non-zero, as u_ra and u_rb are
+            const unsigned ld = 255u - g->log[det];
+            const unsigned lx = g->log[g->ex[bu + ld]], ly = g->log[g->ex[au + ld]];
+            bool ok = true;
+#pragma unroll 1
+            for (int p = 3; p < e && ok; ++p)
+                ok = syn[p * stride] == (uint8_t)(g->ex[pair_logp(g, coef[(unsigned)(p * k + ra)]) + lx] ^
+                                                  g->ex[pair_logp(g, coef[(unsigned)(p * k + rb)]) + ly]);
+            if (ok)
+                pair_hit(h, (unsigned)ra, (unsigned)rb, g->ex[lx], g->ex[ly]);
+        }
+    }
+    return h;
 }
 
 }  // namespace rsgpu

@@ -687,10 +687,28 @@ int rsgpu_correct_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch,
     // FUSED (rsgpu_set_correct_kernel), on the rows the fused kernels take: a
     // slice is one launch of the compiled code's kernel, which compares in
     // registers and corrects in its cold path; no scratch, no locate tables
-    const bool fused = work && ctx->correct_kernel == RSGPU_CORRECT_FUSED &&
-                       fused_rows(k, e, len, pitch, d_src, d_parity, coef);
+    const bool want_fused = work && ctx->correct_kernel == RSGPU_CORRECT_FUSED;
+    const bool fused = want_fused && fused_rows(k, e, len, pitch, d_src, d_parity, coef);
+    // Where the compiled form does not apply and the context's scrub kernel is
+    // GENERATED, the generated form: a slice is one k_rs_jit_correct /
+    // k_rs_jitw_correct on the matrix's shared program, row pointers in the
+    // context's scratch as the GENERATED scrub builds them; no encode, and the
+    // parity scratch neither touched nor grown
+    const bool generated = want_fused && !fused && ctx->scrub_kernel == RSGPU_SCRUB_GENERATED &&
+                           jit_correct_fits(k, e, t) && generated_rows(ctx, e, len, pitch, d_src, d_parity);
     // block index in grid.y: larger batches as consecutive slices
     rc = for_grid_slices(work ? blocks : 0, [&](size_t b0, size_t nb) -> int {
+        if (generated) {
+            JitCorrectArgs s{};
+            s.src = d_src + b0 * k * pitch;
+            s.par = d_parity + b0 * e * pitch;
+            const int grc = generated_prepare(ctx, k, e, len, pitch, nb, s.src, s.par, loc.c.data(), &loc, s);
+            s.fold = fold + b0;
+            s.tab = (const uint8_t*)ctx->scrub.p;
+            s.pitch = (long long)pitch;
+            s.t = t;
+            return grc ? grc : generated_launch(ctx, s, nb, "k_rs_jit_correct", launch_rs_jit_correct);
+        }
         if (!fused)
             return two_pass(ctx, k, e, len, pitch, b0, nb, d_src, coef, &loc, compare);
         KTimer kt(ctx, "k_rs_bs_correct", nb);

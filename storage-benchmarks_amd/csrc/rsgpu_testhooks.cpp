@@ -449,4 +449,52 @@ int rsgpu_internal_rs_pair_search(int k, int e, const unsigned char* syn, int* o
     return 1;
 }
 
+// Test hook (not part of include/rsgpu.h): the pair search of k_rs_jit_correct /
+// k_rs_jitw_correct (rs_pairs.h pair_search_lane) on the host, the sibling of
+// the hook above for any e x k matrix `coef` of a locatable code: the tables
+// as the kernel's correct_tables and correct_pending lay them out, every lane
+// of 64 searching, the lanes' results combined as the kernel's ballots combine
+// them.  Returns 0, 1, or 2 for several; with 1, out [4] = row a, row b, x_a,
+// x_b.
+int rsgpu_internal_pair_search(int k, int e, const unsigned char* coef, const unsigned char* syn, int* out)
+{
+    if (k < 1 || k > 255 || e < 3 || e > 64 || !coef || !syn || !out)
+        return RSGPU_ERR_ARG;
+    static const GfTables gf = make_gf_tables();
+    PairGf g;
+    for (int i = 0; i < (int)sizeof g; ++i)
+        reinterpret_cast<uint8_t*>(&g)[i] = pair_gf_byte(gf, i);
+    std::vector<uint8_t> lg(3 * 256);
+    for (int r = 0; r < k; ++r)
+        for (int p = 0; p < 3; ++p)
+            lg[256 * p + r] = pair_log8(gf, coef[(size_t)p * k + r]);
+    const unsigned ls0 = pair_logp(&g, syn[0]), ls1 = pair_logp(&g, syn[1]), ls2 = pair_logp(&g, syn[2]);
+    std::vector<CorRow> row((size_t)k);
+    for (int r = 0; r < k; ++r)
+        row[r] = pair_row(&g, ls0, ls1, ls2, lg[r], lg[256 + r], lg[512 + r]);
+    bool several = false;
+    int holders = 0;
+    CorPairs held{};
+    for (int lane = 0; lane < 64; ++lane) {
+        const CorPairs c = pair_hits(pair_search_lane(
+            (const PairGf*)&g, k, e, (const uint8_t*)syn, 1, (const uint8_t*)lg.data(), (const uint8_t*)lg.data() + 256,
+            (const uint8_t*)lg.data() + 512, (const CorRow*)row.data(), (const uint8_t*)coef, lane,
+            [](unsigned v) { return v; }));
+        several |= c.cnt >= 2;
+        if (c.cnt == 1) {
+            ++holders;
+            held = c;
+        }
+    }
+    if (several || holders > 1)
+        return 2;
+    if (holders == 0)
+        return 0;
+    out[0] = held.ra;
+    out[1] = held.rb;
+    out[2] = held.xa;
+    out[3] = held.xb;
+    return 1;
+}
+
 }  // extern "C"

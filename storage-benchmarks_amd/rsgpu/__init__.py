@@ -512,8 +512,14 @@ class Context:
         encode's program per slice with the stored parity compared in
         registers and the one- and two-row corrections in the cold path,
         where the fused scrub applies (the compiled codes, no coef, 16-byte
-        aligned rows, len % 32 == 0); otherwise two_pass, silently.  Opt-in,
-        auto runs two_pass; set_scrub_kernel has no influence on this call."""
+        aligned rows, len % 32 == 0).  For any other matrix, with or without
+        coef, fused together with set_scrub_kernel("generated") runs the
+        generated form (k_rs_jit_correct): the same epilogue on the matrix's
+        generated encode program, the pair search on the matrix read from
+        memory, for e <= 64, 16-byte aligned rows, len % 32 == 0 and len < 4
+        GiB (t = 2 at e >= 60 while 256 e + 32 k <= 21240).  Otherwise
+        two_pass, silently.  Opt-in, auto runs two_pass; under auto and
+        two_pass set_scrub_kernel has no influence on this call."""
         self.check(lib().rsgpu_set_correct_kernel(self._h, CORRECT_KERNELS[kernel]),
                    "rsgpu_set_correct_kernel")
 
