@@ -135,6 +135,51 @@ int rsgpu_gf_vect_mad(rsgpu_ctx *ctx, int len, int vec, int vec_i, const unsigne
                       unsigned char *src, unsigned char *dest);
 int rsgpu_gf_vect_mul(rsgpu_ctx *ctx, int len, const unsigned char *gftbl, void *src, void *dest);
 
+/* rsgpu_ec_encode_data over `blocks` blocks in one call, each block with its
+ * own rows and its own length: for every block b and byte i < d_len[b]
+ *   d_coding[b * rows + r][i] = XOR_j c[r][j] * d_data[b * k + j][i]
+ * with c the rows x k matrix of the HOST tables `gftbls`, read exactly as
+ * rsgpu_ec_encode_data reads them (one matrix for the whole call: parity rows
+ * to encode, or a decode matrix applied to the rows that survived).
+ *
+ * d_data [blocks][k], d_coding [blocks][rows] (row pointers) and d_len
+ * [blocks] are DEVICE memory, which the caller builds and may keep across
+ * calls; they are only read.  The rows of a block need not be near each other,
+ * and a row may be a source of many blocks; an output row that overlaps any
+ * source or output row of the same call is undefined, as in ISA-L.  d_status
+ * is DEVICE memory of [blocks] ints, or NULL.  max_len is the host's upper
+ * bound of every d_len[b]: it sizes the launches, so nothing is read back from
+ * the device.
+ *
+ * A block gets status -2 when d_len[b] < 0 or d_len[b] > max_len, and under
+ * RSGPU_BATCH_ALIGNED32 also when its length is not a multiple of 32 or one of
+ * its k + rows pointers is not 16-byte aligned; such a block is not touched.
+ * Every other block gets status 0.  A block with d_len[b] == 0 is status 0
+ * whatever its pointers are: none of them is looked at, they may be null.
+ * RSGPU_BATCH_ALIGNED32 is the caller's promise that no block needs the byte
+ * kernel, which is then not launched.
+ *
+ * k <= RSGPU_MAX_SOURCES and rows <= 255 as rsgpu_ec_encode_data; null tables
+ * with rows > 0, max_len < 0 and unknown flags are RSGPU_ERR_ARG.  rows == 0
+ * (only the lengths are judged then, and the pointer tables may be null),
+ * blocks == 0 or max_len == 0 enqueue at most the status fill.  More than
+ * 65535 blocks run as consecutive slices.  The call is enqueued on the
+ * context's stream and does not synchronise, but for the first use of a
+ * matrix, whose program is built then (as under RSGPU_ENCODE_GENERATED; the
+ * context's cache of 64 programs), and for a growth of the context's scratch.
+ * Under RSGPU_ENCODE_THREADED, or without an executable device memory pool,
+ * the byte kernel serves every block whole; the statuses are the same.
+ *
+ * The call writes bytes [0, d_len[b]) of each of the `rows` output rows of
+ * every block of status 0, the first `blocks` ints of d_status when given, and
+ * nothing else: no byte of a source row, of the three tables, or behind a
+ * row's length.  Of a source row it reads bytes [0, d_len[b]) only. */
+#define RSGPU_BATCH_ALIGNED32 1 /* flags: every row 16-byte aligned, every d_len[b] % 32 == 0 */
+int rsgpu_ec_encode_data_batch(rsgpu_ctx *ctx, int k, int rows, const unsigned char *gftbls,
+                               size_t blocks, const unsigned char *const *d_data,
+                               unsigned char *const *d_coding, const int *d_len, int max_len,
+                               int flags, int *d_status);
+
 /* ---- device, batched blocks (the benchmark hot path) --------------------- */
 
 /* isa_encoder::encode_all over `blocks` independent blocks (isa.cpp:69-79):

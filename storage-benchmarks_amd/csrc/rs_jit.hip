@@ -844,6 +844,42 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void 
     jit_run<NW, SH, H>(a, lds, wave, lane, b, tile, JitStore{});
 }
 
+// Block b's own length for the batched entries below (rsgpu_ec_encode_data_batch):
+// lo[b], which k_ec_batch_classify wrote, through the constant address space,
+// a scalar load into an SGPR.
+__device__ __forceinline__ int batch_lo(const int* lo, int b)
+{
+    return ((const int __attribute__((address_space(4)))*)lo)[b];
+}
+// ... and whether the workgroup whose first tile is `tile` has nothing to do:
+// in 32 bits (lo[b] >= 0, and the grid covers less than 2^31 bytes plus a
+// workgroup), so that the compare is a scalar one
+__device__ __forceinline__ bool batch_past(long long tile, int len)
+{
+    return (unsigned)tile * 2048u >= (unsigned)len;
+}
+
+// k_rs_jit<NW, true> over [0, lo[b]) of block b, a length per block: the grid
+// covers the host's bound of every lo[b], and a workgroup whose tile starts at
+// or behind its block's lo[b] leaves before it touches a pointer or LDS (the
+// test is the same for the whole workgroup, in scalar registers).  The others
+// run the body on a copy of the arguments with lo[b] as the length.
+template <int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void k_rs_jit_batch(JitArgs a,
+                                                                                               const int* lo)
+{
+    __shared__ uint4 lds[2][C * 2 * 64];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(a, b, tile)
+    const int len = batch_lo(lo, b);
+    if (batch_past(tile, len))
+        return;
+    JitArgs ab = a;
+    ab.len = len;
+    jit_run<NW, true, JitHooks>(ab, lds, wave, lane, b, tile, JitStore{});
+}
+
 // The generated scrub for e <= 16: k_rs_jit<NW, true>'s accumulation on the
 // matrix's shared program, then the scrub epilogue (scrub_slots)
 template <int NW>
@@ -1249,6 +1285,27 @@ __global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40)))
         return;
     jitw_run<W, TPW, NV>(a, lds, wv, wave, tw, lane, b, wg, tile, JitwStore{});
     RSGPU_DIAG_END();
+}
+
+// k_rs_jitw over [0, lo[b]) of block b, as k_rs_jit_batch: a workgroup whose
+// first tile starts at or behind lo[b] leaves at once; in the others a tile
+// behind lo[b] is idle as a tile behind the row end is in k_rs_jitw.
+template <class W, int TPW, int NV>
+__global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40))) void k_rs_jitw_batch(JitArgs a,
+                                                                                                     const int* lo)
+{
+    __shared__ uint4 lds[2][TPW][W::CS * 2 * 64];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wv % NV, tw = wv / NV;
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(a, b, wg)
+    const int len = batch_lo(lo, b);
+    if (batch_past(wg * TPW, len))
+        return;
+    const long long tile = wg * TPW + tw;
+    JitArgs ab = a;
+    ab.len = len;
+    jitw_run<W, TPW, NV>(ab, lds, wv, wave, tw, lane, b, wg, tile, JitwStore{});
 }
 
 // The (64, 32) encode through the Karatsuba-split program (jit_prog.h
@@ -1803,6 +1860,54 @@ hipError_t launch_rs_jit(const JitArgs& a, long long blocks, hipStream_t st)
     case 8: hipLaunchKernelGGL((jitk::k_rs_jit<4, false>), grid, dim3(256), 0, st, a); break;
     default: hipLaunchKernelGGL((jitk::k_rs_jit<4, true>), grid, dim3(256), 0, st, a); break;
     }
+    return hipGetLastError();
+}
+
+// launch_rs_jit's (shared program) and launch_rs_jitw's choice of kernel and
+// tiles per workgroup, on the entries with a length per block
+hipError_t launch_rs_jit_batch(const JitArgs& a, bool wide, const int* lo, long long max_lo, long long blocks,
+                               hipStream_t st)
+{
+    if (a.rows <= 0 || a.rows > 64 || a.dst_stride < a.rows || a.k <= 0 || !a.code || a.chunk_stride <= 0 ||
+        a.block_stride != 0 || !lo || max_lo <= 0 || max_lo % 32 || max_lo > 0x7fffffffLL || blocks <= 0 ||
+        blocks > (long long)kMaxGridBlocks)
+        return hipErrorInvalidValue;
+    const long long ntile = (max_lo + 2047) / 2048;
+    if (!wide) {  // the 8-row layout
+        if (a.rows > 32)
+            return hipErrorInvalidValue;
+        dim3 grid((unsigned)ntile, (unsigned)blocks);
+        switch ((a.rows + 7) / 8) {
+        case 1: hipLaunchKernelGGL((jitk::k_rs_jit_batch<1>), grid, dim3(64), 0, st, a, lo); break;
+        case 2: hipLaunchKernelGGL((jitk::k_rs_jit_batch<2>), grid, dim3(128), 0, st, a, lo); break;
+        case 3: hipLaunchKernelGGL((jitk::k_rs_jit_batch<3>), grid, dim3(192), 0, st, a, lo); break;
+        default: hipLaunchKernelGGL((jitk::k_rs_jit_batch<4>), grid, dim3(256), 0, st, a, lo); break;
+        }
+        return hipGetLastError();
+    }
+    if (!jitw_rows(a.rows))
+        return hipErrorInvalidValue;
+    const int nv = jit::wide_waves(a.rows);
+    const int tpw = nv == 4 ? 1 : a.tiles_per_wg >= 3 ? 3 : a.tiles_per_wg == 2 ? 2 : 1;
+    dim3 grid((unsigned)((ntile + tpw - 1) / tpw), (unsigned)blocks);
+    dim3 blk(64 * nv * tpw);
+#define RSGPU_JWB_LAUNCH(WT)                                                                            \
+    if (nv == 4)                                                                                        \
+        hipLaunchKernelGGL((jitk::k_rs_jitw_batch<WT, 1, 4>), grid, blk, 0, st, a, lo);                 \
+    else                                                                                                \
+        switch (tpw) {                                                                                  \
+        case 3: hipLaunchKernelGGL((jitk::k_rs_jitw_batch<WT, 3, 2>), grid, blk, 0, st, a, lo); break; \
+        case 2: hipLaunchKernelGGL((jitk::k_rs_jitw_batch<WT, 2, 2>), grid, blk, 0, st, a, lo); break; \
+        default: hipLaunchKernelGGL((jitk::k_rs_jitw_batch<WT, 1, 2>), grid, blk, 0, st, a, lo); break; \
+        }
+    if (jitw_rows(a.rows) == 16) {
+        RSGPU_JWB_LAUNCH(jit::J16)
+    } else if (jitw_rows(a.rows) == 12) {
+        RSGPU_JWB_LAUNCH(jit::J12)
+    } else {
+        RSGPU_JWB_LAUNCH(jit::J10)
+    }
+#undef RSGPU_JWB_LAUNCH
     return hipGetLastError();
 }
 

@@ -240,6 +240,38 @@ hipError_t launch_rs_jitw(const JitArgs& a, long long blocks, hipStream_t st);
 // program, a.k = 64, a.rows = 32, one column tile per workgroup, chunk_rot_ticks
 // and prio as k_rs_jitw.
 hipError_t launch_rs_kara(const JitArgs& a, long long blocks, hipStream_t st);
+// rsgpu_ec_encode_data_batch: blocks of their own rows and lengths, at most
+// kMaxGridBlocks per launch.  k_ec_batch_classify (one wave per block) reads
+// len[b] and, unless it is 0, the block's k + rows pointers, and writes
+//   status[b] (when given)  0, or -2 for a block the call rejects: len[b] < 0
+//              or > max_len, and under `aligned32` a length that is no
+//              multiple of 32 or a pointer that is not 16-byte aligned
+//   lo[b]      where the block's byte range starts: len[b] & ~31 when every
+//              pointer is 16-byte aligned and `fast` is set, else 0
+//   end[b]     len[b], or 0 for a rejected block
+struct BatchClassifyArgs {
+    const uint8_t* const* srcs;  // [B][k]
+    uint8_t* const* dsts;        // [B][rows]
+    const int* len;              // [B]
+    int k, rows, max_len;
+    int aligned32, fast;
+    long long blocks;
+    int* status;                 // [B] or nullptr
+    int* lo;                     // [B]
+    int* end;                    // [B]
+};
+hipError_t launch_ec_batch_classify(const BatchClassifyArgs& a, hipStream_t st);
+// The shared program of launch_rs_jit (rows <= 32, a.block_stride == 0) or,
+// with `wide`, of launch_rs_jitw over [0, lo[b]) of every block b: the grid covers max_lo
+// bytes (% 32 == 0, the host's bound of every lo[b]), and a workgroup whose
+// first tile starts at or behind lo[b] leaves before it touches a pointer or
+// LDS.  a.len and a.status are not used.
+hipError_t launch_rs_jit_batch(const JitArgs& a, bool wide, const int* lo, long long max_lo, long long blocks,
+                               hipStream_t st);
+// k_dot_bytes with one table for every block (DotArgs::tab_block_stride == 0)
+// over bytes [first[b], end[b]) of block b; a.len is the host's bound of every
+// end[b] and sizes the grid.  a.status and a.bytewise are not used.
+hipError_t launch_dot_bytes_batch(const DotArgs& a, const int* first, const int* end, hipStream_t st);
 // The generated scrub (k_rs_jit_scrub, k_rs_jitw_scrub): the shared program's
 // accumulation exactly as the encode runs it, then the stored parity rows read
 // through j.dsts (never written) and compared in registers.  j.rows = e <= 64

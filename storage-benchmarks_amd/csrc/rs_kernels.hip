@@ -216,6 +216,71 @@ __global__ __launch_bounds__(256) void k_dot_bytes(const uint8_t* const* __restr
     }
 }
 
+// k_dot_bytes for rsgpu_ec_encode_data_batch: one table shared by every block,
+// bytes [first[b], end[b]) of block b.  The grid covers the host's bound of
+// every end[b]; a workgroup behind its block's range leaves at once (the two
+// bounds are the same in every lane).
+__global__ __launch_bounds__(256) void k_dot_bytes_batch(const uint8_t* const* __restrict__ srcs,
+                                                         uint8_t* const* __restrict__ dsts,
+                                                         const uint4* __restrict__ tabs4,
+                                                         const uint32_t* __restrict__ ctab, int k, int rows,
+                                                         int rows_pad, const int* __restrict__ first,
+                                                         const int* __restrict__ end)
+{
+    const int b = blockIdx.y;
+    const long long e = end[b];
+    const long long w0 = (long long)first[b] + (long long)blockIdx.x * blockDim.x;
+    if (w0 >= e)
+        return;
+    const long long i = w0 + threadIdx.x;
+    if (i >= e)
+        return;
+    const uint8_t* const* S = srcs + (size_t)b * k;
+    uint8_t* const* Dst = dsts + (size_t)b * rows;
+    for (int r = 0; r < rows; ++r) {
+        uint32_t acc = 0;
+        for (int j = 0; j < k; ++j) {
+            const uint32_t x = S[j][i];
+            const uint4 t = tabs4[(size_t)j * rows_pad + r];
+            const uint32_t c = ctab[(size_t)j * rows_pad + r];
+            acc ^= vperm(t.y, t.x, x & 7u) ^ vperm(t.w, t.z, (x >> 3) & 7u) ^ vperm(c, c, (x >> 6) & 3u);
+        }
+        Dst[r][i] = (uint8_t)acc;
+    }
+}
+
+// The blocks of an rsgpu_ec_encode_data_batch slice, one wave each
+// (rs_kernels.h BatchClassifyArgs): the length judged, the low four bits of
+// the block's k + rows pointers ORed over the wave.  A block of length 0 is
+// accepted without a look at its pointers.
+__global__ __launch_bounds__(256) void k_ec_batch_classify(BatchClassifyArgs a)
+{
+    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= a.blocks)
+        return;  // the whole wave
+    const int lane = threadIdx.x & 63;
+    const int len = a.len[b];
+    bool bad = len < 0 || len > a.max_len;
+    unsigned low = 0;
+    if (!bad && len > 0) {
+        const uint8_t* const* S = a.srcs + (size_t)b * a.k;
+        uint8_t* const* D = a.dsts + (size_t)b * a.rows;
+        for (int i = lane; i < a.k + a.rows; i += 64)
+            low |= (unsigned)(uintptr_t)(i < a.k ? S[i] : D[i - a.k]) & 15u;
+    }
+    for (int o = 32; o > 0; o >>= 1)
+        low |= (unsigned)__shfl_xor((int)low, o, 64);
+    const bool aligned = low == 0;
+    if (a.aligned32)
+        bad = bad || !aligned || (len & 31) != 0;
+    if (lane == 0) {
+        if (a.status)
+            a.status[b] = bad ? -2 : 0;
+        a.lo[b] = !bad && aligned && a.fast ? len & ~31 : 0;
+        a.end[b] = bad ? 0 : len;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Compile-time-coefficient RS (gf_gen_rs_matrix) encode
 // ---------------------------------------------------------------------------
@@ -960,6 +1025,26 @@ hipError_t launch_dot_generic(const DotArgs& a, hipStream_t st)
     case 24: return launch_generic_R<24>(a, st);
     default: return launch_generic_R<32>(a, st);
     }
+}
+
+hipError_t launch_dot_bytes_batch(const DotArgs& a, const int* first, const int* end, hipStream_t st)
+{
+    if (a.k <= 0 || a.rows <= 0 || a.len <= 0 || a.len > 0x7fffffffLL || a.tab_block_stride != 0 || a.blocks <= 0 ||
+        a.blocks > (long long)kMaxGridBlocks || !first || !end)
+        return hipErrorInvalidValue;
+    dim3 grid((unsigned)((a.len + 255) / 256), (unsigned)a.blocks);
+    hipLaunchKernelGGL(k_dot_bytes_batch, grid, dim3(256), 0, st, a.srcs, a.dsts, a.tabs4, a.ctab, a.k, a.rows,
+                       a.rows_pad, first, end);
+    return hipGetLastError();
+}
+
+hipError_t launch_ec_batch_classify(const BatchClassifyArgs& a, hipStream_t st)
+{
+    if (a.k < 0 || a.rows < 0 || a.max_len < 0 || a.blocks <= 0 || a.blocks > (long long)kMaxGridBlocks || !a.len ||
+        !a.lo || !a.end || (a.k + a.rows > 0 && (!a.srcs || !a.dsts)))
+        return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_ec_batch_classify, dim3((unsigned)((a.blocks + 3) / 4)), dim3(256), 0, st, a);
+    return hipGetLastError();
 }
 
 template <int K, int E>

@@ -463,6 +463,54 @@ int encode_slice(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t 
                               aligned, "k_rs_tc(encode)", "k_rs_jit(encode)");
 }
 
+// What the slices of an rsgpu_ec_encode_data_batch call share: the matrix's
+// shared program (null: the byte kernel serves every block whole), the v_perm
+// tables of the byte kernel in the context's scratch (bytes: it is launched)
+// and, behind them, lo [nb] and end [nb] of the slice in flight, which
+// k_ec_batch_classify writes and the two kernels read.
+struct EcBatch {
+    int k, rows, max_len, flags;
+    const rsgpu_ctx::SharedProg* pg;
+    bool bytes;
+    DotArgs dot;
+    int* lo;
+    int* end;
+};
+
+// one slice of at most kMaxGridBlocks blocks: classify, the program over
+// [0, lo[b]) in its passes, the byte kernel over [lo[b], end[b])
+int ec_batch_slice(rsgpu_ctx* ctx, const EcBatch& c, size_t nb, const uint8_t* const* d_data,
+                   uint8_t* const* d_coding, const int* d_len, int* d_status)
+{
+    {
+        const BatchClassifyArgs a{d_data, d_coding, d_len, c.rows ? c.k : 0, c.rows, c.max_len,
+                                  c.flags & RSGPU_BATCH_ALIGNED32, c.pg != nullptr, (long long)nb, d_status, c.lo,
+                                  c.end};
+        KTimer kt(ctx, "classify(ec_batch)", nb);
+        RS_HIP(ctx, launch_ec_batch_classify(a, ctx->stream));
+    }
+    if (c.rows == 0 || c.max_len == 0)
+        return RSGPU_OK;
+    const long long max_lo = c.max_len & ~31;
+    if (c.pg && max_lo > 0) {
+        const bool wide = jitw_layout(c.rows);
+        for (int p = 0; wide ? p < jit::wide_passes(c.rows) : p * 32 < c.rows; ++p) {
+            const JitArgs j = shared_pass_args(ctx, c.pg, c.k, c.rows, p, max_lo, d_data, d_coding);
+            KTimer kt(ctx, "k_rs_jit(ec_batch)", nb);
+            RS_HIP(ctx, launch_rs_jit_batch(j, wide, c.lo, max_lo, (long long)nb, ctx->stream));
+        }
+    }
+    if (c.bytes) {
+        DotArgs a = c.dot;
+        a.srcs = d_data;
+        a.dsts = d_coding;
+        a.blocks = (long long)nb;
+        KTimer kt(ctx, "k_dot_bytes(ec_batch)", nb);
+        RS_HIP(ctx, launch_dot_bytes_batch(a, c.lo, c.end, ctx->stream));
+    }
+    return RSGPU_OK;
+}
+
 }  // namespace
 
 namespace rsgpu {
@@ -990,6 +1038,76 @@ int rsgpu_ec_encode_data(rsgpu_ctx* ctx, int len, int k, int rows, const unsigne
                               (uint8_t* const*)(d + sizeof(void*) * k), ptr_bytes, aligned,
                               "k_rs_tc(ec_encode_data)", "k_rs_jit(ec_encode_data)", hp.data(),
                               sizeof(void*) * hp.size());
+}
+
+int rsgpu_ec_encode_data_batch(rsgpu_ctx* ctx, int k, int rows, const unsigned char* gftbls, size_t blocks,
+                               const unsigned char* const* d_data, unsigned char* const* d_coding,
+                               const int* d_len, int max_len, int flags, int* d_status)
+{
+    if (!ctx || !ec_batch_args_ok(k, rows, gftbls && d_data && d_coding && d_len, max_len, flags))
+        return fail(ctx, RSGPU_ERR_ARG, "rsgpu_ec_encode_data_batch: bad arguments");
+    if (blocks == 0)
+        return RSGPU_OK;
+    if (!d_len) {  // rows == 0 and nothing to judge
+        if (d_status)
+            RS_HIP(ctx, hipMemsetAsync(d_status, 0, sizeof(int) * blocks, ctx->stream));
+        return RSGPU_OK;
+    }
+    const bool work = rows > 0 && max_len > 0;
+    if (!work && !d_status)
+        return RSGPU_OK;
+    EcBatch c{};
+    c.k = k;
+    c.rows = rows;
+    c.max_len = max_len;
+    c.flags = flags;
+    std::vector<uint8_t> coef((size_t)rows * k);
+    if (work) {
+        // coefficient = tbl[1] of each 32-byte table, as rsgpu_ec_encode_data
+        for (size_t i = 0; i < coef.size(); ++i)
+            coef[i] = gftbls[i * 32 + 1];
+        if (ctx->encode_kernel != RSGPU_ENCODE_THREADED && jit_probe(ctx) == 1) {
+            int rc = RSGPU_OK;
+            const std::string err_before = ctx->err;
+            c.pg = shared_program(ctx, coef.data(), k, rows, &rc);
+            if (!c.pg && rc != RSGPU_ERR_UNSUPPORTED)
+                return rc;
+            if (!c.pg)
+                ctx->err = err_before;  // the byte kernel serves: no error is left behind
+        }
+        c.bytes = !c.pg || !(flags & RSGPU_BATCH_ALIGNED32);
+    }
+    const size_t nb_max = std::min(blocks, kMaxGridBlocks);
+    const size_t tab_bytes = c.bytes ? align_up(dot_table_bytes(k, rows), 256) : 0;
+    int rc = ensure_scratch(ctx, tab_bytes + 2 * sizeof(int) * nb_max);
+    if (rc)
+        return rc;
+    char* d = (char*)ctx->scratch.p;
+    c.lo = (int*)(d + tab_bytes);
+    c.end = c.lo + nb_max;
+    if (c.bytes) {
+        const int rows_pad = rows_pad_for(rows);
+        const size_t n = (size_t)k * rows_pad;
+        void* stage;
+        rc = get_stage(ctx, n * (sizeof(uint4) + sizeof(uint32_t)), &stage);
+        if (rc)
+            return rc;
+        fill_tables(coef.data(), k, rows, rows_pad, (uint4*)stage, (uint32_t*)((char*)stage + n * sizeof(uint4)));
+        rc = upload(ctx, d, n * (sizeof(uint4) + sizeof(uint32_t)));
+        if (rc)
+            return rc;
+        c.dot.tabs4 = (const uint4*)d;
+        c.dot.ctab = (const uint32_t*)(d + n * sizeof(uint4));
+        c.dot.tab_block_stride = 0;
+        c.dot.k = k;
+        c.dot.rows = rows;
+        c.dot.rows_pad = rows_pad;
+        c.dot.len = max_len;
+    }
+    return for_grid_slices(blocks, [&](size_t b0, size_t nb) {
+        return ec_batch_slice(ctx, c, nb, d_data ? d_data + b0 * k : nullptr, d_coding ? d_coding + b0 * rows : nullptr,
+                              d_len + b0, d_status ? d_status + b0 : nullptr);
+    });
 }
 
 int rsgpu_ec_encode_data_update(rsgpu_ctx* ctx, int len, int k, int rows, int vec_i,

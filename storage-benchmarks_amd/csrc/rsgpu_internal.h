@@ -49,6 +49,15 @@ uint8_t hmul(uint8_t a, uint8_t b);
 // the argument check every block-batched entry point starts with
 int check_geom(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t blocks);
 
+// rsgpu_ec_encode_data_batch's argument check behind the context (the test
+// hooks run it without a device): tables stands for gftbls, d_data, d_coding
+// and d_len all given
+inline bool ec_batch_args_ok(int k, int rows, bool tables, int max_len, int flags)
+{
+    return k > 0 && k <= RSGPU_MAX_SOURCES && rows >= 0 && rows <= 255 && max_len >= 0 &&
+           (flags & ~RSGPU_BATCH_ALIGNED32) == 0 && (rows == 0 || tables);
+}
+
 // Grow b to >= bytes (a fresh allocation of at least `floor`), its key
 // cleared.  Every kernel that may still read the old buffer was enqueued on
 // the context stream, or on an earlier stream the current one waits on

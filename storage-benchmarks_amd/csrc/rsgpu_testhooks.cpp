@@ -22,6 +22,7 @@
 #include "rs_lane.h"
 #include "rs_pairs.h"
 #include "rsgpu_ctx.h"
+#include "rsgpu_internal.h"
 
 using namespace rsgpu;
 
@@ -406,6 +407,14 @@ int rsgpu_internal_plane_mul_acc(unsigned c, const uint32_t* s, uint32_t* t)
     plane_mul_acc(tv, sv, c);
     std::memcpy(t, tv, sizeof tv);
     return RSGPU_OK;
+}
+
+// Test hook (not part of include/rsgpu.h): what rsgpu_ec_encode_data_batch
+// answers to these arguments with a context at hand, before any device work
+// (rsgpu_internal.h ec_batch_args_ok); `tables`: the four tables are given.
+int rsgpu_internal_ec_batch_args(int k, int rows, int tables, int max_len, int flags)
+{
+    return ec_batch_args_ok(k, rows, tables != 0, max_len, flags) ? RSGPU_OK : RSGPU_ERR_ARG;
 }
 
 // Test hook (not part of include/rsgpu.h): k_rs_bs_correct's pair search

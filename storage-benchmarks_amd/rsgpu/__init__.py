@@ -41,7 +41,7 @@ __all__ = [
     "UPDATE_NONE", "UPDATE_DELTA", "LOST_NONE", "SCRUB_UNCHECKED", "SCRUB_BAD_MATRIX",
     "SCRUB_BAD_LIST", "REBUILD_CHECK", "REBUILD_MAX_LOST", "REBUILD_KERNELS", "SCRUB_ROWS",
     "LOCATE_MAX_ROWS", "LOCATE_KERNELS", "CORRECT_REPORT_DTYPE", "DEGRADED_KERNELS",
-    "REPAIR_KERNELS", "CORRECT_KERNELS",
+    "REPAIR_KERNELS", "CORRECT_KERNELS", "BATCH_ALIGNED32", "row_tables",
 ]
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -101,6 +101,9 @@ DEGRADED_KERNELS = {"auto": 0, "two_pass": 1, "fused": 2}
 REPAIR_KERNELS = {"auto": 0, "generated": 1}
 # rsgpu_set_correct_kernel choices
 CORRECT_KERNELS = {"auto": 0, "two_pass": 1, "fused": 2}
+# rsgpu_ec_encode_data_batch's flag: every row 16-byte aligned, every length a
+# multiple of 32
+BATCH_ALIGNED32 = 1
 
 vp = C.c_void_p
 sz = C.c_size_t
@@ -132,6 +135,7 @@ _SIGS = {
                                        C.POINTER(vp)]),
     "rsgpu_ec_encode_data_update": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp,
                                               C.POINTER(vp)]),
+    "rsgpu_ec_encode_data_batch": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, vp, vp, C.c_int, C.c_int, vp]),
     "rsgpu_gf_vect_dot_prod": (C.c_int, [vp, C.c_int, C.c_int, vp, C.POINTER(vp), vp]),
     "rsgpu_gf_vect_mad": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "rsgpu_gf_vect_mul": (C.c_int, [vp, C.c_int, vp, vp, vp]),
@@ -296,6 +300,38 @@ def erasure_patterns(seed: int, blk0: int, blocks: int, k: int, e: int) -> np.nd
     return out[:blocks, :e]
 
 
+def row_tables(data_rows: Sequence[Sequence], coding_rows: Sequence[Sequence], device):
+    """The device tables of Context.ec_encode_data_batch from per-block lists
+    of torch uint8 tensors or views on `device`: data_rows[b] the k source
+    rows of block b, coding_rows[b] its output rows, each contiguous and all
+    of one block of the same length.  Returns (d_data, d_coding, d_len,
+    max_len): int64 row pointers [blocks, k] and [blocks, rows], int32
+    lengths [blocks], and the largest length.  The caller keeps the rows'
+    tensors alive; the tables hold addresses only."""
+    import torch
+    if len(data_rows) != len(coding_rows):
+        raise ValueError("one list of source rows and one of output rows per block")
+    lens = []
+    for src, out in zip(data_rows, coding_rows):
+        rows = list(src) + list(out)
+        n = {int(t.numel()) for t in rows}
+        if len(n) != 1:
+            raise ValueError("the rows of a block have one length")
+        for t in rows:
+            if t.dtype != torch.uint8 or t.dim() != 1 or not t.is_contiguous() or t.device.type != torch.device(device).type:
+                raise ValueError("rows are contiguous 1-D uint8 tensors on the device")
+        lens.append(n.pop())
+    if len({len(s) for s in data_rows}) > 1 or len({len(o) for o in coding_rows}) > 1:
+        raise ValueError("every block has k source rows and the same number of output rows")
+
+    def table(lists):
+        a = np.array([[t.data_ptr() for t in rows] for rows in lists], np.uint64)
+        return torch.from_numpy(a.view(np.int64).reshape(len(lists), -1)).to(device)
+
+    d_len = torch.tensor(lens, dtype=torch.int32).to(device)
+    return table(data_rows), table(coding_rows), d_len, max(lens, default=0)
+
+
 # ---- device context ---------------------------------------------------------
 
 class Context:
@@ -385,6 +421,19 @@ class Context:
         self.check(lib().rsgpu_ec_encode_data_update(self._h, length, k, rows, vec_i,
                                                      g.ctypes.data, _ptr(data), cp),
                    "rsgpu_ec_encode_data_update")
+
+    def ec_encode_data_batch(self, k: int, rows: int, gftbls: np.ndarray, blocks: int, d_data, d_coding,
+                             d_len, max_len: int, d_status=None, aligned32: bool = False) -> None:
+        """rsgpu_ec_encode_data_batch: ec_encode_data over `blocks` blocks, the
+        rows of block b where the device tables d_data [blocks][k] and
+        d_coding [blocks][rows] (row pointers, int64) say, d_len[b] (int32)
+        bytes long; row_tables() builds the three from lists of tensors.
+        d_status: [blocks] int32 on the device, or None."""
+        g = np.ascontiguousarray(gftbls, np.uint8)
+        self.check(lib().rsgpu_ec_encode_data_batch(self._h, k, rows, g.ctypes.data, blocks, _ptr(d_data),
+                                                    _ptr(d_coding), _ptr(d_len), max_len,
+                                                    BATCH_ALIGNED32 if aligned32 else 0, _ptr(d_status)),
+                   "rsgpu_ec_encode_data_batch")
 
     def gf_vect_dot_prod(self, length: int, vlen: int, gftbls: np.ndarray, src: Sequence, dest) -> None:
         """erasure_code.h gf_vect_dot_prod: dest = XOR_j c[j] * src[j]."""
