@@ -13,7 +13,15 @@
  *   - status returns: RSGPU_OK (0) or a negative RSGPU_ERR_* code; the
  *     context keeps a message for rsgpu_last_error();
  *   - work is enqueued on the context's HIP stream (hipStream_t passed as
- *     void*); nothing synchronises unless the function says so;
+ *     void*); nothing synchronises unless the function says so.  Two waits
+ *     belong to every call: the first use of a matrix (its generated program
+ *     is built then) and a growth of a context-owned buffer may drain the
+ *     stream; and host arguments (coef, gftbls, encode_matrix, pointer arrays)
+ *     are read before the call returns and go through ONE pinned staging
+ *     buffer per context, so a call that stages waits on the host until the
+ *     context's previous staged upload has left that buffer -- at once when
+ *     the stream is idle, and twice within a first use that uploads a program
+ *     and a table (tests/test_gpu_stream_order.py lists the calls seen to);
  *   - one context per device and host thread; distinct contexts are
  *     independent (one process or thread per GPU).
  *
