@@ -50,6 +50,18 @@ extern "C" {
 
 #define RSGPU_MAX_SOURCES 250 /* TEST_SOURCES, isa.cpp:25-27 */
 
+/* The longest row of every block-batched call below (the `size_t len` of
+ * rsgpu_encode_blocks, rsgpu_decode_blocks, rsgpu_decode_prepare / _apply,
+ * rsgpu_decode_general, rsgpu_verify_blocks, the scrub family, rsgpu_update_blocks
+ * and the two host-resident calls): the kernels of 32-byte lanes add a 32-bit
+ * byte offset to a 64-bit row address.  A longer len is refused with RSGPU_ERR_ARG and an
+ * rsgpu_last_error text before anything is enqueued or written; a caller
+ * with longer rows splits them into column ranges (advance d_src, d_parity
+ * and the other row buffers by the range's start, keep the pitch).  pitch,
+ * blocks and the buffers' total size have no such limit: every row address
+ * is computed in 64 bits. */
+#define RSGPU_MAX_LEN 0xFFFFFFFFull
+
 typedef struct rsgpu_ctx rsgpu_ctx;
 
 /* ---- version / context -------------------------------------------------- */
@@ -197,7 +209,8 @@ int rsgpu_ec_encode_data_batch(rsgpu_ctx *ctx, int k, int rows, const unsigned c
  *
  * Under every encode kernel the call writes bytes [0, len) of each parity row
  * and nothing else: bytes in [len, pitch) of any row are never written, nor
- * is any byte of d_src. */
+ * is any byte of d_src.  len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it,
+ * nothing written). */
 int rsgpu_encode_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                         const unsigned char *d_src, unsigned char *d_parity,
                         const unsigned char *coef);
@@ -297,7 +310,8 @@ int rsgpu_set_decode_kernel(rsgpu_ctx *ctx, int kernel);
  * pitch) of any row are never written, nor is any byte of d_src, d_parity or
  * d_err, any byte of d_workspace beyond rsgpu_decode_workspace_bytes(), or any
  * int of d_status beyond `blocks`.  A block with a non-zero status has
- * unspecified bytes only in [0, len) of its own output rows. */
+ * unspecified bytes only in [0, len) of its own output rows.
+ * len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it, nothing written). */
 int rsgpu_decode_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                         const unsigned char *d_src, const unsigned char *d_parity,
                         const unsigned char *d_err, unsigned char *d_out, void *d_workspace,
@@ -319,7 +333,8 @@ int rsgpu_decode_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, 
  * Together the two write what rsgpu_decode_blocks writes, and never what it
  * never writes: the prepare only the first rsgpu_decode_workspace_bytes()
  * bytes of d_workspace and the first `blocks` ints of d_status (no byte of
- * d_out), the apply only bytes [0, len) of the rows of d_out. */
+ * d_out), the apply only bytes [0, len) of the rows of d_out.
+ * len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it, nothing written). */
 int rsgpu_decode_prepare(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                          const unsigned char *d_src, const unsigned char *d_parity,
                          const unsigned char *d_err, unsigned char *d_out, void *d_workspace,
@@ -349,7 +364,8 @@ int rsgpu_decode_apply(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, s
  * never written, nor is any byte of d_src, d_parity or d_err, any byte of
  * d_workspace beyond that size, or any int of d_status beyond `blocks`.  A
  * block with a non-zero status has unspecified bytes only in [0, len) of its
- * own output rows. */
+ * own output rows.
+ * len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it, nothing written). */
 size_t rsgpu_decode_general_workspace_bytes(int k, int m, int nerrs, size_t blocks);
 int rsgpu_decode_general(rsgpu_ctx *ctx, int k, int m, size_t len, size_t pitch, size_t blocks,
                          const unsigned char *encode_matrix, const unsigned char *d_src,
@@ -357,7 +373,8 @@ int rsgpu_decode_general(rsgpu_ctx *ctx, int k, int m, size_t len, size_t pitch,
                          unsigned char *d_out, void *d_workspace, int *d_status);
 
 /* isa_decoder::verify_data (isa.cpp:215-229) on the device: adds to
- * d_mismatch[b] the number of bytes where out[b][i] != src[b][d_err[b][i]]. */
+ * d_mismatch[b] the number of bytes where out[b][i] != src[b][d_err[b][i]].
+ * len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it, nothing written). */
 int rsgpu_verify_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                         const unsigned char *d_src, const unsigned char *d_out,
                         const unsigned char *d_err, unsigned long long *d_mismatch);
@@ -400,7 +417,8 @@ typedef struct rsgpu_scrub_report {
  * Enqueued on the context's stream, no synchronisation.  Any geometry
  * rsgpu_encode_blocks accepts; e == 0 or len == 0 reports every block CLEAN.
  * RSGPU_SCRUB_LOCATE with a matrix that is not locatable (e < 2 included)
- * returns RSGPU_ERR_UNSUPPORTED and enqueues nothing. */
+ * returns RSGPU_ERR_UNSUPPORTED and enqueues nothing.
+ * len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it, nothing written). */
 int rsgpu_scrub_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                        const unsigned char *d_src, const unsigned char *d_parity,
                        const unsigned char *coef, int flags, rsgpu_scrub_report *d_report);
@@ -529,6 +547,7 @@ int rsgpu_set_scrub_kernel(rsgpu_ctx *ctx, int kernel);
 #define RSGPU_SCRUB_UNCHECKED 3     /* n == e: no spare row, nothing can be checked */
 #define RSGPU_SCRUB_BAD_MATRIX (-1) /* the lost data rows are not determined by the surviving parity */
 #define RSGPU_SCRUB_BAD_LIST (-2)   /* malformed list */
+/* len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it, nothing written). */
 int rsgpu_scrub_degraded_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch,
                                 size_t blocks, const unsigned char *d_src,
                                 const unsigned char *d_parity, const unsigned char *coef,
@@ -681,6 +700,7 @@ int rsgpu_set_degraded_kernel(rsgpu_ctx *ctx, int kernel);
  * rsgpu_locate_blocks below, whose lists this call takes as they are.) */
 #define RSGPU_REBUILD_CHECK 1 /* flags: scrub the survivors first, let the verdict decide */
 #define RSGPU_REBUILD_MAX_LOST 32 /* the longest list without RSGPU_REBUILD_CHECK (and at most e) */
+/* len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it, nothing written). */
 int rsgpu_rebuild_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                          unsigned char *d_src, unsigned char *d_parity,
                          const unsigned char *coef, int u, const unsigned char *d_lost,
@@ -786,6 +806,7 @@ int rsgpu_set_rebuild_kernel(rsgpu_ctx *ctx, int kernel);
  * one byte column: rsgpu_correct_blocks, below. */
 #define RSGPU_SCRUB_ROWS 4        /* the damage lies in exactly the 2..u listed rows */
 #define RSGPU_LOCATE_MAX_ROWS 8
+/* len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it, nothing written). */
 int rsgpu_locate_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                         const unsigned char *d_src, const unsigned char *d_parity,
                         const unsigned char *coef, int u, unsigned char *d_rows,
@@ -919,7 +940,8 @@ typedef struct rsgpu_repair_report {
  * error (RSGPU_ERR_HIP, RSGPU_ERR_NOMEM: work may already be enqueued) the
  * report's contents are undefined and must not be read as verdicts; rows are
  * only ever written as described above, so a block is either as it was or
- * corrected. */
+ * corrected.
+ * len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it, nothing written). */
 int rsgpu_repair_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                         unsigned char *d_src, unsigned char *d_parity,
                         const unsigned char *coef, int mode, rsgpu_repair_report *d_report);
@@ -1069,6 +1091,7 @@ typedef struct rsgpu_correct_report {
     int row; /* the one row every corrected column lay in, each a one-row correction; else -1 */
 } rsgpu_correct_report;                   /* 32 bytes */
 
+/* len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it, nothing written). */
 int rsgpu_correct_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                          unsigned char *d_src, unsigned char *d_parity,
                          const unsigned char *coef, int t, rsgpu_correct_report *d_report);
@@ -1210,7 +1233,8 @@ int rsgpu_set_correct_kernel(rsgpu_ctx *ctx, int kernel);
  * update beats "copy the new rows in, then re-encode" up to 8 rows per block
  * (17.1 against 24.9 ms) and loses from 9 rows on (29.5 against 25.3 ms),
  * where the second walk over the parity starts.  For another geometry compare
- * the bytes: 3 n + 2 e ceil(n / 8) rows against k + e + 2 n. */
+ * the bytes: 3 n + 2 e ceil(n / 8) rows against k + e + 2 n.
+ * len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it, nothing written). */
 int rsgpu_update_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                         int u, const unsigned char *d_cols, const unsigned char *d_upd,
                         unsigned char *d_src, unsigned char *d_parity,
@@ -1232,7 +1256,8 @@ int rsgpu_host_free(rsgpu_ctx *ctx, void *hptr);
  * return.  `coef` as rsgpu_encode_blocks.  In host memory the call writes
  * bytes [0, len) of each row of h_parity and nothing else, whatever the
  * pitch: bytes in [len, pitch) of any row are never written, nor is any byte
- * of h_src. */
+ * of h_src.
+ * len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it, nothing written). */
 int rsgpu_encode_blocks_host(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                              const unsigned char *h_src, unsigned char *h_parity,
                              const unsigned char *coef);
@@ -1250,7 +1275,8 @@ int rsgpu_encode_blocks_host(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pi
  * [len, pitch) of any row are never written, nor is any byte of h_src,
  * h_parity or h_err, or any int of h_status beyond `blocks`.  A block with a
  * non-zero status has unspecified bytes only in [0, len) of its own rows of
- * h_out. */
+ * h_out.
+ * len <= RSGPU_MAX_LEN (RSGPU_ERR_ARG beyond it, nothing written). */
 int rsgpu_decode_blocks_host(rsgpu_ctx *ctx, int k, int e, size_t len, size_t pitch, size_t blocks,
                              const unsigned char *h_src, const unsigned char *h_parity,
                              const unsigned char *h_err, unsigned char *h_out, int *h_status);

@@ -564,6 +564,14 @@ int check_geom(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pitch, size_t bl
         return RSGPU_ERR_ARG;
     if (k <= 0 || e < 0 || k + e > RSGPU_MAX_SOURCES || pitch < len || blocks == 0)
         return fail(ctx, RSGPU_ERR_ARG, "bad geometry (k, e, len, pitch, blocks)");
+    // The kernels that work in 32-byte lanes (rs_bitsliced, rs_jit, rs_tc)
+    // load a row's bytes at a 64-bit row base plus a 32-bit offset, the
+    // operand of bs::glds32: in a row of 4 GiB or more they would read the
+    // sources at off mod 2^32.  (The byte and 16-byte column kernels index
+    // in 64 bits; one limit for every path keeps the contract simple.)
+    // Pitch and the block count have no such limit.
+    if (len > RSGPU_MAX_LEN)
+        return fail(ctx, RSGPU_ERR_ARG, "len must be below 4 GiB (at most RSGPU_MAX_LEN)");
     return RSGPU_OK;
 }
 

@@ -138,7 +138,7 @@ int rsgpu_encode_blocks_host(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pi
 {
     if (!ctx)
         return RSGPU_ERR_ARG;
-    if (k <= 0 || e < 0 || k + e > 255 || len > pitch || (blocks && (!h_src || !h_parity)))
+    if (k <= 0 || e < 0 || k + e > 255 || len > pitch || len > RSGPU_MAX_LEN || (blocks && (!h_src || !h_parity)))
         return fail(ctx, RSGPU_ERR_ARG, "rsgpu_encode_blocks_host: bad arguments");
     if (e == 0 || len == 0 || blocks == 0)
         return RSGPU_OK;
@@ -183,7 +183,7 @@ int rsgpu_decode_blocks_host(rsgpu_ctx* ctx, int k, int e, size_t len, size_t pi
 {
     if (!ctx)
         return RSGPU_ERR_ARG;
-    if (k <= 0 || e < 0 || e > k || k + e > 255 || len > pitch ||
+    if (k <= 0 || e < 0 || e > k || k + e > 255 || len > pitch || len > RSGPU_MAX_LEN ||
         (blocks && e && (!h_src || !h_parity || !h_err || !h_out)))
         return fail(ctx, RSGPU_ERR_ARG, "rsgpu_decode_blocks_host: bad arguments");
     if (e == 0 || blocks == 0) {
