@@ -445,11 +445,14 @@ int rsgpu_scrub_locatable(int k, int e, const unsigned char *coef);
  *             `coef`, for 1 <= e <= 64, 16-byte aligned rows (pitch % 16 == 0),
  *             len % 32 == 0 and len < 4 GiB, on a device with an executable
  *             memory pool; no parity scratch, a clean tile writes nothing.
- *             Opt-in: AUTO never takes it.  rsgpu_repair_blocks and
- *             rsgpu_scrub_degraded_blocks do not use it: under GENERATED the
- *             repair runs its TWO_PASS form; its own generated form is
- *             rsgpu_set_repair_kernel's GENERATED (below, at
- *             rsgpu_repair_blocks).  rsgpu_locate_blocks does, under
+ *             Opt-in: AUTO never takes it.  rsgpu_repair_blocks does not use
+ *             it: under GENERATED the repair runs its TWO_PASS form; its own
+ *             generated form is rsgpu_set_repair_kernel's GENERATED (below,
+ *             at rsgpu_repair_blocks).  rsgpu_scrub_degraded_blocks, and the
+ *             check of rsgpu_rebuild_blocks with it, does under
+ *             rsgpu_set_degraded_kernel's FUSED (below) and not otherwise: the
+ *             two settings together select the generated degraded scrub for
+ *             the matrices that are not compiled in.  rsgpu_locate_blocks does, under
  *             rsgpu_set_locate_kernel's FUSED (below): the two settings
  *             together select the generated locate.  rsgpu_correct_blocks
  *             does likewise, under rsgpu_set_correct_kernel's FUSED (below),
@@ -570,9 +573,29 @@ int rsgpu_scrub_degraded_blocks(rsgpu_ctx *ctx, int k, int e, size_t len, size_t
  *             No encode is launched and the parity scratch is neither touched
  *             nor grown; a workgroup whose block the prepare has reported loads
  *             nothing, a lost parity row is never read, a clean tile writes
- *             nothing.  Any other call runs TWO_PASS, silently.  Opt-in: AUTO
- *             does not take it yet.
- * rsgpu_set_scrub_kernel has no influence on these calls.
+ *             nothing.  Where that form does not apply and the context's scrub
+ *             kernel is RSGPU_SCRUB_GENERATED (rsgpu_set_scrub_kernel), the
+ *             generated form, k_rs_jit_degraded, in the same place: the
+ *             generated encode's shared program of the call's matrix (the one
+ *             a GENERATED encode or scrub of it runs, built once per matrix
+ *             and context) with the same reduction for a matrix known at run
+ *             time -- any matrix, with or without `coef`, for e <= 64,
+ *             pitch % 16 == 0, 16-byte aligned d_src and d_parity,
+ *             len % 32 == 0 and len < 4 GiB, on a device with an executable
+ *             memory pool; the compiled form has precedence where both apply.
+ *             The same holds of it: no encode, no parity scratch, a reported
+ *             block's workgroups load nothing, a lost parity row is never
+ *             read, a clean workgroup writes nothing.  Every layout of the
+ *             generated scrub has this form (none falls back for registers).
+ *             Any other call runs TWO_PASS, silently.  Opt-in: AUTO does not
+ *             take either form yet.
+ * Of rsgpu_set_scrub_kernel's choices only GENERATED has an influence on these
+ * calls, and only under FUSED, as above; AUTO and TWO_PASS here ignore it.
+ * The generated form is not measured yet (tools/degraded_measure.py
+ * --generated, profiles/degraded_generated): expected from the generated
+ * locate and repair is the generated scrub's time on clean blocks and, at
+ * small e, a loss to TWO_PASS on damaged ones, whose cold path is small code
+ * and not fast code.
  * Measured at (64, 32), 1 MB rows, 1024 blocks on one MI355X, both choices in
  * mirrored pairs in one process, medians of 24 runs, FUSED / TWO_PASS and the
  * spread of the pairs' ratio (profiles/degraded_fused), clean

@@ -28,6 +28,7 @@
 
 #include "bitslice.h"
 #include "diag_clock.h"
+#include "plane_mul.h"
 #include "rs_jit.h"
 #include "rs_kernels.h"
 #include "rs_lane.h"
@@ -1503,6 +1504,397 @@ __global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40)))
                          JitwCorrect{{s.fold, s.tab, s.t, s.src, s.par, s.pitch, s.j.len, tile * 2048}});
 }
 
+// ---------------------------------------------------------------------------
+// The degraded scrub (rsgpu_scrub_degraded_blocks under FUSED with the scrub
+// kernel GENERATED; k_rs_jit_degraded, k_rs_jitw_degraded): degraded_tile
+// (rs_bitsliced.hip) for a matrix known at run time, on the tables
+// k_degraded_prepare wrote for the block (rs_kernels.h: the pivot parity rows
+// Q, the other surviving parity rows `rest`, R and, with locate, every row's
+// reduced column H).  The wave holds rows [r0, r0 + nrow) of the computed
+// parity in its slots, as in scrub_slots, and what each of them is -- pivot
+// i, rest row pi, or lost -- is a ballot of the row against Q (lane i: Q[i])
+// and against `rest` (lane l: rest[l]), so every test below is wave-uniform.
+//   barrier    other waves may still be reading the last chunk's planes; the
+//              header, the row pointers and the first pivot row's load are
+//              under way before it
+//   pivots     the stored row (one row's load in flight ahead), tr8, the
+//              slot's planes XORed in: the syndrome s_Q[i], written to pivot
+//              slot i of the wave's tile ([2][64] uint4 = 2 KB, at most 8,
+//              behind the masks); a barrier
+//   rest rows  the stored row likewise, then t_p = s_p ^ XOR_i R[p][i] s_Q[i],
+//              the pivot's planes read once per i and multiplied by the
+//              uniform constant on planes (plane_mul.h); the OR over the rest
+//              rows' planes is the lane's mask.  xor_into leaves the slots as
+//              they are, so they hold the computed parity to the end and
+//              nothing is kept across the pivot barrier
+//   lost rows  neither loaded nor counted; their pointers may be loaded
+// A surviving parity row's 32 bytes per lane are so loaded once.  From the
+// masks on, scrub_slots' logic: the masks meet in LDS (their 2 KiB part is no
+// pivot slot's), a clean workgroup ends there and has written nothing, wave 0
+// of a bad tile counts the tile's bad columns.
+// The cold path (a dirty workgroup with locate; small code, not fast code) is
+// the generated scrub's eight passes: the waves lay 4 bytes per lane of the
+// raw syndromes of the surviving parity rows into LDS (syn [e][256] per tile,
+// over the pivot slots, which every wave is past at the mask barrier; zeros
+// for a lost row, which is not loaded), and a tile's threads walk the 256
+// columns on bytes: a column with a non-zero syndrome is reduced in place, by
+// the one thread that owns it, and judged by deg_locate's rule
+// (degraded_column_row below).
+// LDS, in the chunk buffers: masks 2 KiB | per tile 8 pivot slots of 2 KiB,
+// then syn [e][256] in their place.
+// ---------------------------------------------------------------------------
+constexpr int kDegSlotBytes = 2 * 64 * 16, kDegSlots = 8;
+
+struct JitDegraded {
+    ScrubFold* fold;
+    const uint8_t* tab;  // the block's own table
+    int locate;
+    long long tile0 = 0;  // k_rs_jitw_degraded: the first column of the wave's tile (JitwDeg)
+};
+
+// deg_locate's rule (rs_degraded.hip) on the reduced syndromes t(p), p <
+// nrest, of one bad column: the first non-zero entry p*, a screen on one other
+// entry, then t_p h_r[p*] == t_p* h_r[p] for every rest row; a row only when
+// exactly one of the k + e rows passes (H of a lost row is zero).  h: the
+// table's H, [rows][e].  A second copy of what degraded_tile (rs_bitsliced.hip)
+// walks: that one runs on compile-time K and E and its own LDS layout, and
+// sharing the text changes k_rs_bs_degraded's code, which this form leaves as
+// it is.
+template <class T>
+__device__ __forceinline__ int degraded_column_row(int rows, int e, int nrest, const uint8_t* h, T&& t)
+{
+    auto mul = [](uint8_t a, uint8_t b) -> uint8_t { return a && b ? kGfJit.exp[kGfJit.log[a] + kGfJit.log[b]] : 0; };
+    int ps = -1;
+    uint8_t ts = 0, t0 = 0, t2 = 0;
+#pragma unroll 1
+    for (int p = 0; p < nrest; ++p) {
+        const uint8_t v = t(p);
+        if (p == 0)
+            t0 = v;
+        if (ps < 0 && v) {
+            ps = p;
+            ts = v;
+        } else if (ps >= 0 && p == ps + 1) {
+            t2 = v;
+        }
+    }
+    if (ps < 0)
+        return -2;  // not a bad column
+    // the screen: entry 0 (zero) when p* > 0, else entry 1 when there is one
+    const int p2 = ps > 0 ? 0 : nrest > 1 ? 1 : -1;
+    if (ps > 0)
+        t2 = t0;
+    int found = 0, row = -1;
+#pragma unroll 1
+    for (int r = 0; r < rows && found < 2; ++r) {
+        const uint8_t* hr = h + (size_t)r * e;
+        const uint8_t hs = hr[ps];
+        if (!hs)
+            continue;
+        if (p2 >= 0 && mul(t2, hs) != mul(ts, hr[p2]))
+            continue;
+        bool ok = true;
+#pragma unroll 1
+        for (int p = 0; p < nrest && ok; ++p)
+            ok = mul(t(p), hs) == mul(ts, hr[p]);
+        if (ok) {
+            ++found;
+            row = r;
+        }
+    }
+    return found == 1 ? row : -1;
+}
+
+template <class SL, int NV, int TPW>
+__device__ __forceinline__ void degraded_slots(const JitDegraded& s, int k, int e, uint8_t* const* dsts, int b, int r0,
+                                               int nrow, int wave, int tw, bool inb, uint32_t po, uint8_t* ldsb,
+                                               uint32_t m4, uint32_t m2, uint32_t m1)
+{
+    static_assert(4 * NV * TPW * 64 <= kScrubMaskBytes, "the masks fit their part");
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    // the block's table: the header, and R[pi] per rest row below, through the
+    // constant address space (scalar registers); lane l < e rest[l]
+    const uint8_t* tab = s.tab;
+    const uint8_t* t_rest = tab + sizeof(DegradedHdr);
+    const uint8_t* t_r = t_rest + degraded_rest_bytes(e);
+    typedef const uint32_t __attribute__((address_space(4))) * CHdr;
+    const uint32_t hd1 = ((CHdr)tab)[1], hd2 = ((CHdr)tab)[2], hd3 = ((CHdr)tab)[3];
+    const int nq = (int)(hd1 & 0xFFu), nrest = (int)((hd1 >> 8) & 0xFFu);
+    // Q and `rest` ascend and the wave's rows are consecutive, so its pivots
+    // take consecutive slots and its rest rows consecutive indices: two bit
+    // masks (bit i: row r0 + i) and the first of each, in scalar registers
+    unsigned pivm = 0, restm = 0;
+    int slot0 = 0, pi0 = 0;
+    {
+        const int rv = lane < e ? ((const g_cu8*)t_rest)[lane] : 0;
+        const int qv = (int)(((lane & 4 ? hd3 : hd2) >> (8 * (lane & 3))) & 0xFFu);  // lane i < 8: Q[i]
+        const unsigned long long qlanes = (1ull << nq) - 1;  // nq <= 8
+        const unsigned long long rlanes = nrest >= 64 ? ~0ull : (1ull << nrest) - 1;
+#pragma unroll
+        for (int i = SL::N - 1; i >= 0; --i) {
+            const int sq = __ffsll(__ballot(qv == r0 + i) & qlanes), sr = __ffsll(__ballot(rv == r0 + i) & rlanes);
+            if (i < nrow) {
+                pivm |= (sq ? 1u : 0u) << i;
+                restm |= (sr ? 1u : 0u) << i;
+                slot0 = sq ? sq - 1 : slot0;
+                pi0 = sr ? sr - 1 : pi0;
+            }
+        }
+    }
+    // the row's pivot slot / index among the rest rows, as 1 + index, 0: none
+    auto pivot_of = [&](int i) { return (pivm >> i) & 1u ? 1 + slot0 + __builtin_popcount(pivm & ((1u << i) - 1)) : 0; };
+    auto rest_of = [&](int i) { return (restm >> i) & 1u ? 1 + pi0 + __builtin_popcount(restm & ((1u << i) - 1)) : 0; };
+    // the stored rows' pointers: scalar loads under one wait, clamped in bounds
+    typedef const uint8_t* const __attribute__((address_space(4)))* CRows;
+    const uint8_t* dp[SL::N];
+#pragma unroll
+    for (int i = 0; i < SL::N; ++i)
+        dp[i] = ((CRows)dsts)[min(r0 + i, e - 1)];
+    uint4* piv = reinterpret_cast<uint4*>(ldsb + kScrubMaskBytes + tw * (kDegSlots * kDegSlotBytes));
+    uint32_t Pn[8];
+    bs::load32(dp[0], po, pivot_of(0) != 0, Pn);
+    __syncthreads();  // the chunk buffers are free
+    [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
+        (
+            [&] {
+                if (Ss < nrow) {
+                    const int slot = pivot_of(Ss);
+                    uint32_t Pw[8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q)
+                        Pw[q] = Pn[q];
+                    if constexpr (Ss + 1 < SL::N)
+                        if (Ss + 1 < nrow)
+                            bs::load32(dp[Ss + 1], po, pivot_of(Ss + 1) != 0, Pn);
+                    if (slot) {
+                        tr8(Pw, m4, m2, m1);
+                        SL::template xor_into<Ss>(Pw);  // the pivot's syndrome, as planes
+                        piv[((slot - 1) * 2 + 0) * 64 + lane] = make_uint4(Pw[0], Pw[1], Pw[2], Pw[3]);
+                        piv[((slot - 1) * 2 + 1) * 64 + lane] = make_uint4(Pw[4], Pw[5], Pw[6], Pw[7]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }(),
+            ...);
+    }(std::make_integer_sequence<int, SL::N>{});
+    bs::load32(dp[0], po, rest_of(0) != 0, Pn);
+    __syncthreads();  // the pivots' syndromes are in their slots
+    uint32_t mine = 0;
+    [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
+        (
+            [&] {
+                if (Ss < nrow) {
+                    const int pi = rest_of(Ss);
+                    uint32_t Pw[8];
+#pragma unroll
+                    for (int q = 0; q < 8; ++q)
+                        Pw[q] = Pn[q];
+                    if constexpr (Ss + 1 < SL::N)
+                        if (Ss + 1 < nrow)
+                            bs::load32(dp[Ss + 1], po, rest_of(Ss + 1) != 0, Pn);
+                    if (pi) {
+                        // R[pi]: byte i the factor of pivot i, a scalar load under the transpose
+                        const uint32_t f0 = nq ? ((CHdr)t_r)[2 * (pi - 1)] : 0u,
+                                       f1 = nq > 4 ? ((CHdr)t_r)[2 * (pi - 1) + 1] : 0u;
+                        tr8(Pw, m4, m2, m1);
+                        SL::template xor_into<Ss>(Pw);  // the syndrome, as planes
+#pragma unroll 1
+                        for (int i = 0; i < nq; ++i) {
+                            const uint32_t c = ((i & 4 ? f1 : f0) >> (8 * (i & 3))) & 0xFFu;
+                            if (c) {
+                                const uint4 u = piv[(i * 2 + 0) * 64 + lane], v = piv[(i * 2 + 1) * 64 + lane];
+                                const uint32_t sq[8] = {u.x, u.y, u.z, u.w, v.x, v.y, v.z, v.w};
+                                plane_mul_acc(Pw, sq, c);
+                            }
+                        }
+#pragma unroll
+                        for (int q = 0; q < 8; ++q)
+                            mine |= Pw[q];
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }(),
+            ...);
+    }(std::make_integer_sequence<int, SL::N>{});
+    uint32_t* wmask = reinterpret_cast<uint32_t*>(ldsb);
+    wmask[(tw * NV + wave) * 64 + lane] = inb ? mine : 0u;
+    __syncthreads();
+    uint32_t tm = 0, any = 0;  // this lane's columns: of the tile, of the workgroup
+#pragma unroll
+    for (int g = 0; g < NV * TPW; ++g) {
+        const uint32_t m = wmask[g * 64 + lane];
+        any |= m;
+        tm |= g / NV == tw ? m : 0u;
+    }
+    if (__ballot(any != 0) == 0)
+        return;  // the same for every wave of the workgroup
+    ScrubFold* f = s.fold + b;
+    if (wave == 0) {
+        unsigned n = __builtin_popcount(tm);
+        for (int o = 32; o > 0; o >>= 1)
+            n += __shfl_down(n, o, 64);
+        if (lane == 0 && n)
+            atomicAdd(&f->bad, (unsigned long long)n);
+    }
+    if (!s.locate)
+        return;
+    // as scrub_slots' cold path: LDS through its own address space, the stored
+    // dword through an SGPR base and one VGPR offset, every loop rolled
+    typedef __attribute__((address_space(3))) uint8_t lds_u8;
+    typedef __attribute__((address_space(3))) uint32_t lds_u32;
+    lds_u8* syn = (lds_u8*)ldsb + kScrubMaskBytes + tw * e * 256;
+    const uint8_t* t_h = t_r + (size_t)e * 8;
+    const unsigned live = pivm | restm;  // bit i: row r0 + i survives
+    unsigned hi1 = 0, lo1 = 0;
+    auto mul = [](uint8_t x, uint8_t y) -> uint8_t { return x && y ? kGfJit.exp[kGfJit.log[x] + kGfJit.log[y]] : 0; };
+#pragma unroll 1
+    for (int pass = 0; pass < 8; ++pass) {
+        // bytes 4 pass .. 4 pass + 3 of the lane's 32 of every row (zeros from an idle lane)
+        lds_u32* mine4 = (lds_u32*)(syn + r0 * 256 + lane * 4);
+        const uint32_t po4 = po + 4 * pass;
+        const uint32_t p4 = vconst(0x0F0F0F0Fu), p2 = vconst(0x33333333u), p1 = vconst(0x55555555u);
+        [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
+            (
+                [&] {
+                    if (Ss < nrow) {
+                        uint32_t d = 0;
+                        if ((live >> Ss) & 1u) {
+                            uint32_t W[8], st;
+                            // (s_nop 4: as scrub_slots)
+                            asm volatile("s_nop 4\n global_load_dword %0, %1, %2\n s_waitcnt vmcnt(0)"
+                                         : "=v"(st)
+                                         : "v"(po4), "s"(dp[Ss])
+                                         : "memory");
+                            SL::template read<Ss>(W);
+                            tr8(W, p4, p2, p1);  // computed parity, bytes
+                            d = W[0];
+#pragma unroll
+                            for (int q = 1; q < 8; ++q)
+                                d = pass == q ? W[q] : d;
+                            d ^= st;
+                        }
+                        mine4[Ss * 64] = inb ? d : 0u;
+                        __builtin_amdgcn_sched_barrier(0);  // slot by slot
+                    }
+                }(),
+                ...);
+        }(std::make_integer_sequence<int, SL::N>{});
+        __syncthreads();
+#pragma unroll 1
+        for (int c = wave * 64 + lane; c < 256; c += 64 * NV) {
+            unsigned nz = 0;
+#pragma unroll 1
+            for (int p = 0; p < e; ++p)
+                nz |= syn[p * 256 + c];
+            if (!nz)
+                continue;  // no surviving row's syndrome: t is zero
+            // t_p over s_p, in place: the column is this thread's alone
+#pragma unroll 1
+            for (int p = 0; p < nrest; ++p) {
+                lds_u8* at = syn + t_rest[p] * 256 + c;
+                uint8_t t = *at;
+#pragma unroll 1
+                for (int i = 0; i < nq; ++i)
+                    t ^= mul(t_r[p * 8 + i], syn[((i & 4 ? hd3 : hd2) >> (8 * (i & 3)) & 0xFFu) * 256 + c]);
+                *at = t;
+            }
+            const int row = degraded_column_row(k + e, e, nrest, t_h, [&](int p) { return syn[t_rest[p] * 256 + c]; });
+            if (row == -2)
+                continue;  // consistent: the pivots' syndromes explain it
+            hi1 = max(hi1, row >= 0 ? (unsigned)row + 1 : kScrubNoRow);
+            lo1 = max(lo1, row >= 0 ? kScrubBias - (unsigned)row : kScrubNoRow);
+        }
+        __syncthreads();  // the next pass overwrites syn
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        hi1 = max(hi1, (unsigned)__shfl_down((int)hi1, o, 64));
+        lo1 = max(lo1, (unsigned)__shfl_down((int)lo1, o, 64));
+    }
+    if (lane == 0 && hi1) {
+        atomicMax(&f->hi1, hi1);
+        atomicMax(&f->lo1, lo1);
+    }
+}
+
+// the state k_degraded_prepare left in a block's table, in a scalar register
+__device__ __forceinline__ int degraded_state(const uint8_t* tab)
+{
+    return *(const int __attribute__((address_space(4)))*)tab;
+}
+
+// wave w's rows [8 w, 8 w + 8) of k_rs_jit's layout ...
+struct JitDeg8 : JitDegraded {
+    template <int NW>
+    __device__ __forceinline__ void run(const JitArgs& a, uint8_t* const* dsts, int b, int wave, int,
+                                        long long off, uint4* lds, uint32_t m4, uint32_t m2, uint32_t m1) const
+    {
+        static_assert(kScrubMaskBytes + kDegSlots * kDegSlotBytes <= 2 * C * 2 * 64 * 16 &&
+                          kScrubMaskBytes + 32 * 256 <= 2 * C * 2 * 64 * 16,
+                      "masks and pivot slots, then masks and syn (rows <= 32), fit the chunk buffers");
+        const bool inb = off + 32 <= a.len;
+        degraded_slots<Slots8, NW, 1>(static_cast<const JitDegraded&>(*this), a.k, a.rows, dsts, b, wave * 8,
+                                      min(8, a.rows - wave * 8), wave, 0, inb, inb ? (uint32_t)off : 0u,
+                                      reinterpret_cast<uint8_t*>(lds), m4, m2, m1);
+    }
+};
+
+// ... and the wave's rows of k_rs_jitw's (JitwEpi)
+struct JitwDeg : JitDegraded {
+    template <class W, int TPW, int NV>
+    __device__ __forceinline__ void run(const JitArgs& a, uint8_t* const* dsts, int b, int wave, int tw, int,
+                                        long long, uint4* lds) const
+    {
+        static_assert(kScrubMaskBytes + TPW * kDegSlots * kDegSlotBytes <= 2 * TPW * W::CS * 2 * 64 * 16,
+                      "masks and every tile's pivot slots fit the chunk buffers");
+        static_assert(kScrubMaskBytes + TPW * (NV == 4 ? 64 : 32) * 256 <= 2 * TPW * W::CS * 2 * 64 * 16,
+                      "e <= 32 (two waves), e <= 64 (four): syn fits the chunk buffers");
+        const uint32_t m4 = vconst(0x0F0F0F0Fu), m2 = vconst(0x33333333u), m1 = vconst(0x55555555u);
+        const int r0 = jit::wide_row0(a.rows, wave), nrow = jit::wide_row0(a.rows, wave + 1) - r0;
+        // the lane's offset afresh from the tile's first column, a scalar (as
+        // JitwEpi does for the correction): `off` kept live across the main
+        // loop put a VGPR of these kernels into scratch
+        const long long o =
+            this->tile0 + 32 * (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const bool inb = o + 32 <= a.len;
+        degraded_slots<SlotsW<W::R>, NV, TPW>(static_cast<const JitDegraded&>(*this), a.k, a.rows, dsts, b, r0, nrow,
+                                              wave, tw, inb, inb ? (uint32_t)o : 0u,
+                                              reinterpret_cast<uint8_t*>(lds), m4, m2, m1);
+    }
+};
+
+// The generated degraded scrub for e <= 16: k_rs_jit<NW, true>'s accumulation
+// on the matrix's shared program, then degraded_slots.  A workgroup whose
+// block the prepare has already reported (state != kDegRun) leaves before it
+// touches a row pointer or LDS; the test is uniform per workgroup.
+template <int NW>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_num_vgpr(64))) void k_rs_jit_degraded(JitDegradedArgs s)
+{
+    __shared__ uint4 lds[2][C * 2 * 64];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(s.j, b, tile)
+    const uint8_t* tab = s.tab + (size_t)b * s.tab_stride;
+    if (degraded_state(tab) != kDegRun)
+        return;
+    jit_run<NW, true, JitHooks>(s.j, lds, wave, lane, b, tile, JitDeg8{{s.fold, tab, s.locate}});
+}
+
+// ... and for 16 < e <= 64, on k_rs_jitw's
+template <class W, int TPW, int NV>
+__global__ __launch_bounds__(64 * NV * TPW) __attribute__((amdgpu_num_vgpr(40))) void k_rs_jitw_degraded(JitDegradedArgs s)
+{
+    __shared__ uint4 lds[2][TPW][W::CS * 2 * 64];
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int wave = wv % NV, tw = wv / NV;
+    const int lane = threadIdx.x & 63;
+    RSGPU_JIT_PLACE(s.j, b, wg)
+    const uint8_t* tab = s.tab + (size_t)b * s.tab_stride;
+    if (degraded_state(tab) != kDegRun)
+        return;
+    const long long tile = wg * TPW + tw;
+    jitw_run<W, TPW, NV>(s.j, lds, wv, wave, tw, lane, b, wg, tile, JitwDeg{{s.fold, tab, s.locate, tile * 2048}});
+}
+
 // every 8-byte slot a return: a call that lands in code never written
 // comes straight back
 __global__ void k_jit_fill(uint64_t* code, long long n)
@@ -1946,6 +2338,14 @@ struct CorrectFamily {
     static constexpr auto wide = &jitk::k_rs_jitw_correct<W, TPW, NV>;
 };
 
+struct DegradedFamily {
+    using Args = JitDegradedArgs;
+    template <int NW>
+    static constexpr auto jit = &jitk::k_rs_jit_degraded<NW>;
+    template <class W, int TPW, int NV>
+    static constexpr auto wide = &jitk::k_rs_jitw_degraded<W, TPW, NV>;
+};
+
 template <class F, class W>
 void launch_wide(const typename F::Args& s, int nv, int tpw, dim3 grid, dim3 blk, hipStream_t st)
 {
@@ -2029,6 +2429,14 @@ hipError_t launch_rs_jit_correct(const JitCorrectArgs& s, long long blocks, hipS
         !jit_correct_fits(s.j.k, s.j.rows, s.t))
         return hipErrorInvalidValue;
     return launch_scrub_family<CorrectFamily>(s, blocks, st);
+}
+
+// the blocks' tables as k_degraded_prepare wrote them, 16-byte aligned
+hipError_t launch_rs_jit_degraded(const JitDegradedArgs& s, long long blocks, hipStream_t st)
+{
+    if (!s.tab || (uintptr_t)s.tab % 16 || s.tab_stride % 16 || s.tab_stride < degraded_tab_stride(s.j.k, s.j.rows))
+        return hipErrorInvalidValue;
+    return launch_scrub_family<DegradedFamily>(s, blocks, st);
 }
 
 // a slot per tile: no workgroup's claim can pass the block's area

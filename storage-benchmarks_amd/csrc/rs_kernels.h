@@ -515,6 +515,23 @@ hipError_t launch_rs_bitsliced_degraded(int k, int e, const uint8_t* src, const 
                                         long long len, long long blocks, const uint8_t* tab, ScrubFold* fold,
                                         int locate, hipStream_t st);
 
+// The degraded scrub fused into the matrix's generated encode (rs_jit.hip
+// k_rs_jit_degraded, k_rs_jitw_degraded; FUSED with the scrub kernel
+// GENERATED), in the same place: the shared program's accumulation exactly as
+// the GENERATED encode and scrub run it, then the syndromes reduced with the
+// block's table and compared in registers, for any matrix.  j as
+// JitScrubArgs::j (j.rows = e <= 64); tab and fold as
+// launch_rs_bitsliced_degraded's, tab_stride >= degraded_tab_stride(k, e) and a
+// multiple of 16.  A lost parity row is never read.
+struct JitDegradedArgs {
+    JitArgs j;
+    const uint8_t* tab;
+    size_t tab_stride;
+    ScrubFold* fold;  // [B]
+    int locate;
+};
+hipError_t launch_rs_jit_degraded(const JitDegradedArgs& a, long long blocks, hipStream_t st);
+
 // Rebuild in place (rsgpu_rebuild_blocks, rs_rebuild.hip): the listed rows of
 // a block, and with `check` the one row its degraded report names, written
 // back as fixed linear combinations of k surviving rows: the surviving data

@@ -92,10 +92,12 @@ struct rsgpu_ctx {
     void* d_update = nullptr;
     std::vector<uint8_t> update_key;
     // degraded scrub (rsgpu_scrub_degraded_blocks): the per-block tables
-    // k_degraded_prepare writes for one slice, and its kernel choice
-    // (rsgpu_set_degraded_kernel)
+    // k_degraded_prepare writes for one slice, its kernel choice
+    // (rsgpu_set_degraded_kernel), and the test hook that caps a group's
+    // blocks (0: the 64 MiB rule)
     DevBuf degraded;
     int degraded_kernel = RSGPU_DEGRADED_AUTO;
+    size_t degraded_group_max = 0;
     // correction per column (rsgpu_correct_blocks): its kernel choice
     // (rsgpu_set_correct_kernel)
     int correct_kernel = RSGPU_CORRECT_AUTO;

@@ -789,17 +789,35 @@ int rsgpu_scrub_degraded_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t
     // a slice is what the scrub scratch holds of computed parity (the TWO_PASS
     // rule): encode, then compare.  FUSED (rsgpu_set_degraded_kernel) on the
     // rows the fused scrub takes: one k_rs_bs_degraded launch over the group
-    // in their place, no encode and no parity scratch.
+    // in their place, no encode and no parity scratch.  Where the compiled
+    // form does not apply and the context's scrub kernel is GENERATED, the
+    // generated form: per group one k_rs_jit_degraded / k_rs_jitw_degraded on
+    // the matrix's shared program, row pointers in the context's scratch as
+    // the GENERATED scrub builds them, for any matrix; no encode, and the
+    // parity scratch neither touched nor grown.
     const size_t per_block = (size_t)e * pitch, stride = degraded_tab_stride(k, e);
-    const size_t group = std::max<size_t>(1, std::min({blocks, kMaxGridBlocks, kDegTabBytes / stride}));
+    size_t group = std::max<size_t>(1, std::min({blocks, kMaxGridBlocks, kDegTabBytes / stride}));
+    if (ctx->degraded_group_max)
+        group = std::min(group, ctx->degraded_group_max);
     rc = ensure_device(ctx, ctx->degraded, group * stride);
     if (rc)
         return rc;
-    const bool fused = work && ctx->degraded_kernel == RSGPU_DEGRADED_FUSED &&
-                       fused_rows(k, e, len, pitch, d_src, d_parity, coef);
+    const bool want_fused = work && ctx->degraded_kernel == RSGPU_DEGRADED_FUSED;
+    const bool compiled = want_fused && fused_rows(k, e, len, pitch, d_src, d_parity, coef);
+    const bool generated = want_fused && !compiled && ctx->scrub_kernel == RSGPU_SCRUB_GENERATED &&
+                           generated_rows(ctx, e, len, pitch, d_src, d_parity);
+    const bool fused = compiled || generated;
+    const std::vector<uint8_t> matrix = generated ? parity_matrix(k, e, coef) : std::vector<uint8_t>();
     if (work) {
         // the scratch of the largest group now, so that no walk below grows it
         rc = fused ? RSGPU_OK : grow_parity_scratch(ctx, group, per_block);
+        // generated: the row pointers of the largest group, [group][k] then
+        // [group][e], before any group's prepare is enqueued (a growth waits
+        // for the stream and frees the old buffer).  H comes from the block's
+        // table, so the scrub's table buffer (ctx->scrub) is not needed.
+        if (!rc && generated)
+            rc = ensure_scratch(ctx, align_up(sizeof(void*) * (size_t)k * group, 256) +
+                                         align_up(sizeof(void*) * (size_t)e * group, 256));
         if (rc)
             return rc;
         // the v_perm tables of every coefficient value and the matrix, on the device
@@ -827,6 +845,21 @@ int rsgpu_scrub_degraded_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t
         a.report = d_report + g0;
         if (work)
             set_tables(a, ctx);
+        // generated: the group's row pointers and the matrix's program (built
+        // on first use) before the prepare is enqueued; the launch follows it
+        JitDegradedArgs js{};
+        if (generated) {
+            RowPtrs rp;
+            rc = row_ptr_tables(ctx, k, e, pitch, ng, d_src + g0 * (size_t)k * pitch, d_parity + g0 * per_block, rp);
+            if (!rc)
+                rc = shared_epilogue_args(ctx, matrix.data(), k, e, (long long)len, rp, js.j);
+            if (rc)
+                return rc;
+            js.tab = a.tab;
+            js.tab_stride = stride;
+            js.fold = reinterpret_cast<ScrubFold*>(d_report + g0);
+            js.locate = a.locate;
+        }
         {
             KTimer kt(ctx, "k_degraded_prepare", ng);
             RS_HIP(ctx, launch_degraded_prepare(a, ctx->stream));
@@ -847,7 +880,11 @@ int rsgpu_scrub_degraded_blocks(rsgpu_ctx* ctx, int k, int e, size_t len, size_t
             };
             return launch_head_and_tail(ctx, kDegradedNames, nb, n16, (long long)len, launch);
         };
-        if (fused) {
+        if (generated) {
+            rc = generated_launch(ctx, js, ng, "k_rs_jit_degraded", launch_rs_jit_degraded);
+            if (rc)
+                return rc;
+        } else if (compiled) {
             KTimer kt(ctx, "k_rs_bs_degraded", ng);
             RS_HIP(ctx, launch_rs_bitsliced_degraded(k, e, d_src + g0 * (size_t)k * pitch, d_parity + g0 * per_block,
                                                      (long long)pitch, (long long)len, (long long)ng, a.tab,

@@ -156,6 +156,17 @@ int rsgpu_internal_set_locate_group(rsgpu_ctx* ctx, long long blocks)
     return RSGPU_OK;
 }
 
+// Test hook (not part of include/rsgpu.h): caps the blocks of a group of
+// rsgpu_scrub_degraded_blocks (0: the 64 MiB rule), so that a small call runs
+// as several groups.
+int rsgpu_internal_set_degraded_group(rsgpu_ctx* ctx, long long blocks)
+{
+    if (!ctx || blocks < 0)
+        return RSGPU_ERR_ARG;
+    ctx->degraded_group_max = (size_t)blocks;
+    return RSGPU_OK;
+}
+
 // Test hook (not part of include/rsgpu.h): the bytes of the scrub family's
 // device buffer [tables | parity scratch of the two-pass forms] as the context
 // holds it now, 0 before the first call that needed it -- for the tests of the

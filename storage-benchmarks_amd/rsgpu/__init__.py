@@ -548,9 +548,15 @@ class Context:
         same reports.  fused: between the prepare and the finalise one launch
         of the compiled encode's program with the stored parity read and the
         syndromes reduced in registers, where the fused scrub applies (the
-        compiled codes, no coef, 16-byte aligned rows, len % 32 == 0);
-        otherwise two_pass, silently.  Opt-in, auto runs two_pass;
-        set_scrub_kernel has no influence on these calls."""
+        compiled codes, no coef, 16-byte aligned rows, len % 32 == 0).  For
+        any other matrix, with or without coef, fused together with
+        set_scrub_kernel("generated") runs the generated form
+        (k_rs_jit_degraded): the same reduction behind the matrix's generated
+        encode program, for e <= 64, 16-byte aligned rows, a pitch that is a
+        multiple of 16, len % 32 == 0 and len < 4 GiB.  Otherwise two_pass,
+        silently.  Opt-in, auto runs two_pass.  Of set_scrub_kernel's choices
+        only generated has an influence on these calls, and only under
+        fused."""
         self.check(lib().rsgpu_set_degraded_kernel(self._h, DEGRADED_KERNELS[kernel]),
                    "rsgpu_set_degraded_kernel")
 

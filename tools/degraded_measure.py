@@ -33,6 +33,15 @@ rebuild at n = 1, 4, 7 with clean survivors -- after one untimed run of each
 whose reports must be equal byte for byte under both choices.  Per case:
 the medians, and min / median / max of the ratio FUSED / TWO_PASS over the
 pairs of a round's two halves.
+
+--generated --matrix rs | cauchy is the same measurement of the generated form
+(profiles/degraded_generated/README.md): the matrix is passed as `coef`
+(gf_gen_rs_matrix, so that a compiled code does not take the compiled form, or
+gf_gen_cauchy1_matrix), the first side runs under FUSED with the scrub kernel
+GENERATED (k_rs_jit_degraded), and the yardstick beside the all-NONE case is
+the GENERATED rsgpu_scrub_blocks with LOCATE.  The summary also holds the
+ratio all-NONE / yardstick over the mirrored pairs beside the yardstick's own
+first-half / second-half spread, measured in the same run.
 """
 import numpy as np
 import torch
@@ -40,9 +49,13 @@ import torch
 import measure_lib as ml  # puts the engine's directory on the path
 
 
-def both(a, ctx, enc):
-    """--kernel both: FUSED against TWO_PASS, case by case."""
+def both(a, ctx, enc, coef=None):
+    """--kernel both: FUSED against TWO_PASS, case by case; with `coef`
+    (--generated): FUSED under the scrub kernel GENERATED against TWO_PASS."""
     k, e, L, B = a.k, a.e, a.len, a.blocks
+    gen = coef is not None
+    yard = "scrub_generated" if gen else "scrub_fused"  # the scrub of the complete blocks
+    form = "k_rs_jit_degraded" if gen else "k_rs_bs_degraded"
     dev, pitch = enc.src.device, enc.pitch
     rep = ml.reports(enc)
     rng = np.random.default_rng(9)
@@ -55,12 +68,14 @@ def both(a, ctx, enc):
         "none": none,
         "data1": (np.arange(B) % k).astype(np.uint8).reshape(B, 1),
         "parity1": (k + np.arange(B) % e).astype(np.uint8).reshape(B, 1),
-        "rows4": np.stack([pad(rng.choice(k + e, 4, replace=False), 4) for _ in range(B)]),
-        "data8": np.stack([pad(rng.choice(k, 8, replace=False), 8) for _ in range(B)]),
-        "mixed": np.stack([pad(rng.choice(k + e, b % 9, replace=False), 8) for b in range(B)]),
+        # (a small code: no more rows than it has parity rows, or data rows)
+        "rows4": np.stack([pad(rng.choice(k + e, min(4, e), replace=False), 4) for _ in range(B)]),
+        "data8": np.stack([pad(rng.choice(k, min(8, e, k), replace=False), 8) for _ in range(B)]),
+        "mixed": np.stack([pad(rng.choice(k + e, b % (min(8, e) + 1), replace=False), 8) for b in range(B)]),
     }
     for n in (1, 4, 7):
-        lists[f"rebuild{n}"] = np.stack([pad(rng.choice(k + e, n, replace=False), n) for _ in range(B)])
+        lists[f"rebuild{n}"] = np.stack([pad(rng.choice(k + e, min(n, max(1, e - 1)), replace=False), n)
+                                         for _ in range(B)])
     lists["bad1pct"] = lists["data1"]
     d_lists = {n: torch.from_numpy(v).to(dev) for n, v in lists.items()}
     cases = list(lists)
@@ -74,13 +89,15 @@ def both(a, ctx, enc):
 
     def run(kind):
         case, kernel = kind.rsplit("/", 1)
-        if case == "scrub_fused":
-            ctx.set_scrub_kernel("fused")
+        if case == yard:
+            ctx.set_scrub_kernel("generated" if gen else "fused")
             try:
-                return ml.timed(ctx, lambda: ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, rep))
+                return ml.timed(ctx, lambda: ctx.scrub_blocks(k, e, L, pitch, B, enc.src, enc.par, rep, coef=coef))
             finally:
                 ctx.set_scrub_kernel("auto")
         ctx.set_degraded_kernel(kernel)
+        if gen and kernel == "fused":
+            ctx.set_scrub_kernel("generated")
         lst = d_lists[case]
         u = lst.shape[1]
         if case == "bad1pct":
@@ -88,14 +105,16 @@ def both(a, ctx, enc):
         try:
             if case.startswith("rebuild"):
                 return ml.timed(ctx, lambda: ctx.rebuild_blocks(k, e, L, pitch, B, enc.src, enc.par, u, lst, rep,
-                                                                check=True))
-            return ml.timed(ctx, lambda: ctx.scrub_degraded_blocks(k, e, L, pitch, B, enc.src, enc.par, u, lst, rep))
+                                                                coef=coef, check=True))
+            return ml.timed(ctx, lambda: ctx.scrub_degraded_blocks(k, e, L, pitch, B, enc.src, enc.par, u, lst, rep,
+                                                                   coef=coef))
         finally:
             ctx.set_degraded_kernel("auto")
+            ctx.set_scrub_kernel("auto")
             if case == "bad1pct":
                 flip()
 
-    kinds = [f"{c}/{kern}" for c in cases for kern in ("fused", "two_pass")] + ["scrub_fused/-"]
+    kinds = [f"{c}/{kern}" for c in cases for kern in ("fused", "two_pass")] + [f"{yard}/-"]
     kernels_seen, statuses = {}, {}
     for c in cases:  # untimed and checked: the same reports under both choices
         got = {}
@@ -105,12 +124,12 @@ def both(a, ctx, enc):
             kernels_seen[f"{c}/{kern}"] = sorted(by)
             got[kern] = rep.cpu().numpy().tobytes()
         assert got["fused"] == got["two_pass"], c
-        assert "k_rs_bs_degraded" in kernels_seen[f"{c}/fused"], kernels_seen
+        assert form in kernels_seen[f"{c}/fused"], kernels_seen
         r = np.frombuffer(got["fused"], ml.rsgpu.SCRUB_REPORT_DTYPE)
         statuses[c] = {int(v): int((r["status"] == v).sum()) for v in np.unique(r["status"])}
         if c != "bad1pct":
             assert (r["bad_columns"] == 0).all(), c
-    run("scrub_fused/-")
+    run(f"{yard}/-")
     out = {**ml.header(enc), "kernels": kernels_seen, "statuses": statuses,
            "runs": ml.mirrored_rounds(kinds, a.rounds, run)}
     summ = ml.summarise(out["runs"], kinds, kernel_medians=True)
@@ -123,18 +142,33 @@ def both(a, ctx, enc):
                 ratios.append(ms[f"{c}/fused"] / ms[f"{c}/two_pass"])
         summ[f"{c}/fused"]["pair_ratio_to_two_pass"] = {"min": float(min(ratios)), "median": float(np.median(ratios)),
                                                         "max": float(max(ratios))}
+    # all-NONE against the scrub of the complete blocks, and the yardstick's own spread
+    ratios, own = [], []
+    for rnd in range(a.rounds):
+        mine = [r for r in out["runs"] if r["round"] == rnd]
+        first, second = ({r["kind"]: r["ms"] for r in h} for h in (mine[:len(kinds)], mine[len(kinds):]))
+        ratios += [first["none/fused"] / first[f"{yard}/-"], second["none/fused"] / second[f"{yard}/-"]]
+        own.append(first[f"{yard}/-"] / second[f"{yard}/-"])
+    summ["none/fused"]["pair_ratio_to_scrub"] = {**ml.stats(ratios), "mean": float(np.mean(ratios))}
+    summ[f"{yard}/-"]["first_over_second_half"] = {**ml.stats(own), "mean": float(np.mean(own))}
     ml.finish(a.out, out, summ)
 
 
 def main():
     ap = ml.shape_parser()
     ap.add_argument("--kernel", choices=("auto", "two_pass", "fused", "both"), default="auto")
+    ap.add_argument("--generated", action="store_true", help="the generated form against TWO_PASS, as --kernel both")
+    ap.add_argument("--matrix", choices=["rs", "cauchy"], default="rs", help="with --generated: the matrix, as coef")
     a = ap.parse_args()
     k, e, L, B = a.k, a.e, a.len, a.blocks
 
-    ctx, enc = ml.setup(a)
-    if a.kernel == "both":
-        both(a, ctx, enc)
+    coef = None
+    if a.generated:
+        gen = ml.rsgpu.gf_gen_rs_matrix if a.matrix == "rs" else ml.rsgpu.gf_gen_cauchy1_matrix
+        coef = gen(k + e, k)[k:]
+    ctx, enc = ml.setup(a, coef)
+    if a.kernel == "both" or a.generated:
+        both(a, ctx, enc, coef)
         ctx.close()
         return
     ctx.set_degraded_kernel(a.kernel)

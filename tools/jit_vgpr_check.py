@@ -26,7 +26,7 @@ import kernel_isa_diff as kid  # noqa: E402
 
 # the templates' symbols go on with I<arguments>, k_rs_kara's (no template)
 # with E<parameter types>
-KERNEL = re.compile(r"^(_ZN5rsgpu4jitk\d+k_rs_(?:jit(w?)(?:_scrub|_locate|_repair|_correct|_batch)?I|karaE)\S*):")
+KERNEL = re.compile(r"^(_ZN5rsgpu4jitk\d+k_rs_(?:jit(w?)(?:_scrub|_locate|_repair|_correct|_degraded|_batch)?I|karaE)\S*):")
 FAMILIES = ("k_rs_jitI", "k_rs_jitwI", "k_rs_karaE")  # each must be seen at least once
 WIDE_R = re.compile(r"WideILi(\d+)E")
 
