@@ -428,6 +428,16 @@ int rsgpu_internal_ec_batch_args(int k, int rows, int tables, int max_len, int f
     return ec_batch_args_ok(k, rows, tables != 0, max_len, flags) ? RSGPU_OK : RSGPU_ERR_ARG;
 }
 
+// Test hook (not part of include/rsgpu.h): whether the search's tables of
+// rsgpu_correct_blocks' generated form fit the chunk buffers at (k, e, t)
+// (rs_jit.hip jit_correct_fits), 1 or 0; -1 for arguments the call refuses.
+int rsgpu_internal_jit_correct_fits(int k, int e, int t)
+{
+    if (k < 1 || e < 1 || e > 64 || k + e > 250 || t < 1 || t > 2)
+        return RSGPU_ERR_ARG;
+    return jit_correct_fits(k, e, t) ? 1 : 0;
+}
+
 // Test hook (not part of include/rsgpu.h): k_rs_bs_correct's pair search
 // (rs_pairs.h rs_pair_search_lane) on the host, for the CPU suite to compare
 // with the model's brute force: the gf_gen_rs_matrix code (k, e), the syndrome

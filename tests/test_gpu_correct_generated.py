@@ -12,7 +12,10 @@ none of the names a plain encode of the same arguments records.
 A tile is 2048 bytes, a lane's share 32: len 32 is one lane, 2112 a full tile
 and two lanes, L0 = 6304 three full tiles and five lanes (a workgroup of three
 tiles and one whose last two tiles lie past the row end); with plus48 the
-bytes in [len, pitch) hold sentinels."""
+bytes in [len, pitch) hold sentinels.
+
+More than 64 source rows on the two- and four-wave layouts (here only on the
+one-wave one): tests/test_gpu_family_generated_wide.py."""
 import ctypes as C
 
 import numpy as np

@@ -11,7 +11,9 @@ give the same report bytes.
 
 A tile is 2048 bytes, a lane's share 32: L0 = 3 * 2048 + 5 * 32 gives three
 full tiles and one whose last 59 lanes are idle; with two or three tiles per
-workgroup the last workgroup also owns tiles past the row end."""
+workgroup the last workgroup also owns tiles past the row end.
+
+More than 64 source rows: tests/test_gpu_family_generated_wide.py."""
 import ctypes as C
 
 import numpy as np

@@ -6,7 +6,8 @@ model of the contract (tests/repair_model.py, run on the damaged rows read back
 from the device) and reports, the whole source allocation and the whole parity
 allocation (gap and guard bytes included), byte for byte, against what the same
 call writes under the two-pass repair; the modes' semantics; the launch
-sequence; the fallbacks; and a batch of more blocks than a grid holds."""
+sequence; the fallbacks; and a batch of more blocks than a grid holds.  More
+than 64 source rows: tests/test_gpu_family_generated_wide.py."""
 import ctypes as C
 
 import numpy as np

@@ -4,7 +4,8 @@ the lengths at which a tile, a lane or a workgroup is partly or wholly idle,
 the reports under `generated` against the numpy model of the contract
 (tests/scrub_model.py, run on the rows read back from the device) and, byte for
 byte, against `two_pass`; with and without locate, into a poisoned report
-buffer; the launch sequence; the fallbacks; and that the rows are only read."""
+buffer; the launch sequence; the fallbacks; and that the rows are only read.  More
+than 64 source rows: tests/test_gpu_family_generated_wide.py."""
 import numpy as np
 import pytest
 
